@@ -5,8 +5,13 @@ the HBM replay buffer + one QLearner.train on 32 sampled episodes (MultiAgentExp
 src/runs/train/ma_experiment.py:224-241). value = env steps (t_env increments, parallel_stepper.py:178-179)
 of all ranks / max-over-ranks time.
 
+A plain run (``--gpus N --steps K --warmup W``) sets up, warms up and times the headline leg only (``value``: config 2)
+and prints the result line. ``--full`` adds everything else the bench measures: the league and REFIL legs of
+``--mode auto`` and the CPU baselines. ``--dump-outputs DIR`` writes what the headline leg's last timed step computed
+(dump_outputs) as DIR/<name>.npy.
+
 Modes:
-  auto      (default) two legs in one run, both at every N:
+  auto      (default) ``value`` alone; with ``--full`` the league and REFIL legs beside it, all at every N:
             * ``value`` = config 2 per GPU: one learner vs the scripted AI on every rank (N independent learners,
               no data-path collective; weak scaling) -- the metric's "5v5 QMIX, 4096 envs, at 1/2/4/8 MI355X";
             * ``league`` = the league at the same N: config 3 at N = 2 (two PFSP self-play learners, opponent swap
@@ -346,6 +351,50 @@ def cpu_entry(c, leg_names):
             "legs": legs}
 
 
+# ---- --dump-outputs ------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+DUMP_ENVS = 64  # episodes of the last rollout that are written (a fixed, seeded sample of the B envs)
+
+
+def dump_outputs(path, exp):
+    """What the last timed iteration handed its caller, as ``path``/<name>.npy (float32; the learner's five
+    statistics float64), at most 64 MB in all:
+      params / target_params / square_avg   the learner's flat parameter, target and RMSprop buffers after the last
+                                            QLearner.train (agent, then mixer)
+      train_stats                           that train call's statistics (last_stats, in its key order)
+      rollout_ep_len / rollout_returns      the last rollout's per-env summary, every env
+      rollout_envs, rollout_<key>           a seeded sample of its episodes (env indices, then every key of the
+                                            episode batch for those envs, full stored length)
+    The run's seeds are fixed by its arguments, so two builds run with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    stepper, learner = exp.stepper, exp.home_learner
+    out = {"params": learner._flat.flat, "target_params": learner._tflat.flat, "square_avg": learner._sq}
+    out = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    out["train_stats"] = np.array(list(learner.last_stats.values()), dtype=np.float64)
+    last = stepper.last_run
+    out["rollout_ep_len"] = last["ep_len"].numpy().astype(np.float32)
+    out["rollout_returns"] = last["returns"].numpy().astype(np.float32)
+    batch = stepper.home_batch
+    B = batch.batch_size
+    ring = getattr(batch, "ring", None) if getattr(batch, "_data", None) is None else None
+    src = (ring if ring is not None else batch).data.transition_data
+    per_env = sum(v[0].numel() for v in src.values()) * 4
+    used = sum(v.nbytes for v in out.values()) + DUMP_ENVS * 4
+    n = max(1, min(B, DUMP_ENVS, (DUMP_LIMIT_BYTES - used) // per_env))
+    envs = np.sort(np.random.RandomState(0).choice(B, n, replace=False))
+    out["rollout_envs"] = envs.astype(np.float32)
+    # a ring batch's episodes sit in the replay ring's slots [slot0, slot0 + B) mod size: read the sampled rows there
+    rows = (envs + batch.slot0) % ring.buffer_size if ring is not None else envs
+    idx = torch.from_numpy(rows).to(batch.device)
+    for k, v in src.items():
+        out["rollout_" + k] = v.index_select(0, idx).float().cpu().numpy()
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 # ---- N > 1 without an outer launcher: start the ranks ourselves -----------------------------------------------
 def _free_port() -> int:
     import socket
@@ -420,7 +469,11 @@ def main():
     ap.add_argument("--league-teams", dest="league_teams", default="composed", choices=["composed", "mirror"],
                     help="league leg: per-player TeamComposer compositions (default) or the plan mirrored")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline leg: the league and REFIL legs of --mode auto and the CPU baselines")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write what the headline leg's last timed step computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--timing-every", type=int, default=1,
                     help="HIP events around every k-th rollout launch of the timed region (0: none, A/B only; "
                          "every launch when --steps < 2k)")
@@ -488,7 +541,8 @@ def main():
     from maleague.custom_logging import MainLogger
     from maleague.runs import MultiAgentExperiment
 
-    legs = {"auto": ["ai", "league", "refil"], "ai": ["ai"], "league": ["league"], "refil": ["refil"]}[a.mode]
+    legs = {"auto": ["ai", "league", "refil"] if a.full else ["ai"], "ai": ["ai"], "league": ["league"],
+            "refil": ["refil"]}[a.mode]
     results = {}
     for leg in legs:
         args, plan = make_args(leg, a, rank, local_rank)
@@ -533,13 +587,15 @@ def main():
         r.update({"workload": workload, "represents": cfg_name, "parallelism": parallelism, "envs_per_gpu": B,
                   "mean_episode_len": r["env_steps"] / max(1, a.steps * B * world)})
         results[leg] = r
+        if a.dump_outputs and leg == legs[0] and rank == 0:
+            dump_outputs(a.dump_outputs, exp)
         del exp, inst, stepper
         torch.cuda.empty_cache()
 
     head = legs[0]
     h = results[head]
     cpu, cpu_refil = None, None
-    if rank == 0 and world == 1 and head in ("ai", "refil") and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and head in ("ai", "refil") and not a.no_cpu_baseline:
         names = (["vector", "process"] if head == "ai" else []) + (["refil"] if "refil" in results else [])
         c = cpu_baselines(names, a)
         cpu = cpu_entry(c, ["refil"] if head == "refil" else ["vector", "process"])
