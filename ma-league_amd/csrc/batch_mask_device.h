@@ -9,8 +9,9 @@
 // episodes issued before the first is used -- one memory round trip, where the serial per-episode scans it replaces
 // waited once per episode and 64-step chunk -- then ballots: each episode's filled count and live bits are written
 // by one lane (no atomics on shared counters), Te is one atomicMax per episode. Every quantity is an integer count
-// (exact in float), so the results equal the scans bit for bit. Holds B <= waves * EPW episodes of T <= 32 *
-// MLG_MS_TW steps (mask_stats_fits; callers fall back to their scans otherwise).
+// (exact in float). That path holds B <= waves * EPW episodes of T <= 32 * MLG_MS_TW steps (mask_stats_fits); any
+// other shape takes batch_mask_scan, a wave per episode in turn over 64-step chunks, which produces the same
+// counts and therefore the same floats bit for bit. Callers use batch_mask, which picks the path.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -92,5 +93,62 @@ __device__ void batch_mask_stats(const int64_t* __restrict__ filled, const uint8
         msum[1] = (float)Te;
     }
 }
+
+// Any B and T: the same statistics with a wave per episode in turn (episodes wave, wave + waves, ...) and one memory
+// round trip per 64-step chunk. Uses S.te / S.total only.
+template <class SlotFn>
+__device__ void batch_mask_scan(const int64_t* __restrict__ filled, const uint8_t* __restrict__ term, int T1,
+                                SlotFn slot, int B, int T, float* __restrict__ msum, float* __restrict__ mixlen,
+                                MaskStatsLds& S) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+    if (tid == 0) S.te = S.total = 0;
+    __syncthreads();
+    for (int b = wave; b < B; b += nw) {  // filled steps counted with ballots
+        const int64_t base = slot(b) * T1;
+        int n = 0;
+        for (int t0 = 0; t0 < T; t0 += 64) {
+            const int t = t0 + lane;
+            n += __popcll(__ballot(t < T && filled[base + t] != 0));
+        }
+        if (lane == 0) atomicMax(&S.te, n);
+    }
+    __syncthreads();
+    const int Te = min(max(S.te, 2), T);
+    for (int b = wave; b < B; b += nw) {
+        const int64_t base = slot(b) * T1;
+        int c = 0, last = -1;
+        for (int t0 = 0; t0 < Te - 1; t0 += 64) {
+            const int t = t0 + lane;
+            const bool live = t < Te - 1 && filled[base + t] != 0 && (t == 0 || term[base + t - 1] == 0);
+            const uint64_t m = __ballot(live);
+            c += __popcll(m);
+            if (m) last = t0 + 63 - __builtin_clzll(m);
+        }
+        if (lane == 0) {
+            if (c) atomicAdd(&S.total, c);
+            if (mixlen) mixlen[b] = (float)(last + 1);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        msum[0] = (float)S.total;
+        msum[1] = (float)Te;
+    }
+}
+
+// The statistics by whichever path holds the batch (workgroup-uniform choice). mixlen may be null.
+template <int EPW, class SlotFn>
+__device__ __forceinline__ void batch_mask(const int64_t* __restrict__ filled, const uint8_t* __restrict__ term, int T1,
+                                           SlotFn slot, int B, int T, float* __restrict__ msum,
+                                           float* __restrict__ mixlen, MaskStatsLds& S) {
+    if (mask_stats_fits<EPW>(B, T, blockDim.x >> 6))
+        batch_mask_stats<EPW>(filled, term, T1, slot, B, T, msum, mixlen, S);
+    else
+        batch_mask_scan(filled, term, T1, slot, B, T, msum, mixlen, S);
+}
+
+// max_t_filled of the batch (msum[1]): the learners use transitions t < t_eff - 1 only; the sequential kernels stop
+// there and the per-t kernels skip the steps beyond
+__device__ __forceinline__ int t_eff(const float* msum) { return (int)msum[1]; }
 
 }  // namespace mlg

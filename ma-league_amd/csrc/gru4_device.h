@@ -13,12 +13,7 @@
 #include "mlg_device.h"
 
 // prefetch depth (steps) of the recurrences' per-step operand rings (even: the LDS double buffer alternates)
-#ifndef MLG_REC_PD
-#define MLG_REC_PD 4
-#endif
-#ifndef MLG_BWD_PD
-#define MLG_BWD_PD 4
-#endif
+constexpr int MLG_REC_PD = 4, MLG_BWD_PD = 4;
 
 constexpr int MLG_BWD_MAXA = 96;  // output-layer rows staged in LDS by the backward recurrences (host-checked)
 

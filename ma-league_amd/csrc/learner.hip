@@ -3,12 +3,12 @@
 //   pack        online/target agent + mixer weights -> kernel layouts (+ W_ih^T for backward)
 //   mask_sum    mask = filled[:, :-1] * (1 - terminated shifted) and its sum                (:36-42, :89-98)
 //   agent_in    fc1 + W_ih x for every (t, row), online + target, fully parallel               (:44-65)
-//   agent_rec   the recurrence only (W_hh h + gates), one workgroup per 16 sequence rows,
+//   agent_rec4  the recurrence only (W_hh h + gates), one workgroup per 4 sequence rows,
 //               wave w owns hidden chunk w with its W_hh rows in VGPRs; saves gates
 //   agent_q     fc2 for every (t, row), fully parallel
 //   mix_td      per (b, t) row: gather chosen Q, double-Q target, QMixer fwd (online+target),
 //               TD error, masked MSE partials, QMixer backward -> dQ and mixer deltas         (:55-98)
-//   agent_bwd   reverse-time GRU backward (dh carried in registers, dGH exchanged in LDS)    (:103)
+//   agent_bwd4  reverse-time GRU backward on 4-row tiles (gru4_device.h)                     (:103)
 //   agent_dx    dX = W_ih^T dGI * relu' for every (t, row), fully parallel
 //   wgrad       every weight/bias gradient as sum_rows delta^T x, one wave per 64x64 block and row chunk
 //               (deterministic slab reduction; MFMA with the row index as K)
@@ -25,9 +25,8 @@
 namespace {
 
 using WJobs = mlg::BJobsT<16>;
-using mlg::WJob;
-using mlg::job;
 using mlg::block_sum_1024;
+using mlg::t_eff;
 
 // ---- canonical flat parameter offsets (nn.Module named_parameters order) ------------------------
 struct AgentOffs {
@@ -163,44 +162,7 @@ __device__ __forceinline__ float mask_at(const MlgBatch& bt, int b, int t) {
     return m;
 }
 
-// One 1024-thread block: sum of the mask and max_t_filled (msum[0], msum[1]).
-__device__ void mask_sum_block(const MlgBatch& bt, int B, int T, float* __restrict__ msum, float* red) {
-    // msum[1] = max_t_filled (the reference's truncation, ma_experiment.py:235-239): the learner uses transitions
-    // t < max_t_filled - 1 only; the sequential kernels stop there and the per-t kernels skip the steps beyond
-    int mx = 0;  // a wave per episode: filled steps counted with ballots
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (int b = wave; b < B; b += nw) {
-        const int64_t base = bslot(bt, b) * bt.T1;
-        int n = 0;
-        for (int t0 = 0; t0 < T; t0 += 64) {
-            const int t = t0 + lane;
-            n += __popcll(__ballot(t < T && bt.filled[base + t] != 0));
-        }
-        mx = n > mx ? n : mx;
-    }
-    red[threadIdx.x] = (float)mx;
-    __syncthreads();
-    for (int w = blockDim.x / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    const int Te = (int)fminf(fmaxf(red[0], 2.f), (float)T);
-    __syncthreads();
-    float s = 0.f;
-    for (int i = threadIdx.x; i < B * (Te - 1); i += blockDim.x) s += mask_at(bt, i / (Te - 1), i % (Te - 1));
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = blockDim.x / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        msum[0] = red[0];
-        msum[1] = (float)Te;
-    }
-}
-
-// Fused learner prologue (one launch instead of eight): block 0 sums the mask (mask_sum_block); the other blocks
+// Fused learner prologue (one launch instead of eight): block 0 sums the mask (batch_mask_device.h); the other blocks
 // pack the online / target agent weights (pack_agent_elem), transpose W_ih (dX pass), pack the online / target
 // QMixer hypernets (pack_mixer_elem) and zero the sparse delta buffers d2 and dq.
 struct PrepJob {
@@ -228,7 +190,6 @@ static_assert(sizeof(PrepJob) <= 3072, "PrepJob must fit the kernel-argument seg
 
 __global__ void __launch_bounds__(1024) prep_kernel(PrepJob J) {
     if (blockIdx.x == 0) {
-        __shared__ float red[1024];
         __shared__ int32_t srows[MLG_INLINE_ROWS];
         __shared__ mlg::MaskStatsLds ms;
         MlgBatch b2 = J.bt;
@@ -241,11 +202,8 @@ __global__ void __launch_bounds__(1024) prep_kernel(PrepJob J) {
             b2.rows = srows;
         }
         constexpr int EPW = 4;  // episodes per wave: 16 waves cover batches of up to 64 episodes
-        if (mlg::mask_stats_fits<EPW>(J.B, J.T, blockDim.x / 64))  // one round trip (batch_mask_device.h)
-            mlg::batch_mask_stats<EPW>(b2.filled, b2.terminated, b2.T1, [&](int b) { return bslot(b2, b); }, J.B, J.T,
-                                       J.msum, nullptr, ms);
-        else
-            mask_sum_block(b2, J.B, J.T, J.msum, red);
+        mlg::batch_mask<EPW>(b2.filled, b2.terminated, b2.T1, [&](int b) { return bslot(b2, b); }, J.B, J.T, J.msum,
+                             nullptr, ms);
         return;
     }
     const int64_t na = J.L.gsp,  // the learner reads no pre-split rollout sections (gsp, w1s)
@@ -309,8 +267,6 @@ struct LStamps {
     __device__ void flush(int) {}
 };
 #endif
-__device__ __forceinline__ int t_eff(const float* msum) { return (int)msum[1]; }
-
 
 // ================================================================================================
 // 16-row x 16-feature tile product with the activation operand in LDS, row-major [16][lda]:
@@ -329,7 +285,7 @@ __device__ __forceinline__ floatx4 tile_mm_lds(const float* __restrict__ W, int6
 // forward, split into the parallel (non-recurrent) and the recurrent part:
 //   agent_in_kernel  (t, tile, net): dense input row (online), x = relu(fc1(inputs)), and
 //                    GI = [b_ir + b_hr + W_ir x | b_iz + b_hz + W_iz x | b_in + W_in x]  for every timestep
-//   agent_rec_kernel (tile, net):    h_t = GRU(GI_t, h_{t-1}) with W_hh in VGPRs, GI prefetched a step ahead
+//   agent_rec4_kernel (tile4, net):  h_t = GRU(GI_t, h_{t-1}) with W_hh in VGPRs, GI prefetched ahead
 //   agent_q_kernel   (t, tile, net): q = fc2(h_t)
 // The accumulation order per output is the one of the fused unroll (bias, W_ih x chunks, W_hh h chunks).
 // grid (ntiles, T, 2), HC waves: wave w computes x chunk w, then GI chunks w, w + HC, w + 2 HC.
@@ -395,89 +351,6 @@ __global__ void __launch_bounds__(512) agent_in_kernel(LCfg c, MlgBatch bt, Agen
         floatx4 acc = q < 2 ? ld4(P + L.brz + q * H + w * 16 + 4 * g) : ld4(P + L.bih + 2 * H + w * 16 + 4 * g);
         acc = tile_mm_lds(P + L.wih, H, q * H + w * 16, xs, LDA, HC, acc, lane);
         if (valid) *reinterpret_cast<floatx4*>(gi + ((int64_t)t * R + r) * 3 * H + q * H + w * 16 + 4 * g) = acc;
-    }
-}
-
-// grid (2 * ntiles): blockIdx < ntiles online (saves gates), else target. HC waves, wave w owns chunk w.
-template <int H>
-__global__ void __launch_bounds__(512) agent_rec_kernel(LCfg c, AgentLayout L, const float* __restrict__ Pon,
-                                                        const float* __restrict__ Ptg, const float* __restrict__ gi_on,
-                                                        const float* __restrict__ gi_tg, float* __restrict__ hs_on,
-                                                        float* __restrict__ hs_tg, float* __restrict__ ws_gr,
-                                                        float* __restrict__ ws_gz, float* __restrict__ ws_gn,
-                                                        float* __restrict__ ws_ghn, const float* __restrict__ msum) {
-    constexpr int HC = H / 16;
-    constexpr int LDA = H + 4;
-    __shared__ __attribute__((aligned(16))) float hs[2][16 * LDA];
-    const int Te = t_eff(msum);
-    const int ntiles = (c.R + 15) / 16;
-    const bool online = blockIdx.x < ntiles;
-    const int tile = online ? blockIdx.x : blockIdx.x - ntiles;
-    const float* P = online ? Pon : Ptg;
-    const float* gi = online ? gi_on : gi_tg;
-    float* hsg = online ? hs_on : hs_tg;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int col = lane & 15, g = lane >> 4;
-    const int R = c.R;
-    const int r = tile * 16 + col;
-    const bool valid = r < R;
-    const int f0 = w * 16 + 4 * g;  // this lane's 4 hidden features
-    floatx4 wr[3][HC];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int kc = 0; kc < HC; ++kc) wr[q][kc] = ld4(P + L.whh + (int64_t)(q * H + w * 16 + col) * H + kc * 16 + 4 * g);
-    const floatx4 bhn = ld4(P + L.bhh + 2 * H + f0);
-    for (int i = tid; i < 16 * LDA; i += blockDim.x) hs[0][i] = 0.f;
-    if (valid) *reinterpret_cast<floatx4*>(hsg + (int64_t)r * H + f0) = floatx4{0.f, 0.f, 0.f, 0.f};  // HS[0]
-    const int rr = valid ? r : 0;
-    auto gi_at = [&](int t, int q) { return ld4(gi + ((int64_t)t * R + rr) * 3 * H + q * H + f0); };
-    // input gates prefetched a step ahead into ping-pong registers: the 2x-unrolled loop consumes them in place,
-    // so the wait for the prefetch never covers this step's stores (a register copy would force vmcnt(0))
-    const __amdgpu_buffer_rsrc_t rs_h = mlg_rsrc(hsg), rs_r = mlg_rsrc(ws_gr), rs_z = mlg_rsrc(ws_gz),
-                                 rs_n = mlg_rsrc(ws_gn), rs_hn = mlg_rsrc(ws_ghn);
-    auto step = [&](int t, const floatx4 (&gc)[3], floatx4 (&gn)[3], int cur) {
-        const int tn = t + 1 < Te ? t + 1 : t;  // unconditional (clamped) prefetch: no branch in the VMEM stream
-#pragma unroll
-        for (int q = 0; q < 3; ++q) gn[q] = gi_at(tn, q);
-        floatx4 ar = gc[0], az = gc[1];
-        floatx4 ahn = bhn;
-        const float* hrow = hs[cur] + col * LDA + 4 * g;
-#pragma unroll
-        for (int kc = 0; kc < HC; ++kc) {
-            const floatx4 hin = ld4(hrow + kc * 16);
-            ar = mfma_chunk(wr[0][kc], hin, ar);
-            az = mfma_chunk(wr[1][kc], hin, az);
-            ahn = mfma_chunk(wr[2][kc], hin, ahn);
-        }
-        const floatx4 hp = ld4(hs[cur] + col * LDA + f0);
-        floatx4 rg, zg, ng, hn;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            rg[q] = fast_sigmoid(ar[q]);
-            zg[q] = fast_sigmoid(az[q]);
-            ng[q] = fast_tanh(gc[2][q] + rg[q] * ahn[q]);
-            hn[q] = ng[q] + zg[q] * (hp[q] - ng[q]);
-        }
-        *reinterpret_cast<floatx4*>(hs[cur ^ 1] + col * LDA + f0) = hn;
-        const int64_t o = ((int64_t)t * R + r) * H + f0;
-        st4_if(rs_h, o + (int64_t)R * H, hn, valid);  // HS[t + 1]
-        st4_if(rs_r, o, rg, valid && online);          // gates are saved by the online net only
-        st4_if(rs_z, o, zg, valid && online);
-        st4_if(rs_n, o, ng, valid && online);
-        st4_if(rs_hn, o, ahn, valid && online);
-        __syncthreads();
-    };
-    floatx4 ga[3], gb[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) ga[q] = gi_at(0, q);
-    __syncthreads();
-    // step 0 peeled: the loop is entered in the same VMEM state as its back edge (prefetch loads, then the
-    // stores), so the compiler's merged waitcnt for the prefetched gates still lets the stores drain
-    step(0, ga, gb, 0);
-    for (int t = 1; t < Te; t += 2) {
-        step(t, gb, ga, 1);
-        if (t + 1 < Te) step(t + 1, ga, gb, 0);
     }
 }
 
@@ -1452,109 +1325,8 @@ __global__ void __launch_bounds__(128) mix_td2_kernel(LCfg c, MlgBatch bt, MixPt
 }
 
 // ================================================================================================
-// reverse-time GRU backward; wave w owns hidden chunk w. W_hh^T rows of the chunk live in VGPRs, the
-// step's gate values are prefetched one step ahead, dGH is exchanged through LDS (double buffered).
-// dh_{t-1} = dh * z + W_hh^T dGH.  dX = W_ih^T dGI does not feed the recurrence: agent_dx_kernel.
-template <int H>
-__global__ void __launch_bounds__(512) agent_bwd_kernel(LCfg c, MlgBatch bt, AgentLayout L, const float* __restrict__ P,
-                                                        const float* __restrict__ ws_hs, const float* __restrict__ ws_gr,
-                                                        const float* __restrict__ ws_gz, const float* __restrict__ ws_gn,
-                                                        const float* __restrict__ ws_ghn, const float* __restrict__ dqv,
-                                                        float* __restrict__ dgi, float* __restrict__ dgh,
-                                                        const float* __restrict__ msum) {
-    constexpr int LDG = 3 * H + 4;
-    constexpr int KC = 3 * H / 16;
-    __shared__ __attribute__((aligned(16))) float sgh[2][16 * LDG];
-    __shared__ __attribute__((aligned(16))) float w2s[MLG_BWD_MAXA * H];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int col = lane & 15, g = lane >> 4;
-    const int r = blockIdx.x * 16 + col;
-    const bool valid = r < c.R;
-    const int b = valid ? r / c.N : 0, n = valid ? r % c.N : 0;
-    const int R = c.R, N = c.N;
-    const int f0 = w * 16 + 4 * g;
-    // A operand of W_hh^T: row = feature w*16 + col, K = gate-row k: W_hh[k][feature]
-    floatx4 wt[KC];
-#pragma unroll
-    for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) wt[kc][q] = P[L.whh + (int64_t)(kc * 16 + 4 * g + q) * H + w * 16 + col];
-    const int rr = valid ? r : 0;
-    for (int i = tid; i < c.A * H; i += blockDim.x) w2s[i] = P[L.w2 + i];  // fc2 rows for dh += dq W2[a]
-    const int64_t abase = bslot(bt, b) * bt.T1 * N + n;  // loop-invariant: no dependent slot-map load per step
-    struct Step {
-        floatx4 rg, zg, ng, ghn, hp;
-        float dq;
-        int a;
-    };
-    auto load_step = [&](int t, Step& s) {
-        const int64_t o = ((int64_t)t * R + rr) * H + f0;
-        s.rg = ld4(ws_gr + o);
-        s.zg = ld4(ws_gz + o);
-        s.ng = ld4(ws_gn + o);
-        s.ghn = ld4(ws_ghn + o);
-        s.hp = ld4(ws_hs + o);  // HS[t] = h_{t-1}
-        const int tq = t < c.T - 1 ? t : c.T - 2;  // unconditional (clamped) loads; dq / action unused at T-1
-        s.dq = dqv[(int64_t)tq * R + rr];
-        s.a = t < c.T - 1 ? (int)bt.actions[abase + (int64_t)tq * N] : -1;
-    };
-    const int Te = t_eff(msum);
-    if (valid) {  // steps past max_t_filled: zero deltas (wgrad rows)
-        for (int t = Te; t < c.T; ++t) {
-            const int64_t o3 = ((int64_t)t * R + r) * 3 * H + f0;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                *reinterpret_cast<floatx4*>(dgi + o3 + q * H) = floatx4{0.f, 0.f, 0.f, 0.f};
-                *reinterpret_cast<floatx4*>(dgh + o3 + q * H) = floatx4{0.f, 0.f, 0.f, 0.f};
-            }
-        }
-    }
-    floatx4 dh = {0.f, 0.f, 0.f, 0.f};
-    // a step's saved gates are prefetched one step ahead into ping-pong registers (2x-unrolled loop, no copies:
-    // the wait for them never covers the previous step's stores); W2 rows come from LDS, not a dependent load
-    const __amdgpu_buffer_rsrc_t rs_gi = mlg_rsrc(dgi), rs_gh = mlg_rsrc(dgh);
-    auto step = [&](int t, const Step& s, Step& nx, int cur) {
-        load_step(t > 0 ? t - 1 : 0, nx);
-        if (valid && s.a >= 0) dh += s.dq * ld4(w2s + s.a * H + f0);
-        floatx4 drp, dzp, dnp, dghn, dhd;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float dn = dh[q] * (1.f - s.zg[q]);
-            const float dz = dh[q] * (s.hp[q] - s.ng[q]);
-            dhd[q] = dh[q] * s.zg[q];
-            dnp[q] = dn * (1.f - s.ng[q] * s.ng[q]);
-            const float dr = dnp[q] * s.ghn[q];
-            drp[q] = dr * s.rg[q] * (1.f - s.rg[q]);
-            dzp[q] = dz * s.zg[q] * (1.f - s.zg[q]);
-            dghn[q] = dnp[q] * s.rg[q];
-        }
-        float* gh = sgh[cur] + col * LDG;
-        *reinterpret_cast<floatx4*>(gh + f0) = drp;
-        *reinterpret_cast<floatx4*>(gh + H + f0) = dzp;
-        *reinterpret_cast<floatx4*>(gh + 2 * H + f0) = dghn;
-        const int64_t o3 = ((int64_t)t * R + r) * 3 * H + f0;
-        st4_if(rs_gi, o3, drp, valid);
-        st4_if(rs_gi, o3 + H, dzp, valid);
-        st4_if(rs_gi, o3 + 2 * H, dnp, valid);
-        st4_if(rs_gh, o3, drp, valid);
-        st4_if(rs_gh, o3 + H, dzp, valid);
-        st4_if(rs_gh, o3 + 2 * H, dghn, valid);
-        __syncthreads();
-        floatx4 dprev = dhd;
-        const float* ghr = sgh[cur] + col * LDG + 4 * g;
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc) dprev = mfma_chunk(wt[kc], ld4(ghr + kc * 16), dprev);
-        dh = dprev;
-    };
-    Step sa, sb;
-    load_step(Te - 1, sa);
-    step(Te - 1, sa, sb, 0);  // peeled (see agent_rec_kernel)
-    for (int t = Te - 2; t >= 0; t -= 2) {
-        step(t, sb, sa, 1);
-        if (t > 0) step(t - 1, sa, sb, 0);
-    }
-}
-
+// reverse-time GRU backward: dh_{t-1} = dh * z + W_hh^T dGH.  dX = W_ih^T dGI does not feed the recurrence:
+// agent_dx_kernel.
 // The backward recurrence on 4-row tiles (v_mfma_f32_4x4x1_16b_f32, as agent_rec4_kernel). Wave w owns hidden
 // features 16w..16w+15; block b = 4kq + fg accumulates W_hh^T dGH for features 16w + 4fg + i over the K quarter
 // kq (48 of the 3H gate rows, W_hh columns in VGPRs). The four quarter partials are summed across the wave's
@@ -1648,23 +1420,9 @@ __global__ void __launch_bounds__(1024) finish_kernel(const float* __restrict__ 
                                                       int n_nrm, float* __restrict__ tsync, double* __restrict__ trained) {
     __shared__ float red[1024];
     const int tid = threadIdx.x;
-    // this thread's parameter, gradient and square average, requested before the norm reduction they wait for
-    const int64_t ip = (int64_t)blockIdx.x * blockDim.x + tid;
-    const bool has = ip < n_params;
-    const float g0 = has ? grads[ip] : 0.f, sq0 = has ? sq[ip] : 0.f, p0 = has ? params[ip] : 0.f;
-    float s = 0.f;
-    for (int i = tid; i < n_nrm; i += blockDim.x) s += nrm_part[i];
-    const float norm = sqrtf(block_sum_1024(s, red));
-    const float coef = fminf(max_norm / (norm + 1e-6f), 1.f);  // torch clip_grad_norm_ (clamped coef)
-    if (has) {
-        const float gi = g0 * coef;
-        grads[ip] = gi;
-        const float a = alpha * sq0 + (1.f - alpha) * gi * gi;  // RMSprop square_avg
-        sq[ip] = a;
-        const float pn = p0 - lr * gi / (sqrtf(a) + eps);
-        params[ip] = pn;
-        if (tsync) tsync[ip] = pn;  // target update due after this step (q_learner.py:127-128), same launch
-    }
+    // target update due after this step (q_learner.py:127-128): tsync
+    const float norm = mlg::clip_rmsprop_step(params, grads, sq, n_params, nrm_part, n_nrm, lr, alpha, eps, max_norm,
+                                              tsync, red);
     // the four stat sums on blocks 0..3 (one each, same order as one block doing all four: bit-identical), so no
     // block runs four block reductions after its parameter slice
     const float ms = msum_p[0];
@@ -1866,12 +1624,11 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     pj.HE = c.HE;
     pj.mixer = c.mixer;
     // split mixer (default for the FAST shapes): the hypernetwork forward rides in the recurrence launch
-    // (rec4_mixpre_kernel), mix_td2_kernel does the rest; MLG_MIX_FUSED=1: the one-kernel mix_td
-    static const bool rec16 = getenv("MLG_LEARNER_REC16") != nullptr;  // A/B switch: the 16-row tile recurrence
+    // (rec4_mixpre_kernel), mix_td2_kernel does the rest. VDN runs the one-kernel mix_td; MLG_MIX_GENERIC=1
+    // forces its generic form (the path of the other shapes; read per call, so a test can set it)
     const bool fast_mix = p.mp.Sp <= 64 && c.N <= MIXPF_N && c.A <= MIXPF_A && !getenv("MLG_MIX_GENERIC");
-    static const bool fused_env = getenv("MLG_MIX_FUSED") != nullptr;
     const int threads = (c.H / 16) * 64;
-    const bool split_mix = c.mixer == 2 && fast_mix && !fused_env && !rec16 && threads % 128 == 0;
+    const bool split_mix = c.mixer == 2 && fast_mix && threads % 128 == 0;
     pj.d2 = ws + p.w.d2;  // d2 is sparse: zero it (and dq) every call
     pj.dq = ws + p.w.dq;
     pj.n_d2 = (int64_t)c.T * c.R * c.A;
@@ -1921,11 +1678,7 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
                            c, p.L, ws + p.w.p_on, ws + p.w.p_tg, ws + p.w.gi_on, ws + p.w.gi_tg, ws + p.w.hs,
                            ws + p.w.hs_tg, ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, ws + p.w.msum, bt, Mon,
                            Mtg, p.mp, hy);
-    } else if (rec16)
-        hipLaunchKernelGGL((agent_rec_kernel<H>), dim3(2 * ntiles), dim3(threads), 0, s, c, p.L, ws + p.w.p_on,
-                           ws + p.w.p_tg, ws + p.w.gi_on, ws + p.w.gi_tg, ws + p.w.hs, ws + p.w.hs_tg, ws + p.w.gr,
-                           ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, ws + p.w.msum);
-    else
+    } else
         hipLaunchKernelGGL((agent_rec4_kernel<H>), dim3(2 * ((c.R + 3) / 4)), dim3(threads), 0, s, c, p.L,
                            ws + p.w.p_on, ws + p.w.p_tg, ws + p.w.gi_on, ws + p.w.gi_tg, ws + p.w.hs, ws + p.w.hs_tg,
                            ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, ws + p.w.msum);
@@ -1951,16 +1704,12 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     int ta, tb;
     int64_t ra, rb;
     const WJobs JA = mlg::bjob_view(J, 3, J.n, &ta, &ra), JB = mlg::bjob_view(J, 0, 3, &tb, &rb);
-    const bool fused = !rec16 && H == 64 && threads == 256;
-    if (fused) {
+    constexpr bool fused = H == 64;  // 4 waves, as the wgrad workgroups
+    if constexpr (fused) {
         const int nbwd = (c.R + 3) / 4;
         hipLaunchKernelGGL((bwd4_wgrad_kernel<H>), dim3((unsigned)(nbwd + (ta + 3) / 4)), dim3(256), 0, s, c, bt, p.L,
                            ws + p.w.p_on, ws + p.w.hs, ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, ws + p.w.dq,
                            ws + p.w.dgi, ws + p.w.dgh, ws + p.w.msum, JA, ws + p.w.slab, nbwd);
-    } else if (rec16) {
-        hipLaunchKernelGGL((agent_bwd_kernel<H>), dim3(ntiles), dim3(threads), 0, s, c, bt, p.L, ws + p.w.p_on,
-                           ws + p.w.hs, ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, ws + p.w.dq, ws + p.w.dgi,
-                           ws + p.w.dgh, ws + p.w.msum);
     } else {
         hipLaunchKernelGGL((agent_bwd4_kernel<H>), dim3((c.R + 3) / 4), dim3(threads), 0, s, c, bt, p.L, ws + p.w.p_on,
                            ws + p.w.hs, ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, ws + p.w.dq, ws + p.w.dgi,

@@ -20,13 +20,8 @@
 
 using namespace refil;
 
-// Phase functions of the rollout are kept out of line by default: inlined, the compiler hoists weight loads across
-// phases and the kernel needs > 512 registers (1 wave per SIMD, spills); out of line it fits 2 waves per SIMD.
-#ifdef MLG_REFIL_NOINLINE
-#define RO_PHASE __device__ __attribute__((noinline))
-#else
+// Phase functions of the rollouts: inlining is left to the compiler
 #define RO_PHASE __device__ inline
-#endif
 
 #ifdef MLG_STAMPS
 // Diagnostic build only: per-wave cycle counts of the REFIL rollout phases, g_refil_stamps[wave][32]
@@ -210,13 +205,12 @@ __device__ inline void entity_block(const float* __restrict__ P, const RAgent& L
 // stays in registers as in_trans' B operand; only q (agent rows, [NAS][LDX]) and k | v ([NE][LDKV]) go to LDS.
 constexpr int LDKV = 2 * EMB + 4;
 template <int KC1>
-__device__ inline void entity_block_reg(const float* __restrict__ P, const RAgent& L, const float* win, int ldin,
-                                        const floatx4 (&xin)[KC1], float* qs, float* kvs, const uint32_t* mrow, int nq,
-                                        int ne, float* o, int lane) {
+__device__ inline void entity_block_reg(const float* __restrict__ P, const RAgent& L, const floatx4 (&xin)[KC1],
+                                        float* qs, float* kvs, const uint32_t* mrow, int nq, int ne, float* o,
+                                        int lane) {
     const int col = lane & 15;
     floatx4 x1[4];
     bias_init<4>(x1, P + L.b1, 0, lane);
-#if !defined(MLG_REFIL_INTRANS_F32)
     if constexpr (KC1 == 2) {  // K1 = 32: one split-bf16 K step over xin[0], xin[1] (wsp tiles 20-23, kk = 0)
         const u32x4* ws = reinterpret_cast<const u32x4*>(P + L.wsp) + lane;
         bf16x8 w[12];
@@ -237,18 +231,12 @@ __device__ inline void entity_block_reg(const float* __restrict__ P, const RAgen
     } else {
         mm_reg<4, KC1>(x1, P + L.w1, L.K1, 0, xin, lane);
     }
-#else
-    mm_reg<4, KC1>(x1, P + L.w1, L.K1, 0, xin, lane);
-#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i) x1[i] = relu4(x1[i]);
-#if !defined(MLG_REFIL_INTRANS_F32)
     // in_trans as split-bf16 fp32 emulation (gru_tile_b16's scheme): x1 split once per 32-wide K step (K slot (g, i)
     // of step kk = the lane's own registers x1[2kk], x1[2kk + 1]), the weights pre-split in that K order (packed
     // section wsp), streamed in stages of 3 output tiles with the next stage's 18 loads issued before the current
     // stage's MFMAs. Tiles 0-3 = q (agent rows only), 4-11 = k | v. 144 bf16 MFMAs instead of 192 f32 MFMAs.
-    (void)win;
-    (void)ldin;
     {
         Split3 xs[2];
 #pragma unroll
@@ -286,25 +274,6 @@ __device__ inline void entity_block_reg(const float* __restrict__ P, const RAgen
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-#else
-    {  // q: only the agent rows are queried
-        floatx4 acc[4];
-        bias_init<4>(acc, nullptr, 0, lane);
-        mm_reg<4, 4>(acc, win, ldin, 0, x1, lane);
-        if (col < NAS) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) st_row(qs, LDX, i, acc[i], lane);
-        }
-    }
-#pragma unroll
-    for (int m0 = 4; m0 < 12; m0 += 4) {  // k, v
-        floatx4 acc[4];
-        bias_init<4>(acc, nullptr, 0, lane);
-        mm_reg<4, 4>(acc, win, ldin, m0, x1, lane);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) st_row(kvs, LDKV, m0 - 4 + i, acc[i], lane);
-    }
-#endif
     wave_sync();
     if (nq <= 8)
         attn_fwd_half(qs, LDX, kvs, kvs + EMB, LDKV, mrow, nq, ne, o, LDX, lane);
@@ -314,32 +283,25 @@ __device__ inline void entity_block_reg(const float* __restrict__ P, const RAgen
 }
 
 // out_trans (+ post mask) -> fc2 -> ReLU -> GRUCell on the 16-row tile; h in/out (D layout).
-// dead: bit r set = tile row r is a masked agent (post_mask, attention.py:75-76). wout / w2 may live in LDS (ld).
-__device__ inline void agent_tile_post_w(const float* __restrict__ P, const RAgent& L, const float* wout, int ldo,
-                                         const float* w2, int ld2, const float* o, uint32_t dead, floatx4 (&h)[4],
-                                         int lane) {
+// dead: bit r set = tile row r is a masked agent (post_mask, attention.py:75-76).
+RO_PHASE void agent_tile_post(const float* __restrict__ P, const RAgent& L, const float* o, uint32_t dead,
+                              floatx4 (&h)[4], int lane) {
     const int col = lane & 15;
     floatx4 x2[4], x3[4];
     bias_init<4>(x2, P + L.bout, 0, lane);
-    mm_lds<4>(x2, wout, ldo, 0, o, LDX, EMB / 16, lane);
+    mm_lds<4>(x2, P + L.wout, EMB, 0, o, LDX, EMB / 16, lane);
     if ((dead >> col) & 1u) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) x2[i] = floatx4{0.f, 0.f, 0.f, 0.f};
     }
     bias_init<4>(x3, P + L.b2, 0, lane);
-    mm_reg<4, 4>(x3, w2, ld2, 0, x2, lane);
+    mm_reg<4, 4>(x3, P + L.w2, EMB, 0, x2, lane);
 #pragma unroll
     for (int i = 0; i < 4; ++i) x3[i] = relu4(x3[i]);
-#if defined(MLG_REFIL_GRU_PLAIN)
-    gru_tile(P + L.wih, P + L.whh, P + L.bih, P + L.bhh, P + L.brz, x3, h, lane);
-#elif defined(MLG_REFIL_GRU_F32)  // A/B: f32 MFMA products (round 1)
-    gru_tile_pipe(P + L.wih, P + L.whh, P + L.bih, P + L.bhh, P + L.brz, x3, h, lane);
-#else
     gru_tile_b16(P, L, x3, h, lane);
-#endif
 }
 
-// Rollout form of agent_tile_post_w with out_trans and fc2 as split-bf16 fp32 emulation: o (LDS rows) is split once
+// Rollout form of agent_tile_post with out_trans and fc2 as split-bf16 fp32 emulation: o (LDS rows) is split once
 // per 32-wide K step in the wsp K order (lane (col, g) reads features (2kk) * 16 + 4g .. + 3 and (2kk + 1) * 16 + 4g
 // .. + 3 of row col), x2 from its D-layout registers; weights from the wsp tiles 12-19, all 48 loads issued up front.
 __device__ inline void agent_tile_post_b16(const float* __restrict__ P, const RAgent& L, const float* o, uint32_t dead,
@@ -384,11 +346,6 @@ __device__ inline void agent_tile_post_b16(const float* __restrict__ P, const RA
 #pragma unroll
     for (int i = 0; i < 4; ++i) x3[i] = relu4(x3[i]);
     gru_tile_b16(P, L, x3, h, lane);
-}
-
-RO_PHASE void agent_tile_post(const float* __restrict__ P, const RAgent& L, const float* o, uint32_t dead,
-                              floatx4 (&h)[4], int lane) {
-    agent_tile_post_w(P, L, P + L.wout, EMB, P + L.w2, EMB, o, dead, h, lane);
 }
 
 // fc3 action tile `at` of the tile rows (q masked to 0 for dead rows, entity_rnn_agent.py:61)
@@ -531,46 +488,20 @@ __device__ inline void ro_zero_tail(const MlgEntityBatch& bt, const RoArgs& a, i
     z(bt.filled, 8);
 }
 
-// Workgroup = RO_WAVES waves; every wave owns two envs for the whole episode (no cross-wave dependency after the
-// prologue); the waves share one LDS copy of in_trans / out_trans / fc2 (padded rows, conflict-free A reads).
+// Workgroup = RO_WAVES waves; every wave owns two envs for the whole episode (no cross-wave dependency); the waves
+// stream the pre-split weights from L2 (69 KB of LDS per workgroup).
 constexpr int RO_WAVES = 4;
-constexpr int LDW = EMB + 4;
-// fp32 in_trans / out_trans / fc2 copies in LDS only for the f32 A/B forms; the split-bf16 default streams the
-// pre-split weights from L2 (69 KB of LDS per workgroup instead of 156 KB)
-#if defined(MLG_REFIL_INTRANS_F32) || defined(MLG_REFIL_POST_F32) || defined(MLG_REFIL_GRU_PLAIN) || defined(MLG_REFIL_GRU_F32)
-#define RO_LDS_WEIGHTS 1
-#endif
 struct RoShared {
-#ifdef RO_LDS_WEIGHTS
-    float win[3 * EMB * LDW];
-    float wout[EMB * LDW];
-    float w2[EMB * LDW];
-#endif
     RoLds S[RO_WAVES];
 };
 
 template <int KC1>
-#ifdef MLG_REFIL_W2  // experiment: two waves per SIMD (<= 256 VGPR + AGPR per lane)
-#define RO_OCC __attribute__((amdgpu_waves_per_eu(2, 2)))
-#else
-#define RO_OCC
-#endif
-__global__ void __launch_bounds__(64 * RO_WAVES) RO_OCC refil_rollout_kernel(MlgEntityEnvSpec spec, MlgEnvState st, RAgent L,
+__global__ void __launch_bounds__(64 * RO_WAVES) refil_rollout_kernel(MlgEntityEnvSpec spec, MlgEnvState st, RAgent L,
                                                                       const float* __restrict__ P, MlgEntityBatch bt,
                                                                       MlgRunInfo info, RoArgs a, float eps,
                                                                       int test_mode) {
     extern __shared__ __attribute__((aligned(16))) float ro_smem[];
     RoShared& SH = *reinterpret_cast<RoShared*>(ro_smem);
-#ifdef RO_LDS_WEIGHTS
-    for (int i = threadIdx.x; i < 3 * EMB * EMB; i += blockDim.x) SH.win[(i / EMB) * LDW + i % EMB] = P[L.win + i];
-    for (int i = threadIdx.x; i < EMB * EMB; i += blockDim.x) {
-        SH.wout[(i / EMB) * LDW + i % EMB] = P[L.wout + i];
-        SH.w2[(i / EMB) * LDW + i % EMB] = P[L.w2 + i];
-    }
-    const float* sh_win = SH.win;
-#else
-    const float* sh_win = nullptr;
-#endif
     __syncthreads();
     const int wave = threadIdx.x >> 6;
     RoLds& S = SH.S[wave];
@@ -670,7 +601,7 @@ __global__ void __launch_bounds__(64 * RO_WAVES) RO_OCC refil_rollout_kernel(Mlg
                     xin[kc][r] = v;
                 }
             stp.mark(0);
-            entity_block_reg<KC1>(Pw, L, sh_win, LDW, xin, S.q, S.kv, S.om[ee], a.NA, a.U, S.o + ee * NAS * LDX, lane);
+            entity_block_reg<KC1>(Pw, L, xin, S.q, S.kv, S.om[ee], a.NA, a.U, S.o + ee * NAS * LDX, lane);
             stp.mark(1);
             rows += (uint64_t)a.NA;
         }
@@ -681,23 +612,16 @@ __global__ void __launch_bounds__(64 * RO_WAVES) RO_OCC refil_rollout_kernel(Mlg
             m |= ~((1u << a.NA) - 1u) & 0xFFu;  // padding rows >= n_agents
             dead |= (m & 0xFFu) << (8 * ee);
         }
-#if defined(MLG_REFIL_POST_F32) || defined(MLG_REFIL_GRU_PLAIN) || defined(MLG_REFIL_GRU_F32)
-        agent_tile_post_w(Pw, L, SH.wout, LDW, SH.w2, LDW, S.o, dead, h, lane);
-#else
         agent_tile_post_b16(Pw, L, S.o, dead, h, lane);
-#endif
         stp.mark(2);
         // fc3 + masked argmax + epsilon-greedy
         const int re = col >> 3, rn = col & 7;
         const uint32_t avm = (rn < a.NA) ? S.av[re][rn] : 1u;
         ArgmaxState as{-INFINITY, 1 << 30};
-#if !defined(MLG_REFIL_POST_F32) && !defined(MLG_REFIL_GRU_PLAIN) && !defined(MLG_REFIL_GRU_F32)
         Split3 hs3[2];  // fc3 as split-bf16 (wsp tiles 24-25; Ap <= 32 host-checked)
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) hs3[kk] = split3(h[2 * kk], h[2 * kk + 1]);
-#endif
         for (int at = 0; at < L.Ap / 16; ++at) {
-#if !defined(MLG_REFIL_POST_F32) && !defined(MLG_REFIL_GRU_PLAIN) && !defined(MLG_REFIL_GRU_F32)
             floatx4 q;
             {
                 const u32x4* ws = reinterpret_cast<const u32x4*>(Pw + L.wsp) + lane;
@@ -715,9 +639,6 @@ __global__ void __launch_bounds__(64 * RO_WAVES) RO_OCC refil_rollout_kernel(Mlg
                 }
                 if ((dead >> (lane & 15)) & 1u) q = floatx4{0.f, 0.f, 0.f, 0.f};
             }
-#else
-            const floatx4 q = agent_q(Pw, L, h, at, dead, lane);
-#endif
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int ac = at * 16 + 4 * g + r;

@@ -468,101 +468,8 @@ __device__ __forceinline__ void attn_bwd(const float* qkv, const float* P, int n
 }
 
 // ---- GRUCell on one 16-row tile, x and h in registers (D layout), PyTorch gate order r, z, n ------------
-// brz = b_ih + b_hh for r, z (pre-summed). h updated in place; optional gate outputs for the backward.
+// brz = b_ih + b_hh for r, z (pre-summed). h updated in place.
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-
-__device__ inline void gru_tile(const float* __restrict__ wih, const float* __restrict__ whh, const float* __restrict__ bih,
-                                const float* __restrict__ bhh, const float* __restrict__ brz, const floatx4 (&x)[4],
-                                floatx4 (&h)[4], int lane) {
-    const int col = lane & 15, g = lane >> 4;
-    floatx4 hn[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-        floatx4 ar = ld4(brz + mt * 16 + 4 * g);
-        floatx4 az = ld4(brz + EMB + mt * 16 + 4 * g);
-        floatx4 ain = ld4(bih + 2 * EMB + mt * 16 + 4 * g);
-        floatx4 ahn = ld4(bhh + 2 * EMB + mt * 16 + 4 * g);
-        const float* wi = wih + (int64_t)(mt * 16 + col) * EMB + 4 * g;
-        const float* wh = whh + (int64_t)(mt * 16 + col) * EMB + 4 * g;
-        constexpr int64_t GATE = (int64_t)EMB * EMB;
-#pragma unroll
-        for (int kc = 0; kc < 4; ++kc) {
-            ar = mfma_chunk(ld4(wi + kc * 16), x[kc], ar);
-            az = mfma_chunk(ld4(wi + GATE + kc * 16), x[kc], az);
-            ain = mfma_chunk(ld4(wi + 2 * GATE + kc * 16), x[kc], ain);
-            ar = mfma_chunk(ld4(wh + kc * 16), h[kc], ar);
-            az = mfma_chunk(ld4(wh + GATE + kc * 16), h[kc], az);
-            ahn = mfma_chunk(ld4(wh + 2 * GATE + kc * 16), h[kc], ahn);
-#ifdef MLG_REFIL_LEAN
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float rg = sigm(ar[r]);
-            const float zg = sigm(az[r]);
-            const float ng = tanhf(ain[r] + rg * ahn[r]);
-            hn[mt][r] = ng + zg * (h[mt][r] - ng);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) h[mt] = hn[mt];
-}
-
-
-// GRUCell tile with software-pipelined weight loads: the 24 weight vectors of output chunk mt + 1 are issued
-// before the MFMAs of chunk mt (weights stream from L2 at one wave per SIMD; 2 x 96 VGPRs in flight).
-__device__ inline void gru_tile_pipe(const float* __restrict__ wih, const float* __restrict__ whh,
-                                     const float* __restrict__ bih, const float* __restrict__ bhh,
-                                     const float* __restrict__ brz, const floatx4 (&x)[4], floatx4 (&h)[4], int lane) {
-    const int col = lane & 15, g = lane >> 4;
-    constexpr int64_t GATE = (int64_t)EMB * EMB;
-    floatx4 wb[2][24];
-    auto load = [&](int mt, floatx4 (&w)[24]) {
-        const float* wi = wih + (int64_t)(mt * 16 + col) * EMB + 4 * g;
-        const float* wh = whh + (int64_t)(mt * 16 + col) * EMB + 4 * g;
-#pragma unroll
-        for (int kc = 0; kc < 4; ++kc) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                w[kc * 6 + q] = ld4(wi + q * GATE + kc * 16);
-                w[kc * 6 + 3 + q] = ld4(wh + q * GATE + kc * 16);
-            }
-        }
-    };
-    floatx4 hn[4];
-    load(0, wb[0]);
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-        if (mt + 1 < 4) load(mt + 1, wb[(mt + 1) & 1]);
-        __builtin_amdgcn_sched_barrier(0);
-        const floatx4(&w)[24] = wb[mt & 1];
-        floatx4 ar = ld4(brz + mt * 16 + 4 * g);
-        floatx4 az = ld4(brz + EMB + mt * 16 + 4 * g);
-        floatx4 ain = ld4(bih + 2 * EMB + mt * 16 + 4 * g);
-        floatx4 ahn = ld4(bhh + 2 * EMB + mt * 16 + 4 * g);
-#pragma unroll
-        for (int kc = 0; kc < 4; ++kc) {
-            ar = mfma_chunk(w[kc * 6 + 0], x[kc], ar);
-            az = mfma_chunk(w[kc * 6 + 1], x[kc], az);
-            ain = mfma_chunk(w[kc * 6 + 2], x[kc], ain);
-            ar = mfma_chunk(w[kc * 6 + 3], h[kc], ar);
-            az = mfma_chunk(w[kc * 6 + 4], h[kc], az);
-            ahn = mfma_chunk(w[kc * 6 + 5], h[kc], ahn);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float rg = sigm(ar[r]);
-            const float zg = sigm(az[r]);
-            const float ng = tanhf(ain[r] + rg * ahn[r]);
-            hn[mt][r] = ng + zg * (h[mt][r] - ng);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) h[mt] = hn[mt];
-}
 
 // GRUCell tile with the products as split-bf16 fp32 emulation on the bf16 matrix cores: x and h
 // (D layout) are split once into three bf16 pieces per 32-wide K step -- K slot (g, i) of step kk holds feature

@@ -43,7 +43,7 @@ constexpr int REFIL_HYPER_JOBS = 16;  // weight-gradient jobs of the 4 hypernets
 constexpr int64_t REFIL_HSP = 12 * 2 * 3 * 64 * 4;  // split hypernet in_trans (hyper_split_kernel)
 struct WsR {
     int64_t pa_on, pa_tg, ph_on[4], ph_tg[4];
-    int64_t a_winT, a_woutT, a_w2T, a_wihT, h_winT[4], h_woutT[4], h_w2T[4];
+    int64_t a_woutT, a_w2T, a_wihT, h_woutT[4], h_w2T[4];
     int64_t h_wsp[10], h_wspT[5];  // + in_trans^T split for hyper_bwd (hypernet k) / ent_bwd (agent: [4])  // in_trans as split-bf16 A operands: hypernet k of net at [k + 4 net], agent net at [8 + net]
     int64_t ein, x1, qkv, P, o, x2, x3, gi_on, gi_tg, hs_on, hs_tg, gr, gz, gn, ghn, mac, tmac;
     int64_t x1m[4], qkvm[4], Pm[4], om[4], x2m[4], X[4], Xtg[4], dX[4], doutm[4], dqkvm[4], dfc1m[4];
@@ -113,12 +113,10 @@ Plan make_plan(const MlgRefilLearnerCfg* cfg, int T1) {
     w.pa_tg = take(p.La.total);
     for (int k = 0; k < 4; ++k) w.ph_on[k] = take(p.Lh.total);
     for (int k = 0; k < 4; ++k) w.ph_tg[k] = take(p.Lh.total);
-    w.a_winT = take(EMB * 3 * EMB);
     w.a_woutT = take(EMB * EMB);
     w.a_w2T = take(EMB * EMB);
     w.a_wihT = take(EMB * 3 * EMB);
     for (int k = 0; k < 4; ++k) {
-        w.h_winT[k] = take(EMB * 3 * EMB);
         w.h_woutT[k] = take(EMB * EMB);
         w.h_w2T[k] = take(EMB * EM);
     }
@@ -311,8 +309,8 @@ __device__ void hyper_splitT_body(const HSplit& J, int bx, int by) {
     J.dst[by][k] = split_bf16_pair(W[(int64_t)f0 * EMB + row], W[(int64_t)(f0 + 1) * EMB + row], pc);
 }
 
-// acc[mt] += in_trans^T . X over one 16-row tile (X = dQKV rows in LDS, K = 192) as split-bf16 fp32 emulation;
-// replaces mm_lds<4>(acc, winT, 3 * EMB, 0, X, LDQ, 12, lane). Weights streamed per output tile (18 loads).
+// acc[mt] += in_trans^T . X over one 16-row tile (X = dQKV rows in LDS, K = 192) as split-bf16 fp32 emulation.
+// Weights streamed per output tile (18 loads).
 __device__ inline void in_transT_lds_b16(floatx4 (&acc)[4], const float* __restrict__ wspT, const float* X, int lane) {
     const int col = lane & 15, g = lane >> 4;
     Split3 xs[6];
@@ -345,7 +343,7 @@ __device__ inline void in_transT_lds_b16(floatx4 (&acc)[4], const float* __restr
 
 // Y = in_trans(X) over one 16-row tile (X, Y in LDS) as split-bf16 fp32 emulation (six partial products; the
 // rollout's entity_block_reg scheme): X rows split once per 32-wide K step in the wsp K order, weights streamed in
-// 3-tile stages. Replaces dense_lds<false>(win, ...) -- 144 bf16 MFMAs instead of 192 f32 MFMAs.
+// 3-tile stages: 144 bf16 MFMAs where the f32 form takes 192.
 __device__ inline void in_trans_lds_b16(const float* __restrict__ wsp, const float* X, float* Y, int ldy, int lane) {
     const int col = lane & 15, g = lane >> 4;
     Split3 xs[2];
@@ -411,62 +409,11 @@ __device__ __forceinline__ float emask_at(const MlgEntityBatch& bt, int b, int t
     return m;
 }
 
-__device__ void mask_sum_body(const MlgEntityBatch& bt, int B, int T, float* __restrict__ msum, float* red) {
-    // msum[1] = max_t_filled (the reference's truncation, ma_experiment.py:235-239): the learner uses transitions
-    // t < max_t_filled - 1 only; the sequential kernels stop there and the per-t kernels skip the steps beyond
-    int mx = 0;  // a wave per episode: filled steps counted with ballots
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (int b = wave; b < B; b += nw) {
-        const int64_t base = eslot(bt, b) * bt.T1;
-        int n = 0;
-        for (int t0 = 0; t0 < T; t0 += 64) {
-            const int t = t0 + lane;
-            n += __popcll(__ballot(t < T && bt.filled[base + t] != 0));
-        }
-        mx = n > mx ? n : mx;
-    }
-    red[threadIdx.x] = (float)mx;
-    __syncthreads();
-    for (int w = blockDim.x / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    const int Te = (int)fminf(fmaxf(red[0], 2.f), (float)T);
-    __syncthreads();
-    float s = 0.f;
-    for (int i = threadIdx.x; i < B * (Te - 1); i += blockDim.x) s += emask_at(bt, i / (Te - 1), i % (Te - 1));
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = blockDim.x / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        msum[0] = red[0];
-        msum[1] = (float)Te;
-    }
-    // msum[4 + b]: the episode's live mixer items = 1 + the last t < Te - 1 with mask(b, t) != 0 (0: none). Every item
-    // t >= it has mask 0 (its loss, its deltas and every gradient through it are exactly zero), so the per-item kernels
-    // skip items t >= mix_len (mixer, agent backward) and t > mix_len (agent forward: Q at mix_len is the last step's
-    // target): at the bench's sampled batches (max_t_filled 101, episodes ~47 steps) about half of all items.
-    for (int b = wave; b < B; b += nw) {
-        const int64_t base = eslot(bt, b) * bt.T1;
-        int last = -1;
-        for (int t0 = 0; t0 < Te - 1; t0 += 64) {
-            const int t = t0 + lane;
-            bool live = false;
-            if (t < Te - 1) {
-                live = bt.filled[base + t] != 0 && (t == 0 || bt.terminated[base + t - 1] == 0);
-            }
-            const uint64_t m = __ballot(live);
-            if (m) last = t0 + 63 - __builtin_clzll(m);
-        }
-        if (lane == 0) msum[4 + b] = (float)(last + 1);
-    }
-}
-
-__device__ __forceinline__ int t_eff(const float* msum) { return (int)msum[1]; }
-// live mixer items of episode b (mask(b, t) == 0 for every t >= it; see mask_sum_body)
+using mlg::t_eff;
+// msum[4 + b]: the episode's live mixer items = 1 + the last t < Te - 1 with mask(b, t) != 0 (0: none). Every item
+// t >= it has mask 0 (its loss, its deltas and every gradient through it are exactly zero), so the per-item kernels
+// skip items t >= mix_len (mixer, agent backward) and t > mix_len (agent forward: Q at mix_len is the last step's
+// target): at the bench's sampled batches (max_t_filled 101, episodes ~47 steps) about half of all items.
 __device__ __forceinline__ int mix_len(const float* msum, int b) { return (int)msum[4 + b]; }
 
 // entity inputs ein[i][j][c] (K1 columns, zero padded)
@@ -509,7 +456,6 @@ inline int prologue_blocks(const Prologue& P) {
     return 1 + 2 * P.nb_a + 8 * P.nb_h + 15 * P.nb_s + P.tj.n * P.nb_t + P.nb_e;
 }
 __global__ void __launch_bounds__(256) prologue_kernel(Prologue P) {
-    __shared__ float red[256];
     __shared__ int32_t srows[MLG_INLINE_ROWS];
     MlgEntityBatch bt = P.bt;
     if (P.n_rows_in > 0) {  // this launch reads the slot map from LDS, the later launches from rows_dst
@@ -524,11 +470,8 @@ __global__ void __launch_bounds__(256) prologue_kernel(Prologue P) {
     if (blk == 0) {
         __shared__ mlg::MaskStatsLds ms;
         constexpr int EPW = 8;  // episodes per wave: 4 waves cover the bench's 32-episode batches
-        if (mlg::mask_stats_fits<EPW>(P.c.B, P.c.T, blockDim.x / 64))  // one round trip (batch_mask_device.h)
-            mlg::batch_mask_stats<EPW>(bt.filled, bt.terminated, bt.T1, [&](int b) { return eslot(bt, b); }, P.c.B,
-                                       P.c.T, P.msum, P.msum + 4, ms);
-        else
-            mask_sum_body(bt, P.c.B, P.c.T, P.msum, red);
+        mlg::batch_mask<EPW>(bt.filled, bt.terminated, bt.T1, [&](int b) { return eslot(bt, b); }, P.c.B, P.c.T,
+                             P.msum, P.msum + 4, ms);
         return;
     }
     blk -= 1;
@@ -656,11 +599,7 @@ __global__ void __launch_bounds__(64) ent_fwd_kernel(RCfg c_arg, MlgEntityBatch 
         wave_sync();
         dense_lds<true>(A.P + L.w1, L.K1, A.P + L.b1, EMB / 16, s_ein, LDI, L.K1 / 16, s_x1, LDX, lane);
         wave_sync();
-#if defined(MLG_HYPER_F32)
-        dense_lds<false>(A.P + L.win, EMB, nullptr, 3 * EMB / 16, s_x1, LDX, EMB / 16, s_qkv, LDQ, lane);
-#else
         in_trans_lds_b16(A.wsp, s_x1, s_qkv, LDQ, lane);
-#endif
         wave_sync();
         if (online) {
             for (int k = lane; k < NE * EMB; k += 64) A.x1[(int64_t)i * NE * EMB + k] = s_x1[(k / EMB) * LDX + k % EMB];
@@ -719,87 +658,8 @@ __global__ void __launch_bounds__(64) ent_fwd_kernel(RCfg c_arg, MlgEntityBatch 
 }
 
 // ---- GRU recurrence (online rows then target rows) ------------------------------------------------------
-// grid (ntiles_on + ntiles_tg), 4 waves: wave w owns hidden chunk w, its W_hh rows in VGPRs.
-__global__ void __launch_bounds__(256) rec_kernel(RCfg c, RAgent L, const float* __restrict__ Pon,
-                                                  const float* __restrict__ Ptg, const float* __restrict__ gi_on,
-                                                  const float* __restrict__ gi_tg, float* __restrict__ hs_on,
-                                                  float* __restrict__ hs_tg, float* __restrict__ ws_gr,
-                                                  float* __restrict__ ws_gz, float* __restrict__ ws_gn,
-                                                  float* __restrict__ ws_ghn, const float* __restrict__ msum) {
-    constexpr int H = EMB, HC = 4;
-    const int Te = t_eff(msum);
-    __shared__ __attribute__((aligned(16))) float hs[2][16 * LDX];
-    const int nt_on = (c.Ron + 15) / 16;
-    const bool online = (int)blockIdx.x < nt_on;
-    const int tile = online ? blockIdx.x : blockIdx.x - nt_on;
-    const int R = online ? c.Ron : c.Rtg;
-    const float* P = online ? Pon : Ptg;
-    const float* gi = online ? gi_on : gi_tg;
-    float* hsg = online ? hs_on : hs_tg;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int col = lane & 15, g = lane >> 4;
-    const int r = tile * 16 + col;
-    const bool valid = r < R;
-    const int f0 = w * 16 + 4 * g;
-    floatx4 wr[3][HC];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int kc = 0; kc < HC; ++kc) wr[q][kc] = ld4(P + L.whh + (int64_t)(q * H + w * 16 + col) * H + kc * 16 + 4 * g);
-    const floatx4 bhn = ld4(P + L.bhh + 2 * H + f0);
-    const __amdgpu_buffer_rsrc_t rs_h = mlg_rsrc(hsg), rs_gr = mlg_rsrc(ws_gr), rs_gz = mlg_rsrc(ws_gz),
-                                 rs_gn = mlg_rsrc(ws_gn), rs_ghn = mlg_rsrc(ws_ghn);
-    for (int i = tid; i < 16 * LDX; i += blockDim.x) hs[0][i] = 0.f;
-    if (valid) *reinterpret_cast<floatx4*>(hsg + (int64_t)r * H + f0) = floatx4{0.f, 0.f, 0.f, 0.f};
-    const int rr = valid ? r : 0;
-    auto gi_at = [&](int t, int q) { return ld4(gi + ((int64_t)t * R + rr) * 3 * H + q * H + f0); };
-    floatx4 nr = gi_at(0, 0), nz = gi_at(0, 1), nn = gi_at(0, 2);
-    __syncthreads();
-    int cur = 0;
-    for (int t = 0; t < Te; ++t) {
-        floatx4 ar = nr, az = nz;
-        const floatx4 gin = nn;
-        if (t + 1 < Te) {
-            nr = gi_at(t + 1, 0);
-            nz = gi_at(t + 1, 1);
-            nn = gi_at(t + 1, 2);
-        }
-        floatx4 ahn = bhn;
-        const float* hrow = hs[cur] + col * LDX + 4 * g;
-#pragma unroll
-        for (int kc = 0; kc < HC; ++kc) {
-            const floatx4 hin = ld4(hrow + kc * 16);
-            ar = mfma_chunk(wr[0][kc], hin, ar);
-            az = mfma_chunk(wr[1][kc], hin, az);
-            ahn = mfma_chunk(wr[2][kc], hin, ahn);
-        }
-        const floatx4 hp = ld4(hs[cur] + col * LDX + f0);
-        floatx4 rg, zg, ng, hn;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {  // gates on v_exp_f32 / v_rcp_f32 (as the QMIX learner's recurrence)
-            rg[q] = fast_sigmoid(ar[q]);
-            zg[q] = fast_sigmoid(az[q]);
-            ng[q] = fast_tanh(gin[q] + rg[q] * ahn[q]);
-            hn[q] = ng[q] + zg[q] * (hp[q] - ng[q]);
-        }
-        *reinterpret_cast<floatx4*>(hs[cur ^ 1] + col * LDX + f0) = hn;
-        {  // branch-free stores (dropped rows: out-of-range buffer offsets), so the prefetch waits count them
-            const int64_t o = ((int64_t)t * R + r) * H + f0;
-            st4_if(rs_h, o + (int64_t)R * H, hn, valid);
-            if (online) {
-                st4_if(rs_gr, o, rg, valid);
-                st4_if(rs_gz, o, zg, valid);
-                st4_if(rs_gn, o, ng, valid);
-                st4_if(rs_ghn, o, ahn, valid);
-            }
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-}
-
-// The recurrences on 4-row tiles (gru4_device.h, shared with the QMIX learner): 4x the CUs of the 16-row tiles above
-// on the sequential T loop. grid (ntiles4 online + ntiles4 target), 4 waves; online tiles store the gates.
+// The recurrences on 4-row tiles (gru4_device.h, shared with the QMIX learner): 4x the CUs of 16-row tiles on the
+// sequential T loop. grid (ntiles4 online + ntiles4 target), 4 waves; online tiles store the gates.
 __global__ void __launch_bounds__(256) rec4_kernel(RCfg c, RAgent L, const float* __restrict__ Pon,
                                                    const float* __restrict__ Ptg, const float* __restrict__ gi_on,
                                                    const float* __restrict__ gi_tg, float* __restrict__ hs_on,
@@ -913,11 +773,7 @@ __global__ void __launch_bounds__(64) hyper_fwd_kernel(RCfg c_arg, MlgEntityBatc
     wave_sync();
     dense_lds<true>(P + L.w1, L.K1, P + L.b1, EMB / 16, s_ein, LDI, L.K1 / 16, s_x1, LDX, lane);
     wave_sync();
-#if defined(MLG_HYPER_F32)
-    dense_lds<false>(P + L.win, EMB, nullptr, 3 * EMB / 16, s_x1, LDX, EMB / 16, s_qkv, LDQ, lane);
-#else
     in_trans_lds_b16(hp.Wsp[k + 4 * net], s_x1, s_qkv, LDQ, lane);
-#endif
     wave_sync();
     if (!net) {
         for (int q = lane; q < NE * EMB; q += 64) hp.x1m[k][(int64_t)i * NE * EMB + q] = s_x1[(q / EMB) * LDX + q % EMB];
@@ -1243,7 +1099,6 @@ struct HypBwd {
     const float* Pon[4];
     const float* woutT[4];
     const float* w2T[4];
-    const float* winT[4];
     const float* x1m[4];
     const float* qkvm[4];
     const float* Pm[4];
@@ -1309,11 +1164,7 @@ __global__ void __launch_bounds__(64) hyper_bwd_kernel(RCfg c_arg, MlgEntityBatc
     // dx1 = W_in^T dqkv * relu'(x1)
     floatx4 dx1[4];
     bias_init<4>(dx1, nullptr, 0, lane);
-#if defined(MLG_HYPER_F32)
-    mm_lds<4>(dx1, hb.winT[k], 3 * EMB, 0, s_dqkv, LDQ, 3 * EMB / 16, lane);
-#else
     in_transT_lds_b16(dx1, hb.wspT[k], s_dqkv, lane);
-#endif
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const floatx4 xv = x1v[q];
@@ -1324,106 +1175,6 @@ __global__ void __launch_bounds__(64) hyper_bwd_kernel(RCfg c_arg, MlgEntityBatc
 }
 
 // ---- reverse-time GRU backward of the online rows ------------------------------------------------------------
-__global__ void __launch_bounds__(256) rec_bwd_kernel(RCfg c, MlgEntityBatch bt, RAgent L, const float* __restrict__ P,
-                                                      const float* __restrict__ ws_hs, const float* __restrict__ ws_gr,
-                                                      const float* __restrict__ ws_gz, const float* __restrict__ ws_gn,
-                                                      const float* __restrict__ ws_ghn, const float* __restrict__ dqv,
-                                                      float* __restrict__ dgi, float* __restrict__ dgh,
-                                                      const float* __restrict__ msum) {
-    constexpr int H = EMB;
-    constexpr int LDG = 3 * H + 4;
-    constexpr int KC = 3 * H / 16;
-    __shared__ __attribute__((aligned(16))) float sgh[2][16 * LDG];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int col = lane & 15, g = lane >> 4;
-    const int r = blockIdx.x * 16 + col;
-    const int R = c.Ron;
-    const bool valid = r < R;
-    int b = 0, n = 0;
-    if (valid) row_bn(c, r, b, n);
-    const int f0 = w * 16 + 4 * g;
-    floatx4 wt[KC];
-#pragma unroll
-    for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) wt[kc][q] = P[L.whh + (int64_t)(kc * 16 + 4 * g + q) * H + w * 16 + col];
-    const int rr = valid ? r : 0;
-    const int64_t srow = eslot(bt, b) * bt.T1;
-    struct Step {
-        floatx4 rg, zg, ng, ghn, hp, w3;
-        float dq;
-    };
-    auto load_step = [&](int t) {
-        Step s;
-        const int64_t o = ((int64_t)t * R + rr) * H + f0;
-        s.rg = ld4(ws_gr + o);
-        s.zg = ld4(ws_gz + o);
-        s.ng = ld4(ws_gn + o);
-        s.ghn = ld4(ws_ghn + o);
-        s.hp = ld4(ws_hs + o);
-        s.dq = 0.f;
-        s.w3 = floatx4{0.f, 0.f, 0.f, 0.f};
-        if (t < c.T - 1) {
-            s.dq = dqv[(int64_t)t * R + rr];
-            const int a = (int)bt.actions[(srow + t) * c.NA + n];
-            s.w3 = ld4(P + L.w3 + (int64_t)a * H + f0);
-        }
-        return s;
-    };
-    const int Te = t_eff(msum);
-    if (valid) {  // steps past max_t_filled: zero deltas (wgrad rows)
-        for (int t = Te; t < c.T; ++t) {
-            const int64_t o3 = ((int64_t)t * R + r) * 3 * H + f0;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                *reinterpret_cast<floatx4*>(dgi + o3 + q * H) = floatx4{0.f, 0.f, 0.f, 0.f};
-                *reinterpret_cast<floatx4*>(dgh + o3 + q * H) = floatx4{0.f, 0.f, 0.f, 0.f};
-            }
-        }
-    }
-    floatx4 dh = {0.f, 0.f, 0.f, 0.f};
-    const __amdgpu_buffer_rsrc_t rs_gi = mlg_rsrc(dgi), rs_gh = mlg_rsrc(dgh);
-    Step nx = load_step(Te - 1);
-    int cur = 0;
-    for (int t = Te - 1; t >= 0; --t) {
-        const Step s = nx;
-        if (t > 0) nx = load_step(t - 1);
-        if (valid && t < c.T - 1) dh += s.dq * s.w3;
-        floatx4 drp, dzp, dnp, dghn, dhd;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float dn = dh[q] * (1.f - s.zg[q]);
-            const float dz = dh[q] * (s.hp[q] - s.ng[q]);
-            dhd[q] = dh[q] * s.zg[q];
-            dnp[q] = dn * (1.f - s.ng[q] * s.ng[q]);
-            const float dr = dnp[q] * s.ghn[q];
-            drp[q] = dr * s.rg[q] * (1.f - s.rg[q]);
-            dzp[q] = dz * s.zg[q] * (1.f - s.zg[q]);
-            dghn[q] = dnp[q] * s.rg[q];
-        }
-        float* gh = sgh[cur] + col * LDG;
-        *reinterpret_cast<floatx4*>(gh + f0) = drp;
-        *reinterpret_cast<floatx4*>(gh + H + f0) = dzp;
-        *reinterpret_cast<floatx4*>(gh + 2 * H + f0) = dghn;
-        {  // branch-free stores (dropped rows: out-of-range buffer offsets)
-            const int64_t o3 = ((int64_t)t * R + r) * 3 * H + f0;
-            st4_if(rs_gi, o3, drp, valid);
-            st4_if(rs_gi, o3 + H, dzp, valid);
-            st4_if(rs_gi, o3 + 2 * H, dnp, valid);
-            st4_if(rs_gh, o3, drp, valid);
-            st4_if(rs_gh, o3 + H, dzp, valid);
-            st4_if(rs_gh, o3 + 2 * H, dghn, valid);
-        }
-        __syncthreads();
-        const float* ghr = sgh[cur] + col * LDG + 4 * g;
-        floatx4 dp[4] = {dhd, floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc) dp[kc & 3] = mfma_chunk(wt[kc], ld4(ghr + kc * 16), dp[kc & 3]);
-        dh = (dp[0] + dp[1]) + (dp[2] + dp[3]);  // four independent MFMA chains instead of one of 48
-        cur ^= 1;
-    }
-}
-
 // reverse-time GRU backward of the online rows on 4-row tiles (gru4_device.h); dh += dQ W3[a] (fc3 rows)
 __global__ void __launch_bounds__(256) rec_bwd4_kernel(RCfg c, MlgEntityBatch bt, RAgent L, const float* __restrict__ P,
                                                        const float* __restrict__ ws_hs, const float* __restrict__ ws_gr,
@@ -1442,7 +1193,7 @@ __global__ void __launch_bounds__(256) rec_bwd4_kernel(RCfg c, MlgEntityBatch bt
 
 // ---- agent entity block backward: one wave per item pair --------------------------------------------------
 struct EntBwd {
-    const float *wihT, *w2T, *woutT, *winT;
+    const float *wihT, *w2T, *woutT;
     const float* wspT;
     const float *x1, *qkv, *Pw, *x3, *dgi;
     float *dfc2, *dout, *dqkv, *dfc1;
@@ -1538,11 +1289,7 @@ __global__ void __launch_bounds__(64) ent_bwd_kernel(RCfg c_arg, MlgEntityBatch 
             eb.dqkv[(int64_t)ii * NE * 3 * EMB + q] = s_dqkv[(q / (3 * EMB)) * LDQ + q % (3 * EMB)];
         floatx4 dx1[4];
         bias_init<4>(dx1, nullptr, 0, lane);
-#if defined(MLG_HYPER_F32)
-        mm_lds<4>(dx1, eb.winT, 3 * EMB, 0, s_dqkv, LDQ, 3 * EMB / 16, lane);
-#else
         in_transT_lds_b16(dx1, eb.wspT, s_dqkv, lane);
-#endif
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const floatx4 xv = x1v[q];
@@ -1564,23 +1311,9 @@ __global__ void __launch_bounds__(1024) refil_finish_kernel(const float* __restr
                                                       double* __restrict__ trained, float* __restrict__ tsync) {
     __shared__ float red[1024];
     const int tid = threadIdx.x;
-    // this thread's parameter, gradient and square average, requested before the norm reduction they wait for
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + tid;
-    const bool has = i < n_params;
-    const float g0 = has ? grads[i] : 0.f, sq0 = has ? sq[i] : 0.f, p0 = has ? params[i] : 0.f;
-    float s = 0.f;
-    for (int k = tid; k < n_nrm; k += blockDim.x) s += nrm_part[k];
-    const float norm = sqrtf(mlg::block_sum_1024(s, red));
-    const float coef = fminf(max_norm / (norm + 1e-6f), 1.f);
-    if (has) {
-        const float gi = g0 * coef;
-        grads[i] = gi;
-        const float a = alpha * sq0 + (1.f - alpha) * gi * gi;
-        sq[i] = a;
-        const float pn = p0 - lr * gi / (sqrtf(a) + eps);
-        params[i] = pn;
-        if (tsync) tsync[i] = pn;  // the target update due after this step (refil_learner.py:181-183), same launch
-    }
+    // tsync: the target update due after this step (refil_learner.py:181-183)
+    const float norm = mlg::clip_rmsprop_step(params, grads, sq, n_params, nrm_part, n_nrm, lr, alpha, eps, max_norm,
+                                              tsync, red);
     // the stat sums spread over blocks 0..3 (block 0: loss and im_loss, which combine; blocks 1..3 one each; same
     // order as one block doing all five: bit-identical)
     const float ms = msum_p[0];
@@ -1620,7 +1353,7 @@ RJobs make_jobs(Plan& p, float* ws, float* grads, int64_t* slab_floats, int* n_t
     RJobs J;
     J.n = 0;
     // rows of items / steps past each episode's live mixer items carry exactly zero deltas (the backward kernels'
-    // zero paths): every job skips them (mix_len at msum + 4, mask_sum_body)
+    // zero paths): every job skips them (mix_len at msum + 4, batch_mask_device.h)
     const float* ml = ws ? ws + p.w.msum + 4 : nullptr;
     // (not optional: the kernels above no longer write the skipped rows)
     auto items = [&](mlg::BJob j, int rpi) { return mlg::bjob_items(j, ml, rpi, c.I, c.T); };
@@ -1684,7 +1417,6 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
         if (tj.n < TrJobs::kCap && (int64_t)rows * cols <= 3 * EMB * EMB) tj.j[tj.n++] = TrJob{src, dst, rows, cols};
         else tr_bad = true;
     };
-    tr(params + La.c_win, ws + w.a_winT, 3 * EMB, EMB);
     tr(params + La.c_wout, ws + w.a_woutT, EMB, EMB);
     tr(params + La.c_w2, ws + w.a_w2T, EMB, EMB);
     tr(params + La.c_wih, ws + w.a_wihT, 3 * EMB, EMB);
@@ -1694,7 +1426,6 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
         P.hp.dst[2 * k] = ws + w.ph_on[k];
         P.hp.src[2 * k + 1] = tparams + G0;
         P.hp.dst[2 * k + 1] = ws + w.ph_tg[k];
-        tr(params + G0 + p.Lh.c_win, ws + w.h_winT[k], 3 * EMB, EMB);
         tr(params + G0 + p.Lh.c_wout, ws + w.h_woutT[k], EMB, EMB);
         tr(params + G0 + p.Lh.c_w2, ws + w.h_w2T[k], EM, EMB);
     }
@@ -1746,17 +1477,10 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
     hipLaunchKernelGGL(s8 ? ent_fwd_kernel<1> : ent_fwd_kernel<0>, dim3((unsigned)((c.I + 1) / 2), 2), dim3(64), 0, s, c,
                        bt, bufs->groupA, La,
                        ws + w.ein, on, tg, ws + w.msum);
-    const int nt_on = (c.Ron + 15) / 16, nt_tg = (c.Rtg + 15) / 16;
-    // the recurrences on 4-row tiles (default) or 16-row tiles (MLG_REFIL_REC16, A/B)
-    static const bool rec16 = getenv("MLG_REFIL_REC16") != nullptr;
-    if (rec16)
-        hipLaunchKernelGGL(rec_kernel, dim3((unsigned)(nt_on + nt_tg)), dim3(256), 0, s, c, La, ws + w.pa_on,
-                           ws + w.pa_tg, ws + w.gi_on, ws + w.gi_tg, ws + w.hs_on, ws + w.hs_tg, ws + w.gr, ws + w.gz,
-                           ws + w.gn, ws + w.ghn, ws + w.msum);
-    else
-        hipLaunchKernelGGL(rec4_kernel, dim3((unsigned)((c.Ron + 3) / 4 + (c.Rtg + 3) / 4)), dim3(256), 0, s, c, La,
-                           ws + w.pa_on, ws + w.pa_tg, ws + w.gi_on, ws + w.gi_tg, ws + w.hs_on, ws + w.hs_tg, ws + w.gr,
-                           ws + w.gz, ws + w.gn, ws + w.ghn, ws + w.msum);
+    const int nt_on = (c.Ron + 15) / 16;
+    hipLaunchKernelGGL(rec4_kernel, dim3((unsigned)((c.Ron + 3) / 4 + (c.Rtg + 3) / 4)), dim3(256), 0, s, c, La,
+                       ws + w.pa_on, ws + w.pa_tg, ws + w.gi_on, ws + w.gi_tg, ws + w.hs_on, ws + w.hs_tg, ws + w.gr,
+                       ws + w.gz, ws + w.gn, ws + w.ghn, ws + w.msum);
     hipLaunchKernelGGL(s8 ? q_kernel<1> : q_kernel<0>, dim3((unsigned)nt_on, (unsigned)c.T, 2), dim3(64 * (c.Ap / 16)), 0,
                        s, c, bt, La,
                        ws + w.pa_on, ws + w.pa_tg, ws + w.hs_on, ws + w.hs_tg, ws + w.mac, ws + w.tmac, ws + w.msum);
@@ -1801,7 +1525,6 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
         hb.Pon[k] = ws + w.ph_on[k];
         hb.woutT[k] = ws + w.h_woutT[k];
         hb.w2T[k] = ws + w.h_w2T[k];
-        hb.winT[k] = ws + w.h_winT[k];
         hb.wspT[k] = ws + w.h_wspT[k];
         hb.x1m[k] = ws + w.x1m[k];
         hb.qkvm[k] = ws + w.qkvm[k];
@@ -1825,14 +1548,10 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
     hipLaunchKernelGGL(mlg::wgrad_block_kernel<MJ>, dim3((unsigned)((tH + 3) / 4)), dim3(256), 0, sh, JH, ws + w.slab);
     if (side) MLG_REQUIRE(hipEventRecord(side->ev[3], sh) == hipSuccess, "refil learner: side stream record");
     // ---- agent backward ----
-    if (rec16)
-        hipLaunchKernelGGL(rec_bwd_kernel, dim3((unsigned)nt_on), dim3(256), 0, s, c, bt, La, ws + w.pa_on, ws + w.hs_on,
-                           ws + w.gr, ws + w.gz, ws + w.gn, ws + w.ghn, ws + w.dq, ws + w.dgi, ws + w.dgh, ws + w.msum);
-    else
-        hipLaunchKernelGGL(rec_bwd4_kernel, dim3((unsigned)((c.Ron + 3) / 4)), dim3(256), 0, s, c, bt, La, ws + w.pa_on,
-                           ws + w.hs_on, ws + w.gr, ws + w.gz, ws + w.gn, ws + w.ghn, ws + w.dq, ws + w.dgi, ws + w.dgh,
-                           ws + w.msum);
-    EntBwd eb{ws + w.a_wihT, ws + w.a_w2T, ws + w.a_woutT, ws + w.a_winT, ws + w.h_wspT[4], ws + w.x1, ws + w.qkv, ws + w.P, ws + w.x3,
+    hipLaunchKernelGGL(rec_bwd4_kernel, dim3((unsigned)((c.Ron + 3) / 4)), dim3(256), 0, s, c, bt, La, ws + w.pa_on,
+                       ws + w.hs_on, ws + w.gr, ws + w.gz, ws + w.gn, ws + w.ghn, ws + w.dq, ws + w.dgi, ws + w.dgh,
+                       ws + w.msum);
+    EntBwd eb{ws + w.a_wihT, ws + w.a_w2T, ws + w.a_woutT, ws + w.h_wspT[4], ws + w.x1, ws + w.qkv, ws + w.P, ws + w.x3,
               ws + w.dgi, ws + w.dfc2, ws + w.dout, ws + w.dqkv, ws + w.dfc1};
     hipLaunchKernelGGL(s8 ? ent_bwd_kernel<1> : ent_bwd_kernel<0>, dim3((unsigned)((c.I + 1) / 2)), dim3(64), 0, s, c, bt,
                        eb, ws + w.msum);

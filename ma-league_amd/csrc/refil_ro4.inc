@@ -114,7 +114,7 @@ RO_PHASE void r4_observe(R4Lds& S, const EnvTables& T, const EnvMasks& M, const 
 // LIVE: which envs of the pair still run (bit 0: env 2p, bit 1: env 2p + 1). A finished env's entity tile is skipped
 // (its fc1 / in_trans MFMA chains, q / k | v rows and attention): its agent rows are never read again (no action is
 // recorded for it, and the MFMA columns of the pair's other env do not depend on them).
-template <int KC1, int LIVE = 3>
+template <int KC1, int LIVE>
 RO_PHASE void r4_entity_pair(const float* __restrict__ P, const RAgent& L, R4Lds& S, int p, const RoArgs& a, int t,
                              int lane, RStamps& stp) {
     static_assert(KC1 == 2, "r4 rollout: entity input width 17..32 (ED = 8, A <= 24)");
@@ -605,18 +605,13 @@ __global__ void __launch_bounds__(64 * R4_WAVES) refil_rollout4_kernel(MlgEntity
         stp.mark(0);
         stp.step_begin();
         // ---- agent phase: EntityMAC.forward(t) + epsilon-greedy for the four envs ----
-        // a pair with one env left runs only that env's entity tile (MLG_REFIL_PAIR_BOTH: always both, A/B)
-#if defined(MLG_REFIL_PAIR_BOTH)
-        if (p0) r4_entity_pair<KC1>(Pw, L, S, 0, a, t, lane, stp);
-        if (p1) r4_entity_pair<KC1>(Pw, L, S, 1, a, t, lane, stp);
-#else
+        // a pair with one env left runs only that env's entity tile
         if (s0 != 2 && s1 != 2) r4_entity_pair<KC1, 3>(Pw, L, S, 0, a, t, lane, stp);
         else if (s0 != 2) r4_entity_pair<KC1, 1>(Pw, L, S, 0, a, t, lane, stp);
         else if (s1 != 2) r4_entity_pair<KC1, 2>(Pw, L, S, 0, a, t, lane, stp);
         if (s2 != 2 && s3 != 2) r4_entity_pair<KC1, 3>(Pw, L, S, 1, a, t, lane, stp);
         else if (s2 != 2) r4_entity_pair<KC1, 1>(Pw, L, S, 1, a, t, lane, stp);
         else if (s3 != 2) r4_entity_pair<KC1, 2>(Pw, L, S, 1, a, t, lane, stp);
-#endif
         stp.mark(1);
         // tile row r = env 2p + (r >> 3), agent r & 7; dead = agent entity masked or padding row >= n_agents
         const uint32_t pad = ~((1u << a.NA) - 1u) & 0xFFu;

@@ -1,75 +1,15 @@
 // wgrad_device.h -- weight gradients as job lists, shared by the QMIX and REFIL learners:
-// dW[M][K] = sum_rows delta[row][m] x[row][k], db[m] = sum_rows delta[row][m], split over 256-row chunks (one wave
-// per (job, 16x16 tile, chunk), MFMA with the row index as K) and summed over chunks in a fixed order
-// (deterministic). The reduce pass also emits per-block sums of squares for clip_grad_norm_.
+// dW[M][K] = sum_rows delta[row][m] x[row][k], db[m] = sum_rows delta[row][m]: one wave per (job, 64 x 64 output
+// block, row chunk of up to 1024 rows), MFMA with the row index as K; per 32-row step every lane loads 4 delta and
+// 4 x values of 8 rows and issues 16 MFMA groups. The 4 waves of a workgroup (4 chunks of one block) add their
+// partials in LDS; the partials [block][chunk group][64 * 64 + 64] are summed over groups in a fixed order
+// (deterministic). The reduce pass also emits per-block sums of squares for clip_grad_norm_, which the learners'
+// finish kernels turn into the clipped RMSprop step (clip_rmsprop_step).
 #pragma once
-#include <cstdlib>
-
 #include "mlg_device.h"
 
 namespace mlg {
 
-constexpr int WCH = 256;  // rows per wgrad chunk
-
-// ================================================================================================
-// weight gradients: dW[M][K] = sum_rows delta[row][m] x[row][k], db[m] = sum_rows delta[row][m]
-struct WJob {
-    const float* delta;
-    const float* x;
-    float* dw;
-    float* db;
-    int64_t ldd, ldx;
-    int M, K, rows, mt, nt, chunks;
-    int task0;  // first task index
-    int64_t slab0;
-};
-template <int MJ>
-struct WJobsT {
-    WJob j[MJ];
-    int n;
-};
-
-template <int MJ>
-__device__ __forceinline__ int find_job(const WJobsT<MJ>& J, int task) {
-    int k = 0;
-    while (k + 1 < J.n && J.j[k + 1].task0 <= task) ++k;
-    return k;
-}
-
-// one wave per (job, m-tile, n-tile, row chunk); partial tile (+ bias partial when nt == 0) -> slab
-template <int MJ>
-__global__ void __launch_bounds__(256) wgrad_kernel(WJobsT<MJ> J, float* __restrict__ slab) {
-    const int lane = threadIdx.x & 63;
-    const int task = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (task >= J.j[J.n - 1].task0 + J.j[J.n - 1].mt * J.j[J.n - 1].nt * J.j[J.n - 1].chunks) return;
-    const WJob jb = J.j[find_job(J, task)];
-    const int local = task - jb.task0;
-    const int ch = local % jb.chunks, tt = local / jb.chunks;
-    const int mt = tt / jb.nt, nt = tt % jb.nt;
-    const int col = lane & 15, g = lane >> 4;
-    const int m = mt * 16 + col, k = nt * 16 + col;
-    const int r0 = ch * WCH, r1 = min(jb.rows, r0 + WCH);
-    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-    float bsum = 0.f;
-    const bool mv = m < jb.M, kv = k < jb.K;
-    for (int rr = r0; rr < r1; rr += 4) {
-        const int row = rr + g;
-        const bool rv = row < r1;
-        const float a = (mv && rv) ? jb.delta[(int64_t)row * jb.ldd + m] : 0.f;
-        const float xv = (kv && rv) ? jb.x[(int64_t)row * jb.ldx + k] : 0.f;
-        acc = mfma4(a, xv, acc);
-        bsum += a;
-    }
-    float* out = slab + jb.slab0 + ((int64_t)tt * jb.chunks + ch) * 272;
-    // D layout: reg q -> (m = mt*16 + 4g + q, k = nt*16 + col)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) out[(4 * g + q) * 16 + col] = acc[q];
-    bsum += __shfl_xor(bsum, 16);
-    bsum += __shfl_xor(bsum, 32);
-    if (g == 0) out[256 + col] = bsum;
-}
-
-// fixed-order sum over chunks -> dW, db
 __device__ __forceinline__ float block_sum_1024(float v, float* red) {
     // deterministic sum over blockDim.x (a multiple of 64, <= 1024) threads, result in every thread: a butterfly
     // within each wave (lane 0's fixed association), then the waves' partials in wave order -- two barriers instead
@@ -85,94 +25,9 @@ __device__ __forceinline__ float block_sum_1024(float v, float* red) {
     return r;
 }
 
-// slab partials -> dW / db; every block also emits the sum of squares of the gradients it wrote
-template <int MJ>
-__global__ void __launch_bounds__(256) wgrad_reduce_kernel(WJobsT<MJ> J, const float* __restrict__ slab,
-                                                           float* __restrict__ nrm_part) {
-    __shared__ float red[256];
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over (job, tile, 272)
-    int64_t acc = 0;
-    float sq = 0.f;
-    for (int q = 0; q < J.n; ++q) {
-        const WJob& jb = J.j[q];
-        const int64_t n_el = (int64_t)jb.mt * jb.nt * 272;
-        if (i >= acc && i < acc + n_el) {
-            const int64_t loc = i - acc;
-            const int tt = (int)(loc / 272), e = (int)(loc % 272);
-            const int mt = tt / jb.nt, nt = tt % jb.nt;
-            float s = 0.f;
-            const float* base = slab + jb.slab0 + (int64_t)tt * jb.chunks * 272 + e;
-            for (int ch = 0; ch < jb.chunks; ++ch) s += base[(int64_t)ch * 272];
-            if (e < 256) {
-                const int m = mt * 16 + e / 16, k = nt * 16 + e % 16;
-                if (m < jb.M && k < jb.K) {
-                    jb.dw[(int64_t)m * jb.K + k] = s;
-                    sq = s * s;
-                }
-            } else if (nt == 0 && jb.db) {
-                const int m = mt * 16 + (e - 256);
-                if (m < jb.M) {
-                    jb.db[m] = s;
-                    sq = s * s;
-                }
-            }
-            break;
-        }
-        acc += n_el;
-    }
-    const float bs = block_sum_1024(sq, red);
-    if (threadIdx.x == 0) nrm_part[blockIdx.x] = bs;
-}
-
-
-inline WJob job(const float* delta, int64_t ldd, const float* x, int64_t ldx, float* dw, float* db, int M, int K, int rows) {
-    WJob j;
-    j.delta = delta;
-    j.x = x;
-    j.dw = dw;
-    j.db = db;
-    j.ldd = ldd;
-    j.ldx = ldx;
-    j.M = M;
-    j.K = K;
-    j.rows = rows;
-    j.mt = (M + 15) / 16;
-    j.nt = (K + 15) / 16;
-    j.chunks = (rows + WCH - 1) / WCH;
-    j.task0 = 0;
-    j.slab0 = 0;
-    return j;
-}
-
-// task / slab offsets of a job list; returns the slab floats (partials + per-block norm partials) and the task count
-template <int MJ>
-inline int64_t layout_jobs(WJobsT<MJ>& J, int* n_tasks, int64_t* n_red, int64_t* slab_part) {
-    int tasks = 0;
-    int64_t slab = 0, red = 0;
-    for (int q = 0; q < J.n; ++q) {
-        J.j[q].task0 = tasks;
-        J.j[q].slab0 = slab;
-        tasks += J.j[q].mt * J.j[q].nt * J.j[q].chunks;
-        slab += (int64_t)J.j[q].mt * J.j[q].nt * J.j[q].chunks * 272;
-        red += (int64_t)J.j[q].mt * J.j[q].nt * 272;
-    }
-    *n_tasks = tasks;
-    *n_red = red;
-    *slab_part = mlg_align4(slab);
-    return mlg_align4(slab) + mlg_align4((red + 255) / 256);
-}
-
-}  // namespace mlg
-
-// ================================================================================================
-// Blocked variant: one wave per (job, 64 x 64 output block, 1024-row chunk); per 4-row step every lane loads 4 delta
-// and 4 x values and issues 16 MFMAs (vs 2 loads per MFMA above); the 4 waves of a workgroup (4 chunks of one block)
-// add their partials in LDS, partials [block][chunk group][64 * 64 + 64] summed over groups in a fixed order
-// (deterministic).
-namespace mlg {
-
 constexpr int BCH = 1024;        // max rows per chunk
 constexpr int BSLAB = 64 * 64 + 64;
+constexpr int MLG_WRED_DEPTH = 64;  // slab partials in flight per thread of the reduce pass
 
 struct BJob {
     const float* delta;
@@ -212,18 +67,10 @@ inline BJob bjob(const float* delta, int64_t ldd, const float* x, int64_t ldx, f
     j.mb = (M + 63) / 64;
     j.nb = (K + 63) / 64;
     // chunk length: up to BCH rows, fewer when the job is small so that it still spreads over >= ~256 waves
-    static const int target = [] {  // waves per job (MLG_WGRAD_WAVES overrides, for tuning runs)
-        const char* e = getenv("MLG_WGRAD_WAVES");
-        const int v = e ? atoi(e) : 0;
-        return v > 0 ? v : 256;
-    }();
+    constexpr int target = 256;  // waves per job
     int ch = rows / (target / (j.mb * j.nb) + 1);
     ch = ch < 64 ? 64 : (ch > BCH ? BCH : ch);
-#if defined(MLG_WGRAD_F32)
-    j.ch_rows = (ch + 3) & ~3;
-#else
     j.ch_rows = (ch + 31) & ~31;  // whole 32-row MFMA steps
-#endif
     j.va = (ldd % 4 == 0) && ((uintptr_t)delta % 16 == 0);
     j.vb = (ldx % 4 == 0) && ((uintptr_t)x % 16 == 0);
     j.chunks = (rows + j.ch_rows - 1) / j.ch_rows;
@@ -254,20 +101,6 @@ inline BJob bjob_steps(BJob j, const float* mlen, int R, int NA, int B) {
     return j;
 }
 
-__device__ __forceinline__ bool bjob_row_live(const BJob& jb, int row) {
-    if (!jb.skip) return true;
-    int b, t;
-    if (jb.skip == 1) {
-        const int item = (row / jb.rpi) % jb.I;
-        b = item / jb.T;
-        t = item % jb.T;
-    } else {
-        t = row / jb.R;
-        b = ((row % jb.R) / jb.NA) % jb.B;
-    }
-    return t < (int)jb.mlen[b];
-}
-
 // row chunks are processed (and their partials stored) in groups of 4, one workgroup per group and output block
 __host__ __device__ __forceinline__ int bjob_groups(const BJob& jb) { return (jb.chunks + 3) >> 2; }
 // workgroups of a job: jobs with several output blocks take the groups in stripes of 8 (see wgrad_block_body), the
@@ -285,7 +118,6 @@ __device__ __forceinline__ int find_bjob(const BJobsT<MJ>& J, int task) {
     return k;
 }
 
-#if !defined(MLG_WGRAD_F32)
 // the 8 rows rr + 8g .. rr + 8g + 7 of a lane: delta columns m0 .. m0 + 3 into a, x columns k0 .. k0 + 3 into b
 // (zeros for a dead group / rows past rend / columns past M, K)
 __device__ __forceinline__ void wgrad_load_step(const BJob& jb, int rr, int g, bool glive, int rend, int m0, int k0,
@@ -334,7 +166,6 @@ __device__ __forceinline__ void wgrad_mfma_step(const float (&a)[8][4], const fl
         for (int i = 0; i < 4; ++i) acc[i][j] = mfma_x6(as[i], bs, acc[i][j]);
     }
 }
-#endif
 
 // the work of workgroup `bid` (4 waves = 4 consecutive tasks) of a wgrad launch; a __device__ function so that
 // a learner can run it as extra workgroups of another launch (learner.hip bwd4_wgrad_kernel). 256 threads.
@@ -379,11 +210,10 @@ __device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __r
     // order of every product is unchanged; only the block's output positions are permuted (undone at the store).
     const int m0 = mbi * 64 + 4 * col, k0 = nbi * 64 + 4 * col;
     const bool va = jb.va && m0 + 3 < jb.ldd, vb = jb.vb && k0 + 3 < jb.ldx;
-#if !defined(MLG_WGRAD_F32)
     // 32-row steps on the bf16 matrix cores as split-bf16 fp32 emulation (six partial products, fp32 accumulation,
     // mlg_device.h mfma_x6): lane (col, g) loads rows rr + 8g .. rr + 8g + 7; K slot t of its operands = row
     // rr + 8g + t, so tile i's A operand is element i of the 8 delta vectors and tile j's B operand element j of
-    // the 8 x vectors. Same D layout (and output permutation) as the f32 form below.
+    // the 8 x vectors.
     // jobs that skip dead rows deal their 32-row steps to the chunks round-robin (chunk ch takes steps ch, ch +
     // chunks, ...): the live rows (a prefix of every episode) then spread evenly over the job's waves instead of
     // leaving whole chunks with all the work; other jobs keep contiguous chunks
@@ -491,46 +321,6 @@ __device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __r
         i = next_live(i + 1);
         gl = i < nst && live_of(i);
     }
-#else
-    // two 4-row steps per iteration: both steps' loads are issued before the first step's MFMAs (same
-    // accumulation order as one step per iteration)
-    for (int rr = r0; rr < r1; rr += 8) {
-        float a[2][4], b[2][4];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int row = rr + 4 * h + g;
-            const bool rv = row < r1;
-            const float* dr = jb.delta + (int64_t)row * jb.ldd + m0;
-            const float* xr = jb.x + (int64_t)row * jb.ldx + k0;
-            if (rv && va) {
-                const floatx4 v = ld4(dr);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) a[h][i] = v[i];
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) a[h][i] = (rv && m0 + i < jb.M) ? dr[i] : 0.f;
-            }
-            if (rv && vb) {
-                const floatx4 v = ld4(xr);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) b[h][i] = v[i];
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) b[h][i] = (rv && k0 + i < jb.K) ? xr[i] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            if (h == 1 && rr + 4 >= r1) break;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                bsum[i] += a[h][i];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = mfma4(a[h][i], b[h][j], acc[i][j]);
-            }
-        }
-    }
-#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         bsum[i] += __shfl_xor(bsum[i], 16);
@@ -577,11 +367,7 @@ __device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __r
 // fixed-order sum over chunk groups -> dW / db (bias from the nbi == 0 blocks); per-block sums of squares -> nrm_part
 template <int MJ>
 __global__ void __launch_bounds__(256, 2) wgrad_block_kernel(BJobsT<MJ> J, float* __restrict__ slab) {
-#if defined(MLG_WGRAD_NOGLDS)
-    wgrad_block_body<MJ, false>(J, slab, (int)blockIdx.x);
-#else
     wgrad_block_body<MJ, true>(J, slab, (int)blockIdx.x);
-#endif
 }
 
 template <int MJ>
@@ -602,9 +388,6 @@ __global__ void __launch_bounds__(256) wgrad_block_reduce_kernel(BJobsT<MJ> J, c
             const int ng = bjob_groups(jb);
             const float* base = slab + jb.slab0 + (int64_t)blk * ng * BSLAB + e;
             int ch = 0;
-#ifndef MLG_WRED_DEPTH
-#define MLG_WRED_DEPTH 64
-#endif
             // MLG_WRED_DEPTH loads in flight (the slab partials were just written by other CUs: each round trip is an
             // L2 / MALL miss), summed in group order
             for (; ch + MLG_WRED_DEPTH <= ng; ch += MLG_WRED_DEPTH) {
@@ -680,6 +463,34 @@ inline BJobsT<MJ> bjob_view(const BJobsT<MJ>& J, int q0, int q1, int* n_tasks, i
     *n_tasks = tasks;
     *n_red = red;
     return V;
+}
+
+// clip_grad_norm_ + RMSprop for the parameter of this thread of a finish launch (1024-thread blocks over the flat
+// parameter vector): every block derives the same norm from the reduce pass's per-block partials in a fixed order.
+// Returns the norm. tsync: the target network copy due after this step, stored in the same launch.
+__device__ __forceinline__ float clip_rmsprop_step(float* __restrict__ params, float* __restrict__ grads,
+                                                   float* __restrict__ sq, int64_t n_params,
+                                                   const float* __restrict__ nrm_part, int n_nrm, float lr, float alpha,
+                                                   float eps, float max_norm, float* __restrict__ tsync, float* red) {
+    const int tid = threadIdx.x;
+    // this thread's parameter, gradient and square average, requested before the norm reduction they wait for
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + tid;
+    const bool has = i < n_params;
+    const float g0 = has ? grads[i] : 0.f, sq0 = has ? sq[i] : 0.f, p0 = has ? params[i] : 0.f;
+    float s = 0.f;
+    for (int k = tid; k < n_nrm; k += blockDim.x) s += nrm_part[k];
+    const float norm = sqrtf(block_sum_1024(s, red));
+    const float coef = fminf(max_norm / (norm + 1e-6f), 1.f);  // torch clip_grad_norm_ (clamped coef)
+    if (has) {
+        const float gi = g0 * coef;
+        grads[i] = gi;
+        const float a = alpha * sq0 + (1.f - alpha) * gi * gi;  // RMSprop square_avg
+        sq[i] = a;
+        const float pn = p0 - lr * gi / (sqrtf(a) + eps);
+        params[i] = pn;
+        if (tsync) tsync[i] = pn;
+    }
+    return norm;
 }
 
 }  // namespace mlg

@@ -45,6 +45,17 @@ def np_batch(batch):
     return {k: v.detach().cpu().numpy() for k, v in batch.data.transition_data.items()}
 
 
+def batch_mask_sum(filled, terminated):
+    """The learners' mask sum (reference q_learner.py:58-60, 89-95 after ma_experiment.py:235-239's truncation):
+    mask(b, t) = filled(b, t) * (1 - terminated(b, t - 1)) summed over t < max_t_filled - 1, as float32."""
+    f = np.asarray(filled).reshape(len(filled), -1).astype(np.float32)
+    term = np.asarray(terminated).reshape(len(terminated), -1).astype(np.float32)
+    te = int(np.clip(f.sum(axis=1).max(), 2, f.shape[1]))
+    mask = f.copy()
+    mask[:, 1:] *= 1.0 - term[:, :-1]
+    return np.float32(mask[:, :te - 1].sum())
+
+
 def refil_args(**kw):
     """REFIL (config 5) args: entity scheme + imagine agent + flex_qmix (REFIL defaults)."""
     a = dict(n_agents=8, n_entities=16, n_actions=21, entity_shape=8, entity_last_action=True, attn_embed_dim=64,

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import learner_ref as LR
-from helpers import qmix_args, scheme_for
+from helpers import batch_mask_sum, np_batch, qmix_args, scheme_for
 
 pytestmark = pytest.mark.gpu
 
@@ -60,8 +60,14 @@ def _learner(d, device, args, mixer_prefix="p0.mixer."):
 
 
 @pytest.mark.parametrize("name,kw", [("qlearner_qmix_dq.npz", {}), ("qlearner_qmix_nodq.npz", {"double_q": False}),
-                                     ("qlearner_vdn.npz", {"mixer": "vdn"})])
-def test_qlearner_golden(device, golden, name, kw):
+                                     ("qlearner_vdn.npz", {"mixer": "vdn"}),
+                                     pytest.param("qlearner_qmix_dq.npz", {"generic_mix": True}, id="qmix_dq-generic_mix")])
+def test_qlearner_golden(device, golden, name, kw, monkeypatch):
+    """generic_mix: MLG_MIX_GENERIC=1 (read per call) runs the one-kernel generic QMixer, the path of the shapes
+    outside the prefetching forms, against the same goldens."""
+    kw = dict(kw)
+    if kw.pop("generic_mix", False):
+        monkeypatch.setenv("MLG_MIX_GENERIC", "1")
     d = golden(name)
     args = qmix_args(**kw)
     learner, eb, log = _learner(d, device, args)
@@ -126,6 +132,62 @@ def test_qlearner_vs_oracle_on_rollout(device):
     for t in range(T):
         q = learner.mac.forward(sample, t)
         np.testing.assert_allclose(q.cpu().numpy(), q_ref[:, t].numpy(), atol=1e-4, rtol=0)
+
+
+def _scan_path_case(device, B, episode_limit):
+    """One QLearner.train on the untruncated train-mode rollout of B envs against the oracle on the copy truncated
+    to max_t_filled, plus the exact mask sum (learner._stats[5]) against the reference formula in numpy. For the
+    batch shapes outside the one-round-trip mask statistics (B <= 64, T <= 128: batch_mask_device.h)."""
+    from maleague.components.episode_batch import EpisodeBatch
+    from maleague.controllers import BasicMAC
+    from maleague.custom_logging import MainLogger
+    from maleague.learners import QLearner
+    from maleague.steppers import ParallelStepper
+    args = qmix_args(batch_size_run=B, batch_size=B, seed=1,
+                     env_args={"match_build_plan": "medium_1h_4t", "grid_size": 20, "stochastic_spawns": True,
+                               "episode_limit": episode_limit})
+    stepper = ParallelStepper(args, MainLogger())
+    info = stepper.get_env_info()
+    args.n_agents, args.n_actions, args.state_shape = info["n_agents"], info["n_actions"], info["state_shape"]
+    scheme, groups, preprocess = scheme_for(info, torch)
+    proto = EpisodeBatch(scheme, groups, 1, 2, preprocess=preprocess, device=device)
+    torch.manual_seed(1)
+    mac = BasicMAC(proto.scheme, groups, args)
+    learner = QLearner(mac, proto.scheme, _Log(), args, name="home")
+    agent0 = {k: v.detach().cpu().clone() for k, v in mac.agent.state_dict().items()}
+    mixer0 = {k: v.detach().cpu().clone() for k, v in learner.mixer.state_dict().items()}
+    learner.build_optimizer()
+    stepper.initialize(scheme, groups, preprocess, mac)
+    stepper.t_env = 30000
+    batch, _ = stepper.run(test_mode=False)
+    ep_len = stepper.last_run["ep_len"].numpy()
+    assert batch.batch_size == B and batch.max_seq_length == episode_limit + 1
+    T = int(batch.max_t_filled())
+    tb = {k: v[:, :T].detach().cpu().clone() for k, v in batch.data.transition_data.items()}
+    ref = LR.QLearnerRef(agent0, mixer0, copy.copy(args))
+    exp = ref.train(tb, 30000, 0)
+    learner.train(batch, 30000, 0)
+    for k in ["loss", "grad_norm", "td_error_abs", "q_taken_mean", "target_mean"]:
+        np.testing.assert_allclose(learner.last_stats[k], exp[k], rtol=2e-4, atol=1e-6, err_msg=k)
+    for k, v in learner.mac.agent.state_dict().items():
+        np.testing.assert_allclose(v.cpu().numpy(), ref.agent_state()[k].numpy(), atol=5e-5, rtol=0, err_msg=k)
+    for k, v in learner.mixer.state_dict().items():
+        np.testing.assert_allclose(v.cpu().numpy(), ref.mixer_state()[k].numpy(), atol=5e-5, rtol=0, err_msg=k)
+    nb = np_batch(batch)
+    assert np.float32(learner._stats[5].item()) == batch_mask_sum(nb["filled"], nb["terminated"])
+    return ep_len
+
+
+def test_qlearner_mask_scan_path_many_episodes(device):
+    """72 episodes (> 64): the general mask scan. Some episodes end before the limit, so max_t_filled, the
+    per-episode masks and the truncation all matter."""
+    ep_len = _scan_path_case(device, B=72, episode_limit=100)
+    assert int((ep_len < 100).sum()) > 0, "no episode ended before the limit"
+
+
+def test_qlearner_mask_scan_path_long_episodes(device):
+    """8 episodes stored over 131 steps (> 128): the general mask scan over more than one 64-step chunk pair."""
+    _scan_path_case(device, B=8, episode_limit=130)
 
 
 def test_qlearner_sampled_view_equals_truncated_copy(device):

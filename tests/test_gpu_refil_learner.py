@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import refil_ref as RR
-from helpers import entity_scheme_for, refil_args
+from helpers import batch_mask_sum, entity_scheme_for, refil_args
 
 pytestmark = pytest.mark.gpu
 
@@ -135,6 +135,39 @@ def test_refil_learner_matches_oracle_on_hip_rollouts(device, softmax, double_q)
         for k, v in L.mixer.named_parameters():
             np.testing.assert_allclose(v.detach().cpu().numpy(), ref.mixer[k].detach().numpy(), atol=2e-5, rtol=0,
                                        err_msg=f"call {call} mixer {k}")
+
+
+def test_refil_learner_mask_scan_path(device):
+    """40 episodes (> 32): the general mask scan (batch_mask_device.h) instead of the one-round-trip statistics. One
+    train call against the oracle (a wrong mixlen would drop live items from the loss), and the exact mask sum."""
+    from test_gpu_refil import _rollout
+    B = 40
+    spec, ag, a0, nb, summ, _ = _rollout(device, B=B, T=30, seed=11, eps=0.3, test_mode=False)
+    T = int(summ["len"].max()) + 1
+    arrs = {k: np.ascontiguousarray(v[:, :T]) for k, v in nb.items()}
+    a = refil_args(device="cuda")
+    eb = _batch_from(arrs, device)
+    torch.manual_seed(4)
+    from maleague.modules.mixers import FlexQMixer
+    mixer_p = {k: v.detach().cpu().numpy() for k, v in FlexQMixer(refil_args(device="cpu")).state_dict().items()}
+    agent_p = {k: v.detach().cpu().numpy() for k, v in ag.state_dict().items()}
+    L, _ = _learner(eb, agent_p, mixer_p, a)
+    ref = RR.REFILLearnerRef(agent_p, mixer_p, refil_args(device="cpu"))
+    batch = {k: torch.from_numpy(v) for k, v in arrs.items()}
+    g = torch.Generator().manual_seed(7)
+    groupA = torch.bernoulli(torch.rand(B, 1, 1, generator=g).repeat(1, 1, 16), generator=g).to(torch.uint8)
+    want = ref.train(batch, groupA, episode_num=0)
+    L.train(eb, 0, episode_num=0, groupA=groupA.to(device))
+    got = L.last_stats
+    for k in want:
+        np.testing.assert_allclose(got[k], want[k], rtol=2e-4, atol=1e-5, err_msg=k)
+    for k, v in L.mac.agent.named_parameters():
+        np.testing.assert_allclose(v.detach().cpu().numpy(), ref.agent[k].detach().numpy(), atol=2e-5, rtol=0,
+                                   err_msg=f"agent {k}")
+    for k, v in L.mixer.named_parameters():
+        np.testing.assert_allclose(v.detach().cpu().numpy(), ref.mixer[k].detach().numpy(), atol=2e-5, rtol=0,
+                                   err_msg=f"mixer {k}")
+    assert np.float32(L._stats[6].item()) == batch_mask_sum(arrs["filled"], arrs["terminated"])
 
 
 def test_refil_learner_padded_steps_are_inert(device, golden):
