@@ -192,9 +192,13 @@ typedef struct {
     float *grads;                /* [n_agent + n_mixer] out: clipped gradients */
     float *square_avg;           /* [n_agent + n_mixer] RMSprop state */
     const float *target_params;  /* [n_agent + n_mixer] */
-    float *workspace;            /* mlg_qlearner_workspace_floats() floats */
+    float *workspace;            /* mlg_qlearner_workspace_floats() floats; any contents (a call reads only what it
+                                    wrote; one word carries "target differs" between its launches and is cleared
+                                    by the last) */
     float *stats;                /* [8] out: loss, grad_norm, td_error_abs, q_taken_mean, target_mean,
-                                    mask_sum, count_nonzero(mask), 0 */
+                                    mask_sum, count_nonzero(mask), forward (16-row tile, t, net) blocks planned:
+                                    sum over tiles of the tile's length, times 2 when the target pass ran
+                                    (target_params differ bitwise from params, or MLG_LEARNER_FULL=1) */
     /* optional (NULL = off), folded into the same launches instead of separate copies / adds: */
     float *target_sync;          /* [n_agent + n_mixer] receives the updated parameters (the target update
                                     q_learner.py:127-128 when it is due after this step; usually target_params) */

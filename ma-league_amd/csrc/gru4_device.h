@@ -153,9 +153,11 @@ struct Gru4Bwd {
     const float* dq;               // dQ of the chosen action [T - 1][R]
     const int64_t* actions;        // the batch's actions; row's action at abase + t N (int64 elements)
     float *dgi, *dgh;              // [T][R][3H]
+    int Tz = -1;                   // deltas of steps Te <= t < Tz are zeroed (< 0: up to T). The QMIX learner's weight
+                                   // gradients skip the rows past a tile's steps, so it zeroes none (Tz = 0)
 };
 
-// One 4-row tile of the reverse-time backward over Te steps (rows past Te zeroed: they are wgrad rows). Wave w owns
+// One 4-row tile of the reverse-time backward over Te steps (rows past Te zeroed up to Gru4Bwd::Tz: wgrad rows). Wave w owns
 // hidden features 16w..16w+15; block b = 4kq + fg accumulates W_hh^T dGH for features 16w + 4fg + i over the K
 // quarter kq (48 of the 3H gate rows, W_hh columns in VGPRs). The four quarter partials are summed across the wave's
 // 16-lane rows with a transposing reduction (rows_sum_transpose4): lane (row kq, fg, j) ends up owning feature
@@ -221,7 +223,8 @@ __device__ __forceinline__ void gru4_bwd(const Gru4Bwd& a, int tile, int Te, int
     }
     {  // steps past max_t_filled: zero deltas (wgrad rows); the tile's rows are contiguous per step
         const int nv = min(4, R - tile * 4) * 3 * H / 4;  // float4s per step and array
-        for (int t = Te; t < a.T; ++t) {
+        const int tz = a.Tz < 0 ? a.T : a.Tz;
+        for (int t = Te; t < tz; ++t) {
             float* zi = a.dgi + ((int64_t)t * R + tile * 4) * 3 * H;
             float* zh = a.dgh + ((int64_t)t * R + tile * 4) * 3 * H;
             for (int i = tid; i < nv; i += blockDim.x) {

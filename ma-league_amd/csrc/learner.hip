@@ -13,6 +13,9 @@
 //   wgrad       every weight/bias gradient as sum_rows delta^T x, one wave per 64x64 block and row chunk
 //               (deterministic slab reduction; MFMA with the row index as K)
 //   finish      loss/stat reduction, clip_grad_norm_(10), RMSprop step                       (:104-105, learner.py:25-31)
+// Work whose result nothing reads is not run (Skip, below): steps past the episodes of a 16-row tile, (b, t) mixer
+// rows past the episode's last unmasked transition, and the whole target pass while the target parameters are a
+// bit copy of the online ones. MLG_LEARNER_FULL=1 (read per call) runs every row to max_t_filled and both nets.
 // Tensors saved for backward are t-major: [T][R][F] with R = B * N agent rows (r = b * N + n).
 #include <algorithm>
 
@@ -26,7 +29,6 @@ namespace {
 
 using WJobs = mlg::BJobsT<16>;
 using mlg::block_sum_1024;
-using mlg::t_eff;
 
 // ---- canonical flat parameter offsets (nn.Module named_parameters order) ------------------------
 struct AgentOffs {
@@ -101,14 +103,35 @@ struct LCfg {
     int B, T, T1, N, A, Ap, d_obs, d_in, H, S, E, HE, mixer, double_q, last_action, agent_id;
     int R, RM;
     float gamma;
+    int full;  // MLG_LEARNER_FULL: no skipping
 };
+
+// What a call skips, from prep_kernel (workspace; every kernel after it reads the same three):
+//   mlen[b]   1 + the last t < t_eff - 1 with mask(b, t) != 0: transition (b, t) is live iff t < mlen[b]; the dead
+//             ones have mask 0, so every delta of theirs is an exact zero
+//   l16[tile] steps the agent kernels run for the rows 16 tile .. 16 tile + 15: clamp(max mlen[b] + 1, 2, t_eff)
+//             (the target of transition t reads step t + 1); block (tile, t) is live iff t < l16[tile]. The
+//             recurrences' 4-row tiles run their 16-row tile's steps, so a live block is whole: no kernel reads a
+//             workspace row this call did not write. Exact integers in float.
+//   abits, mbits  the same two predicates per row of the weight-gradient jobs, as bitmaps (wgrad_device.h
+//             bjob_row_bits): agent row t R + r live iff t < l16[r / 16], mixer row b (T - 1) + t iff t < mlen[b]
+//   flag      1 iff some target parameter differs bitwise from its online parameter (stored by prep_kernel's blocks,
+//             cleared by finish_kernel). Otherwise the target network's blocks return at once and its consumers read
+//             the online buffers, which hold the same bits.
+// full: mlen = t_eff - 1 and l16 = t_eff everywhere, target pass always.
+struct Skip {
+    const float *mlen, *l16;
+    const unsigned* flag;
+};
+__device__ __forceinline__ bool target_runs(const LCfg& c, const Skip& k) { return c.full || *k.flag == 1u; }
+__device__ __forceinline__ int tile_steps(const Skip& k, int tile) { return (int)k.l16[tile]; }
 
 // ---- workspace layout --------------------------------------------------------------------------------
 struct WsLayout {
     int64_t p_on, p_tg, wihT, mix_on, mix_tg;
     int64_t in, x, hs, hs_tg, gi_on, gi_tg, gr, gz, gn, ghn, mac, tmac, dq, d2, dgi, dgh, da;
     int64_t srow, l1act, d1, da2, df2, dv2, hyp_on, hyp_tg;
-    int64_t part, msum, rows, nrm, slab, total;
+    int64_t part, msum, rows, mlen, l16, flag, abits, mbits, nrm, slab, total;
     int n_mix_tiles, n_tasks, hyp_stride;
 };
 
@@ -164,7 +187,8 @@ __device__ __forceinline__ float mask_at(const MlgBatch& bt, int b, int t) {
 
 // Fused learner prologue (one launch instead of eight): block 0 sums the mask (batch_mask_device.h); the other blocks
 // pack the online / target agent weights (pack_agent_elem), transpose W_ih (dX pass), pack the online / target
-// QMixer hypernets (pack_mixer_elem) and zero the sparse delta buffers d2 and dq.
+// QMixer hypernets (pack_mixer_elem), zero the sparse delta buffers d2 and dq and compare the target parameters with
+// the online ones (Skip::flag). The target packs always run: whether they are needed is known only after this launch.
 struct PrepJob {
     AgentLayout L;
     MlgAgentParams ap_on, ap_tg;
@@ -182,6 +206,13 @@ struct PrepJob {
     MlgBatch bt;
     int B, T;
     float* msum;
+    float *mlen, *l16;      // Skip tables, written by block 0 after the mask statistics
+    uint32_t *abits, *mbits;
+    unsigned* flag;         // Skip::flag
+    const float *cmp_on, *cmp_tg;  // the flat parameter vectors, compared bitwise
+    int64_t n_cmp;
+    int cmp_vec;            // both 16-byte aligned
+    int R, full;
     int n_rows_in;          // > 0: the slot map travels here (host_rows); block 0 stores it to rows_dst
     int32_t* rows_dst;
     int32_t rows_in[MLG_INLINE_ROWS];
@@ -202,13 +233,59 @@ __global__ void __launch_bounds__(1024) prep_kernel(PrepJob J) {
             b2.rows = srows;
         }
         constexpr int EPW = 4;  // episodes per wave: 16 waves cover batches of up to 64 episodes
-        mlg::batch_mask<EPW>(b2.filled, b2.terminated, b2.T1, [&](int b) { return bslot(b2, b); }, J.B, J.T, J.msum,
-                             nullptr, ms);
+        // the Skip tables stay in LDS for the passes below (up to TABMAX episodes / tiles; global memory otherwise)
+        constexpr int TABMAX = 256;
+        __shared__ float smlen[TABMAX], sl16[TABMAX];
+        const int ntiles = (J.R + 15) / 16;
+        float* ml = J.B <= TABMAX ? smlen : J.mlen;
+        float* lt = ntiles <= TABMAX ? sl16 : J.l16;
+        mlg::batch_mask<EPW>(b2.filled, b2.terminated, b2.T1, [&](int b) { return bslot(b2, b); }, J.B, J.T, J.msum, ml,
+                             ms);
+        __syncthreads();  // ml and ms.te are stored
+        const int Te = min(max(ms.te, 2), J.T);  // = msum[1]
+        for (int b = threadIdx.x; b < J.B; b += blockDim.x) {
+            if (J.full) ml[b] = (float)(Te - 1);
+            if (ml != J.mlen) J.mlen[b] = ml[b];
+        }
+        if (J.full) __syncthreads();
+        for (int tile = threadIdx.x; tile < ntiles; tile += blockDim.x) {
+            int m = 0;  // the tile's rows cover episodes (16 tile) / N .. (16 tile + 15) / N
+            const int b1 = (min(J.R, tile * 16 + 16) - 1) / J.N;
+            for (int b = tile * 16 / J.N; b <= b1; ++b) m = max(m, (int)ml[b] + 1);
+            const float v = (float)min(max(m, 2), Te);
+            lt[tile] = v;
+            if (lt != J.l16) J.l16[tile] = v;
+        }
+        __syncthreads();  // lt is stored
+        // the weight-gradient jobs' row bitmaps, a 32-row word per thread, by runs of rows that share a table entry:
+        // agent rows t R + r by 16-row tile (whole run live iff t < l16), mixer rows b (T - 1) + t by episode (the
+        // run's first mlen[b] - t rows live)
+        const int TR = J.T * J.R, Tm = J.T - 1, RM = J.B * Tm;
+        const int na = (TR + 31) / 32, nm = J.mixer == 2 ? (RM + 31) / 32 : 0;
+        for (int j = threadIdx.x; j < na + nm; j += blockDim.x) {
+            const bool ag = j < na;
+            const int row0 = 32 * (ag ? j : j - na), D = ag ? J.R : Tm, rows = ag ? TR : RM;
+            int hi = row0 / D, lo = row0 - hi * D, k = 0;
+            uint32_t m = 0;
+            while (k < 32 && row0 + k < rows) {
+                const int run = ag ? min(((lo >> 4) + 1) << 4, D) - lo : D - lo;
+                const int n = min(run, min(32 - k, rows - row0 - k));
+                const int live = ag ? (hi < (int)lt[lo >> 4] ? n : 0) : min(max((int)ml[hi] - lo, 0), n);
+                if (live > 0) m |= (live >= 32 ? 0xFFFFFFFFu : (1u << live) - 1u) << k;
+                k += n;
+                lo += n;
+                if (lo == D) {
+                    lo = 0;
+                    ++hi;
+                }
+            }
+            (ag ? J.abits : J.mbits)[ag ? j : j - na] = m;
+        }
         return;
     }
     const int64_t na = J.L.gsp,  // the learner reads no pre-split rollout sections (gsp, w1s)
                    nt = (int64_t)J.rows3 * J.cols, nm = J.mixer == 2 ? J.mp.total : 0;
-    const int64_t total = 2 * na + nt + 2 * nm + J.n_d2 + J.n_dq;
+    const int64_t total = 2 * na + nt + 2 * nm + J.n_d2 + J.n_dq + (J.n_cmp + 3) / 4;
     for (int64_t i = (int64_t)(blockIdx.x - 1) * blockDim.x + threadIdx.x; i < total;
          i += (int64_t)(gridDim.x - 1) * blockDim.x) {
         int64_t k = i;
@@ -228,7 +305,19 @@ __global__ void __launch_bounds__(1024) prep_kernel(PrepJob J) {
         k -= nm;
         if (k < J.n_d2) { J.d2[k] = 0.f; continue; }
         k -= J.n_d2;
-        J.dq[k] = 0.f;
+        if (k < J.n_dq) { J.dq[k] = 0.f; continue; }
+        k -= J.n_dq;
+        // four parameters per item. Bits, not values: a NaN equals only its own copy, and -0 differs from 0
+        bool ne = false;
+        if (J.cmp_vec && 4 * k + 3 < J.n_cmp) {
+            const uint4 a = *reinterpret_cast<const uint4*>(J.cmp_on + 4 * k);
+            const uint4 b = *reinterpret_cast<const uint4*>(J.cmp_tg + 4 * k);
+            ne = a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w;
+        } else {
+            for (int64_t e = 4 * k; e < min(4 * k + 4, J.n_cmp); ++e)
+                ne = ne || __float_as_uint(J.cmp_on[e]) != __float_as_uint(J.cmp_tg[e]);
+        }
+        if (ne) *J.flag = 1u;
     }
 }
 
@@ -293,13 +382,14 @@ template <int H>
 __global__ void __launch_bounds__(512) agent_in_kernel(LCfg c, MlgBatch bt, AgentLayout L, const float* __restrict__ Pon,
                                                        const float* __restrict__ Ptg, float* __restrict__ ws_in,
                                                        float* __restrict__ ws_x, float* __restrict__ gi_on,
-                                                       float* __restrict__ gi_tg, const float* __restrict__ msum) {
+                                                       float* __restrict__ gi_tg, Skip sk) {
     constexpr int HC = H / 16;
     constexpr int LDA = H + 4;
     __shared__ __attribute__((aligned(16))) float xs[16 * LDA];
     const int tile = blockIdx.x, t = blockIdx.y;
-    if (t >= t_eff(msum)) return;
+    if (t >= tile_steps(sk, tile)) return;
     const bool online = blockIdx.z == 0;
+    if (!online && !target_runs(c, sk)) return;
     const float* P = online ? Pon : Ptg;
     float* gi = online ? gi_on : gi_tg;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -368,15 +458,17 @@ __device__ __forceinline__ void agent_rec4_body(const LCfg& c, const AgentLayout
                                                 const float* __restrict__ gi_tg, float* __restrict__ hs_on,
                                                 float* __restrict__ hs_tg, float* __restrict__ ws_gr,
                                                 float* __restrict__ ws_gz, float* __restrict__ ws_gn,
-                                                float* __restrict__ ws_ghn, const float* __restrict__ msum, int bid) {
-    LStamps lst;
-    lst.init();
+                                                float* __restrict__ ws_ghn, const Skip& sk, int bid) {
     const int nt4 = (c.R + 3) / 4;
     const bool online = bid < nt4;
+    if (!online && !target_runs(c, sk)) return;
+    LStamps lst;
+    lst.init();
     const float* P = online ? Pon : Ptg;
     const mlg::Gru4Fwd a{c.R, P + L.whh, P + L.bhh, online ? gi_on : gi_tg, online ? hs_on : hs_tg,
                          ws_gr, ws_gz, ws_gn, ws_ghn, online};
-    mlg::gru4_fwd<H>(a, online ? bid : bid - nt4, t_eff(msum), lst);
+    const int tile4 = online ? bid : bid - nt4;
+    mlg::gru4_fwd<H>(a, tile4, tile_steps(sk, tile4 >> 2), lst);
     lst.flush(0);
 }
 
@@ -386,8 +478,8 @@ __global__ void __launch_bounds__(512) agent_rec4_kernel(LCfg c, AgentLayout L, 
                                                          const float* __restrict__ gi_tg, float* __restrict__ hs_on,
                                                          float* __restrict__ hs_tg, float* __restrict__ ws_gr,
                                                          float* __restrict__ ws_gz, float* __restrict__ ws_gn,
-                                                         float* __restrict__ ws_ghn, const float* __restrict__ msum) {
-    agent_rec4_body<H>(c, L, Pon, Ptg, gi_on, gi_tg, hs_on, hs_tg, ws_gr, ws_gz, ws_gn, ws_ghn, msum, blockIdx.x);
+                                                         float* __restrict__ ws_ghn, Skip sk) {
+    agent_rec4_body<H>(c, L, Pon, Ptg, gi_on, gi_tg, hs_on, hs_tg, ws_gr, ws_gz, ws_gn, ws_ghn, sk, blockIdx.x);
 }
 
 // grid (ntiles, T, 2), Ap/16 waves: wave = action tile. q = b2 + W2 . h_t (h_t = HS[t + 1]).
@@ -395,11 +487,12 @@ template <int H>
 __global__ void __launch_bounds__(512) agent_q_kernel(LCfg c, AgentLayout L, const float* __restrict__ Pon,
                                                       const float* __restrict__ Ptg, const float* __restrict__ hs_on,
                                                       const float* __restrict__ hs_tg, float* __restrict__ mac,
-                                                      float* __restrict__ tmac, const float* __restrict__ msum) {
+                                                      float* __restrict__ tmac, Skip sk) {
     constexpr int HC = H / 16;
     const int tile = blockIdx.x, t = blockIdx.y;
-    if (t >= t_eff(msum)) return;
+    if (t >= tile_steps(sk, tile)) return;
     const bool online = blockIdx.z == 0;
+    if (!online && !target_runs(c, sk)) return;
     const float* P = online ? Pon : Ptg;
     const float* hsg = (online ? hs_on : hs_tg) + (int64_t)(t + 1) * c.R * H;
     float* qout = online ? mac : tmac;
@@ -867,8 +960,8 @@ struct MixOut {
 // Identical arithmetic either way.
 template <int HE, int E, bool FAST = false>
 __global__ void __launch_bounds__(128) mix_td_kernel(LCfg c, MlgBatch bt, MixPtrs Mon, MixPtrs Mtg, MixPack mp,
-                                                    const float* __restrict__ mac, const float* __restrict__ tmac,
-                                                    const float* __restrict__ msum_p, MixOut o) {
+                                                    const float* __restrict__ mac, const float* __restrict__ tmac_,
+                                                    const float* __restrict__ msum_p, MixOut o, Skip sk) {
     using Mx = Mixer<HE, E>;
     using MP = MixerPF<HE, E, 4, MIXPF_N>;
     floatx4 w1c[MIXPF_N][Mx::TE];  // FAST: the online forward's pre-abs hyper_w_1 outputs
@@ -882,20 +975,30 @@ __global__ void __launch_bounds__(128) mix_td_kernel(LCfg c, MlgBatch bt, MixPtr
     const bool valid = rm < c.RM;
     const int b = valid ? rm / Tm : 0, t = valid ? rm % Tm : 0;
     const int N = c.N, S = c.S, L1 = 2 * HE + 2 * E, NE = N * E;
+    // a dead transition (Skip::mlen) has mask 0: it takes zeros for its Qs and state, stores nothing (the weight
+    // gradients skip its rows, dq / d2 keep prep_kernel's zeros) and adds exact zeros to the tile's sums
+    const bool live = valid && t < (int)sk.mlen[b];
+    if (!__any(live)) {  // both waves of the tile alike
+        if (wv == 1 && lane < 4) o.part[(int64_t)blockIdx.x * 4 + lane] = 0.f;
+        return;
+    }
+    const bool tr = target_runs(c, sk);  // else the online buffers hold the target's bits
+    const float* tmac = tr ? tmac_ : mac;
+    const MixPtrs& Mt = tr ? Mtg : Mon;
     float cq[MAXN], tq[MAXN];
     for (int n = 0; n < N; ++n) cq[n] = tq[n] = 0.f;
-    if (valid) {
+    if (live) {
         if constexpr (FAST)
             gather_q_pf<MIXPF_A>(c, bt, mac, tmac, b, t, cq, tq);
         else
             gather_q(c, bt, mac, tmac, b, t, cq, tq);
     }
-    const float m = (valid && t < t_eff(msum_p) - 1) ? mask_at(bt, b, t) : 0.f;  // reference truncation
+    const float m = live ? mask_at(bt, b, t) : 0.f;  // reference truncation: mlen <= t_eff - 1
     const float rwd = valid ? bt.reward[bslot(bt, b) * bt.T1 + t] : 0.f;
     const float term = valid ? (float)bt.terminated[bslot(bt, b) * bt.T1 + t] : 0.f;
     const float msum = msum_p[0];
-    const float* s0 = valid ? bt.state + (bslot(bt, b) * bt.T1 + t) * S : nullptr;
-    const float* s1 = valid ? bt.state + (bslot(bt, b) * bt.T1 + t + 1) * S : nullptr;
+    const float* s0 = live ? bt.state + (bslot(bt, b) * bt.T1 + t) * S : nullptr;
+    const float* s1 = live ? bt.state + (bslot(bt, b) * bt.T1 + t + 1) * S : nullptr;
     float qtot, tgt;
     floatx4 l1[Mx::L1T], pre[Mx::TE], hid[Mx::TE], wfp[Mx::TE];
     if (c.mixer == 2) {
@@ -904,9 +1007,9 @@ __global__ void __launch_bounds__(128) mix_td_kernel(LCfg c, MlgBatch bt, MixPtr
             float tv;
             if constexpr (FAST) {
                 floatx4 tw1c[MIXPF_N][Mx::TE];
-                tv = MP::forward(Mtg, mp, S, N, s1, tq, tl1, tpre, thid, twfp, tw1c, lane);
+                tv = MP::forward(Mt, mp, S, N, s1, tq, tl1, tpre, thid, twfp, tw1c, lane);
             } else {
-                tv = Mx::forward(Mtg, mp, S, N, s1, tq, tl1, tpre, thid, twfp, lane);
+                tv = Mx::forward(Mt, mp, S, N, s1, tq, tl1, tpre, thid, twfp, lane);
             }
             if (g == 0) tgt_sh[col] = tv;
             qtot = 0.f;
@@ -992,7 +1095,7 @@ __global__ void __launch_bounds__(128) mix_td_kernel(LCfg c, MlgBatch bt, MixPtr
                     const float sg = wp[q] > 0.f ? 1.f : (wp[q] < 0.f ? -1.f : 0.f);
                     dlt[q] = cq[n] * dpre[cc][q] * sg;
                 }
-                if (valid) *reinterpret_cast<floatx4*>(o.da2 + (int64_t)rm * NE + n * E + cc * 16 + 4 * g) = dlt;
+                if (live) *reinterpret_cast<floatx4*>(o.da2 + (int64_t)rm * NE + n * E + cc * 16 + 4 * g) = dlt;
                 // dw1h += W_a2^T[:, n*E + cc*16 ..] . dlt   (a2T is [HE][NE])
 #pragma unroll
                 for (int mt = 0; mt < Mx::T1H; ++mt) {
@@ -1018,7 +1121,7 @@ __global__ void __launch_bounds__(128) mix_td_kernel(LCfg c, MlgBatch bt, MixPtr
                 acc = mfma_chunk(ld4(Mon.f2T + (int64_t)(mt * 16 + col) * E + cc * 16 + 4 * g), dwf[cc], acc);
             dwfh[mt] = acc;
         }
-        if (valid) {
+        if (live) {
             float* d1 = o.d1 + (int64_t)rm * L1;
             float* la = o.l1act + (int64_t)rm * L1;
 #pragma unroll
@@ -1056,7 +1159,7 @@ __global__ void __launch_bounds__(128) mix_td_kernel(LCfg c, MlgBatch bt, MixPtr
         for (int n = 0; n < N; ++n) dq[n] = dy;
     }
     // ---- dQ per agent row (t-major) and its one-hot expansion for dW2 ----
-    if (valid && g == 0) {
+    if (live && g == 0) {
         for (int n = 0; n < N; ++n) {
             const int r = b * N + n;
             o.dq[(int64_t)t * c.R + r] = dq[n];
@@ -1083,7 +1186,8 @@ struct HypOut {
 // One 16-row tile by a pair of waves: wv 0 the target net on s_{t+1}, wv 1 the online net on s_t.
 template <int HE, int E>
 __device__ __forceinline__ void mix_pre_tile(const LCfg& c, const MlgBatch& bt, const MixPtrs& Mon, const MixPtrs& Mtg,
-                                             const MixPack& mp, const HypOut& o, int tile, int wv, int lane) {
+                                             const MixPack& mp, const HypOut& o, const Skip& sk, int tile, int wv,
+                                             int lane) {
     using Mx = Mixer<HE, E>;
     using MP = MixerPF<HE, E, 4, MIXPF_N>;
     const int col = lane & 15, g = lane >> 4;
@@ -1093,6 +1197,15 @@ __device__ __forceinline__ void mix_pre_tile(const LCfg& c, const MlgBatch& bt, 
     const bool valid = rm < c.RM;
     const int b = valid ? rm / Tm : 0, t = valid ? rm % Tm : 0;
     const int N = c.N, S = c.S, NE = N * E, L1 = 2 * HE + 2 * E;
+    {  // Which rows of the tile does mix_td2 read? (a wave that has any stores all of its tile's rows)
+        //   online: s_t of a live transition (t < mlen) and, as the target's input while the target net is a copy of the
+        //           online one, s_{t+1} of the episode's last live transition: t <= mlen
+        //   target: s_{t+1} of the live transitions; while it is a copy, only those whose t + 1 has no online row
+        //           (t = T - 2: the online rows end there)
+        const int ml = valid ? (int)sk.mlen[b] : 0;
+        const bool need = valid && (tgt ? t < ml && (t == Tm - 1 || target_runs(c, sk)) : t <= ml);
+        if (!__any(need)) return;
+    }
     const float* s = valid ? bt.state + (bslot(bt, b) * bt.T1 + t + (tgt ? 1 : 0)) * S : nullptr;
     floatx4 l1[Mx::L1T], w1p[MIXPF_N][Mx::TE], wfp[Mx::TE];
     float v;
@@ -1129,23 +1242,23 @@ __global__ void __launch_bounds__(512) rec4_mixpre_kernel(LCfg c, AgentLayout L,
                                                           const float* __restrict__ gi_tg, float* __restrict__ hs_on,
                                                           float* __restrict__ hs_tg, float* __restrict__ ws_gr,
                                                           float* __restrict__ ws_gz, float* __restrict__ ws_gn,
-                                                          float* __restrict__ ws_ghn, const float* __restrict__ msum,
+                                                          float* __restrict__ ws_ghn, Skip sk,
                                                           MlgBatch bt, MixPtrs Mon, MixPtrs Mtg, MixPack mp, HypOut o) {
     const int nrec = 2 * ((c.R + 3) / 4);
     if ((int)blockIdx.x < nrec) {
-        agent_rec4_body<H>(c, L, Pon, Ptg, gi_on, gi_tg, hs_on, hs_tg, ws_gr, ws_gz, ws_gn, ws_ghn, msum, blockIdx.x);
+        agent_rec4_body<H>(c, L, Pon, Ptg, gi_on, gi_tg, hs_on, hs_tg, ws_gr, ws_gz, ws_gn, ws_ghn, sk, blockIdx.x);
         return;
     }
     const int w = threadIdx.x >> 6, per = blockDim.x / 128;
     const int tile = ((int)blockIdx.x - nrec) * per + (w >> 1);
     if (tile * 16 >= c.RM) return;  // whole pair of waves past the last tile (block-uniform per wave pair)
-    mix_pre_tile<64, 32>(c, bt, Mon, Mtg, mp, o, tile, w & 1, threadIdx.x & 63);
+    mix_pre_tile<64, 32>(c, bt, Mon, Mtg, mp, o, sk, tile, w & 1, threadIdx.x & 63);
 }
 
 template <int HE, int E>
 __global__ void __launch_bounds__(128) mix_td2_kernel(LCfg c, MlgBatch bt, MixPtrs Mon, const float* __restrict__ mac,
-                                                      const float* __restrict__ tmac, const float* __restrict__ msum_p,
-                                                      HypOut hy, MixOut o) {
+                                                      const float* __restrict__ tmac_, const float* __restrict__ msum_p,
+                                                      HypOut hy, MixOut o, Skip sk) {
     using Mx = Mixer<HE, E>;
     using MP = MixerPF<HE, E, 4, MIXPF_N>;
     constexpr int TE = Mx::TE, T1H = Mx::T1H;
@@ -1156,8 +1269,32 @@ __global__ void __launch_bounds__(128) mix_td2_kernel(LCfg c, MlgBatch bt, MixPt
     const bool valid = rm < c.RM;
     const int b = valid ? rm / Tm : 0, t = valid ? rm % Tm : 0;
     const int N = c.N, NE = N * E, L1 = 2 * HE + 2 * E;
-    // this lane's hypernet outputs (rows past RM read row 0: finite, and their results are never stored)
-    const float* h = (wv == 0 ? hy.tg : hy.on) + (int64_t)(valid ? rm : 0) * hy.hs;
+    // dead transitions as in mix_td_kernel: zeros for their Qs, nothing stored, exact zeros into the tile's sums
+    const bool live = valid && t < (int)sk.mlen[b];
+    const uint64_t lv = __ballot(live);
+    if (!lv) {  // both waves of the tile alike
+        if (wv == 1 && lane < 4) o.part[(int64_t)blockIdx.x * 4 + lane] = 0.f;
+        return;
+    }
+    const bool tr = target_runs(c, sk);  // else the online buffers hold the target's bits
+    const float* tmac = tr ? tmac_ : mac;
+    // this lane's hypernet outputs. Online (wave 1): its own row; mix_pre_tile stored every row of a tile that has a
+    // live one, and row 0 (rows past RM) is always among them. Target (wave 0): its own row of hy.tg, or while the
+    // target net is a copy of the online one the online outputs on s_{t+1} = row rm + 1 (t = T - 2 has none: hy.tg,
+    // see mix_pre_tile); a dead lane takes the row of the tile's first live lane, which is there and finite.
+    const float* h;
+    if (wv == 0) {
+        int use_on = (!tr && t + 1 < Tm) ? 1 : 0, row = use_on ? rm + 1 : rm;
+        const int first = __builtin_ctzll(lv);
+        const int f_on = __shfl(use_on, first), f_row = __shfl(row, first);
+        if (!live) {
+            use_on = f_on;
+            row = f_row;
+        }
+        h = (use_on ? hy.on : hy.tg) + (int64_t)row * hy.hs;
+    } else {
+        h = hy.on + (int64_t)(valid ? rm : 0) * hy.hs;
+    }
     floatx4 w1c[MIXPF_N][TE], wfp[TE], b1[TE];
 #pragma unroll
     for (int n = 0; n < MIXPF_N; ++n) {
@@ -1200,13 +1337,13 @@ __global__ void __launch_bounds__(128) mix_td2_kernel(LCfg c, MlgBatch bt, MixPt
     }
     float cq[MAXN], tq[MAXN];
     for (int n = 0; n < N; ++n) cq[n] = tq[n] = 0.f;
-    gather_q_rows<MIXPF_A>(c, bt, mac, tmac, b, t, valid, g, cq, tq);
+    gather_q_rows<MIXPF_A>(c, bt, mac, tmac, b, t, live, g, cq, tq);
     floatx4 pre[TE], hid[TE];
     if (wv == 0) {
         const float tv = MP::mix(N, tq, b1, w1c, wfp, vv, pre, hid);
         if (g == 0) tgt_sh[col] = tv;
     }
-    const float m = (valid && t < t_eff(msum_p) - 1) ? mask_at(bt, b, t) : 0.f;  // reference truncation
+    const float m = live ? mask_at(bt, b, t) : 0.f;  // reference truncation: mlen <= t_eff - 1
     const float rwd = valid ? bt.reward[bslot(bt, b) * bt.T1 + t] : 0.f;
     const float term = valid ? (float)bt.terminated[bslot(bt, b) * bt.T1 + t] : 0.f;
     const float msum = msum_p[0];
@@ -1265,7 +1402,7 @@ __global__ void __launch_bounds__(128) mix_td2_kernel(LCfg c, MlgBatch bt, MixPt
                 const float sg = wp[q] > 0.f ? 1.f : (wp[q] < 0.f ? -1.f : 0.f);
                 dlt[q] = cq[n] * dpre[cc][q] * sg;
             }
-            if (valid) *reinterpret_cast<floatx4*>(o.da2 + (int64_t)rm * NE + n * E + cc * 16 + 4 * g) = dlt;
+            if (live) *reinterpret_cast<floatx4*>(o.da2 + (int64_t)rm * NE + n * E + cc * 16 + 4 * g) = dlt;
 #pragma unroll
             for (int mt = 0; mt < T1H; ++mt) dw1h[mt] = mfma_chunk(aT[cc][mt], dlt, dw1h[mt]);
         }
@@ -1281,7 +1418,7 @@ __global__ void __launch_bounds__(128) mix_td2_kernel(LCfg c, MlgBatch bt, MixPt
         for (int cc = 0; cc < TE; ++cc) acc = mfma_chunk(f2w[mt][cc], dwf[cc], acc);
         dwfh[mt] = acc;
     }
-    if (valid) {
+    if (live) {
         // layer-1 activations (stored by mix_pre_tile, loaded above) for the ReLU masks
         float* d1 = o.d1 + (int64_t)rm * L1;
 #pragma unroll
@@ -1313,7 +1450,7 @@ __global__ void __launch_bounds__(128) mix_td2_kernel(LCfg c, MlgBatch bt, MixPt
         }
         if (g == 0) o.dv2[rm] = dy;
     }
-    if (valid && g == 0) {  // dQ per agent row (t-major) and its one-hot expansion for dW2 (d2 zeroed by prep_kernel:
+    if (live && g == 0) {  // dQ per agent row (t-major) and its one-hot expansion for dW2 (d2 zeroed by prep_kernel:
                             // whole-row writes here measured 3.7 us slower, and the zeroing is off prep's critical path)
         for (int n = 0; n < N; ++n) {
             const int r = b * N + n;
@@ -1338,16 +1475,15 @@ __global__ void __launch_bounds__(512) agent_bwd4_kernel(LCfg c, MlgBatch bt, Ag
                                                          const float* __restrict__ ws_hs, const float* __restrict__ ws_gr,
                                                          const float* __restrict__ ws_gz, const float* __restrict__ ws_gn,
                                                          const float* __restrict__ ws_ghn, const float* __restrict__ dqv,
-                                                         float* __restrict__ dgi, float* __restrict__ dgh,
-                                                         const float* __restrict__ msum) {
+                                                         float* __restrict__ dgi, float* __restrict__ dgh, Skip sk) {
     LStamps lst;
     lst.init();
     const int r = blockIdx.x * 4 + ((threadIdx.x & 63) & 3);
     const bool valid = r < c.R;
     const int b = valid ? r / c.N : 0, n = valid ? r % c.N : 0;
     const mlg::Gru4Bwd a{c.R, c.T, c.A, c.N, P + L.whh, P + L.w2, ws_hs, ws_gr, ws_gz, ws_gn, ws_ghn, dqv,
-                         bt.actions, dgi, dgh};
-    mlg::gru4_bwd<H>(a, blockIdx.x, t_eff(msum), bslot(bt, b) * bt.T1 * c.N + n, lst);
+                         bt.actions, dgi, dgh, 0};  // no zeroed tail: the weight gradients skip those rows
+    mlg::gru4_bwd<H>(a, blockIdx.x, tile_steps(sk, blockIdx.x >> 2), bslot(bt, b) * bt.T1 * c.N + n, lst);
     lst.flush(1);
 }
 
@@ -1361,9 +1497,8 @@ __global__ void __launch_bounds__(256, 2) bwd4_wgrad_kernel(LCfg c, MlgBatch bt,
                                                          const float* __restrict__ ws_hs, const float* __restrict__ ws_gr,
                                                          const float* __restrict__ ws_gz, const float* __restrict__ ws_gn,
                                                          const float* __restrict__ ws_ghn, const float* __restrict__ dqv,
-                                                         float* __restrict__ dgi, float* __restrict__ dgh,
-                                                         const float* __restrict__ msum, WJobs JA,
-                                                         float* __restrict__ slab, int nbwd) {
+                                                         float* __restrict__ dgi, float* __restrict__ dgh, Skip sk,
+                                                         WJobs JA, float* __restrict__ slab, int nbwd) {
     if ((int)blockIdx.x >= nbwd) {
         mlg::wgrad_block_body<16>(JA, slab, (int)blockIdx.x - nbwd);
         return;
@@ -1374,8 +1509,8 @@ __global__ void __launch_bounds__(256, 2) bwd4_wgrad_kernel(LCfg c, MlgBatch bt,
     const bool valid = r < c.R;
     const int b = valid ? r / c.N : 0, n = valid ? r % c.N : 0;
     const mlg::Gru4Bwd a{c.R, c.T, c.A, c.N, P + L.whh, P + L.w2, ws_hs, ws_gr, ws_gz, ws_gn, ws_ghn, dqv,
-                         bt.actions, dgi, dgh};
-    mlg::gru4_bwd<H>(a, blockIdx.x, t_eff(msum), bslot(bt, b) * bt.T1 * c.N + n, lst);
+                         bt.actions, dgi, dgh, 0};  // no zeroed tail: the weight gradients skip those rows
+    mlg::gru4_bwd<H>(a, blockIdx.x, tile_steps(sk, blockIdx.x >> 2), bslot(bt, b) * bt.T1 * c.N + n, lst);
     lst.flush(1);
 }
 
@@ -1383,17 +1518,13 @@ __global__ void __launch_bounds__(256, 2) bwd4_wgrad_kernel(LCfg c, MlgBatch bt,
 template <int H>
 __global__ void __launch_bounds__(512) agent_dx_kernel(LCfg c, const float* __restrict__ wihT,
                                                        const float* __restrict__ ws_x, const float* __restrict__ dgi,
-                                                       float* __restrict__ da, const float* __restrict__ msum) {
+                                                       float* __restrict__ da, Skip sk) {
     const int tile = blockIdx.x, t = blockIdx.y;
+    if (t >= tile_steps(sk, tile)) return;  // the fc1 weight gradient skips the block's rows
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int col = lane & 15, g = lane >> 4;
     const int r = tile * 16 + col;
     const bool valid = r < c.R;
-    if (t >= t_eff(msum)) {
-        if (valid)
-            *reinterpret_cast<floatx4*>(da + ((int64_t)t * c.R + r) * H + w * 16 + 4 * g) = floatx4{0.f, 0.f, 0.f, 0.f};
-        return;
-    }
     const int64_t row = (int64_t)t * c.R + (valid ? r : 0);
     const float* wrow = wihT + (int64_t)(w * 16 + col) * 3 * H + 4 * g;
     const float* grow = dgi + row * 3 * H + 4 * g;
@@ -1411,15 +1542,24 @@ __global__ void __launch_bounds__(512) agent_dx_kernel(LCfg c, const float* __re
 
 // ================================================================================================
 // clip_grad_norm_ + RMSprop over all parameters (grid-wide; every block derives the same norm from the
-// per-block partials in a fixed order), loss/stat reduction in block 0.
+// per-block partials in a fixed order), loss/stat reduction in block 0, which also reports the planned forward blocks
+// (stats[7]) and clears Skip::flag for the next call.
 __global__ void __launch_bounds__(1024) finish_kernel(const float* __restrict__ part, int n_part,
                                                       const float* __restrict__ msum_p, float* __restrict__ params,
                                                       float* __restrict__ grads, float* __restrict__ sq, int64_t n_params,
                                                       float lr, float alpha, float eps, float max_norm, int N,
                                                       float* __restrict__ stats, const float* __restrict__ nrm_part,
-                                                      int n_nrm, float* __restrict__ tsync, double* __restrict__ trained) {
+                                                      int n_nrm, float* __restrict__ tsync, double* __restrict__ trained,
+                                                      Skip sk, unsigned* __restrict__ flag, int ntiles, int full) {
     __shared__ float red[1024];
     const int tid = threadIdx.x;
+    // the planned forward blocks (stats[7]: exact integers, any order) and the flag, requested ahead of the step
+    float blocks = 0.f;
+    unsigned fl = 0u;
+    if (blockIdx.x == 0 && tid < 64) {
+        for (int k = tid; k < ntiles; k += 64) blocks += sk.l16[k];
+        fl = *flag;
+    }
     // target update due after this step (q_learner.py:127-128): tsync
     const float norm = mlg::clip_rmsprop_step(params, grads, sq, n_params, nrm_part, n_nrm, lr, alpha, eps, max_norm,
                                               tsync, red);
@@ -1436,11 +1576,16 @@ __global__ void __launch_bounds__(1024) finish_kernel(const float* __restrict__ 
             else stats[k + 1] = sk / (ms * N);  // k = 2, 3: stats[3], stats[4] (per agent)
         }
     }
+    if (blockIdx.x == 0 && tid < 64) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) blocks += __shfl_xor(blocks, m);
+    }
     if (blockIdx.x == 0 && tid == 0) {
         stats[1] = norm;
         stats[5] = ms;
         stats[6] = ms;
-        stats[7] = 0.f;
+        stats[7] = (full || fl == 1u) ? 2.f * blocks : blocks;  // forward (16-row tile, t, net) blocks of this call
+        *flag = 0u;  // the next call's prep_kernel stores 1 where its target differs
         if (trained) trained[0] += (double)ms;  // Agent.trained_steps (q_learner.py:104)
     }
 }
@@ -1497,6 +1642,7 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
     c.R = cfg->B * cfg->N;
     c.RM = cfg->B * (cfg->T - 1);
     c.gamma = cfg->gamma;
+    c.full = getenv("MLG_LEARNER_FULL") != nullptr;  // read per call, so a test can set it
     MlgAgentDims d{cfg->d_obs, cfg->A, cfg->N, cfg->H, c.d_in, cfg->obs_last_action, cfg->obs_agent_id};
     p.L = make_agent_layout(d);
     p.ao = agent_offs(c.H, c.d_in, c.A);
@@ -1544,6 +1690,11 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
     w.part = take((int64_t)w.n_mix_tiles * 4);
     w.msum = take(4);
     w.rows = take(MLG_INLINE_ROWS);
+    w.mlen = take(c.B);
+    w.l16 = take((R + 15) / 16);
+    w.flag = take(4);
+    w.abits = take((T * R + 31) / 32);
+    w.mbits = take((RM + 31) / 32);
     w.nrm = 0;  // placed after the slab (size known once the jobs are built)
     w.slab = o;
     w.total = o;  // + slab size, filled by make_jobs
@@ -1567,6 +1718,7 @@ WJobs make_jobs(Plan& p, float* ws, float* grads, int64_t* slab_floats, int* n_t
     J.j[J.n++] = mlg::bjob(at(p.w.dgh), 3 * H, at(p.w.hs), H, gp(a.whh), gp(a.bhh), 3 * H, H, TR);
     J.j[J.n++] = mlg::bjob(at(p.w.d2), c.A, at(p.w.hs) ? at(p.w.hs) + (int64_t)c.R * H : nullptr, H, gp(a.fc2w), gp(a.fc2b),
                      c.A, H, TR);
+    const int n_agent_jobs = J.n;
     if (c.mixer == 2) {
         const MixOffs& m = p.mo;
         const int64_t G0 = p.n_agent;
@@ -1581,6 +1733,12 @@ WJobs make_jobs(Plan& p, float* ws, float* grads, int64_t* slab_floats, int* n_t
         J.j[J.n++] = mlg::bjob(at(p.w.da2), (int64_t)c.N * c.E, off(la, 0), L1, mg(m.w1_2w), mg(m.w1_2b), c.N * c.E, c.HE, RM);
         J.j[J.n++] = mlg::bjob(at(p.w.df2), c.E, off(la, c.HE), L1, mg(m.wf_2w), mg(m.wf_2b), c.E, c.HE, RM);
         J.j[J.n++] = mlg::bjob(at(p.w.dv2), 1, off(la, 2 * c.HE + c.E), L1, mg(m.v2w), mg(m.v2b), 1, c.E, RM);
+    }
+    // every job loads live rows only (Skip): the agent's t-major rows by their 16-row tile's steps, the mixer's
+    // (b, t) rows by the episode's live transitions. Chunks stay contiguous: each sum keeps its order.
+    for (int q = 0; q < J.n; ++q) {
+        const float* bits = at(q < n_agent_jobs ? p.w.abits : p.w.mbits);
+        J.j[q] = mlg::bjob_row_bits(J.j[q], reinterpret_cast<const uint32_t*>(bits));
     }
     int64_t slab_part;
     *slab_floats = mlg::layout_bjobs(J, n_tasks, n_red, &slab_part);  // slab partials + per-block norm partials
@@ -1637,6 +1795,18 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     pj.B = c.B;
     pj.T = c.T;
     pj.msum = ws + p.w.msum;
+    pj.mlen = ws + p.w.mlen;
+    pj.l16 = ws + p.w.l16;
+    pj.flag = reinterpret_cast<unsigned*>(ws + p.w.flag);
+    pj.abits = reinterpret_cast<uint32_t*>(ws + p.w.abits);
+    pj.mbits = reinterpret_cast<uint32_t*>(ws + p.w.mbits);
+    pj.cmp_on = params;
+    pj.cmp_tg = tparams;
+    pj.n_cmp = p.n_agent + p.n_mixer;
+    pj.cmp_vec = ((uintptr_t)params % 16 == 0) && ((uintptr_t)tparams % 16 == 0);
+    pj.R = c.R;
+    pj.full = c.full;
+    const Skip sk{pj.mlen, pj.l16, pj.flag};
     pj.n_rows_in = 0;
     pj.rows_dst = rows_ws;
     if (bufs->host_rows) {
@@ -1644,7 +1814,8 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
         for (int b = 0; b < c.B; ++b) pj.rows_in[b] = bufs->host_rows[b];
     }
     {
-        const int64_t work = 2 * p.L.total + 3 * (int64_t)c.H * c.H + (c.mixer == 2 ? 2 * p.mp.total : 0) + pj.n_d2 + pj.n_dq;
+        const int64_t work = 2 * p.L.total + 3 * (int64_t)c.H * c.H + (c.mixer == 2 ? 2 * p.mp.total : 0) + pj.n_d2 +
+                             pj.n_dq + (pj.n_cmp + 3) / 4;
         const int blocks = 1 + (int)std::min<int64_t>((work + 1023) / 1024, 512);
         hipLaunchKernelGGL(prep_kernel, dim3(blocks), dim3(1024), 0, s, pj);
     }
@@ -1671,30 +1842,30 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     const int ntiles = (c.R + 15) / 16;
     HypOut hy{ws + p.w.hyp_on, ws + p.w.hyp_tg, ws + p.w.l1act, ws + p.w.srow, p.w.hyp_stride};
     hipLaunchKernelGGL((agent_in_kernel<H>), dim3(ntiles, c.T, 2), dim3(threads), 0, s, c, bt, p.L, ws + p.w.p_on,
-                       ws + p.w.p_tg, ws + p.w.in, ws + p.w.x, ws + p.w.gi_on, ws + p.w.gi_tg, ws + p.w.msum);
+                       ws + p.w.p_tg, ws + p.w.in, ws + p.w.x, ws + p.w.gi_on, ws + p.w.gi_tg, sk);
     if (split_mix) {
         const int nrec = 2 * ((c.R + 3) / 4), per = threads / 128;
         hipLaunchKernelGGL((rec4_mixpre_kernel<H>), dim3(nrec + (p.w.n_mix_tiles + per - 1) / per), dim3(threads), 0, s,
                            c, p.L, ws + p.w.p_on, ws + p.w.p_tg, ws + p.w.gi_on, ws + p.w.gi_tg, ws + p.w.hs,
-                           ws + p.w.hs_tg, ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, ws + p.w.msum, bt, Mon,
+                           ws + p.w.hs_tg, ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, sk, bt, Mon,
                            Mtg, p.mp, hy);
     } else
         hipLaunchKernelGGL((agent_rec4_kernel<H>), dim3(2 * ((c.R + 3) / 4)), dim3(threads), 0, s, c, p.L,
                            ws + p.w.p_on, ws + p.w.p_tg, ws + p.w.gi_on, ws + p.w.gi_tg, ws + p.w.hs, ws + p.w.hs_tg,
-                           ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, ws + p.w.msum);
+                           ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, sk);
     hipLaunchKernelGGL((agent_q_kernel<H>), dim3(ntiles, c.T, 2), dim3(64 * (c.Ap / 16)), 0, s, c, p.L, ws + p.w.p_on,
-                       ws + p.w.p_tg, ws + p.w.hs, ws + p.w.hs_tg, ws + p.w.mac, ws + p.w.tmac, ws + p.w.msum);
+                       ws + p.w.p_tg, ws + p.w.hs, ws + p.w.hs_tg, ws + p.w.mac, ws + p.w.tmac, sk);
     MixOut mo{ws + p.w.srow, ws + p.w.l1act, ws + p.w.d1, ws + p.w.da2, ws + p.w.df2, ws + p.w.dv2,
               ws + p.w.dq, ws + p.w.d2, ws + p.w.part};
     if (split_mix) {
         hipLaunchKernelGGL((mix_td2_kernel<64, 32>), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, ws + p.w.mac,
-                           ws + p.w.tmac, ws + p.w.msum, hy, mo);
+                           ws + p.w.tmac, ws + p.w.msum, hy, mo, sk);
     } else if (fast_mix)
         hipLaunchKernelGGL((mix_td_kernel<64, 32, true>), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, Mtg, p.mp,
-                           ws + p.w.mac, ws + p.w.tmac, ws + p.w.msum, mo);
+                           ws + p.w.mac, ws + p.w.tmac, ws + p.w.msum, mo, sk);
     else
         hipLaunchKernelGGL((mix_td_kernel<64, 32>), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, Mtg, p.mp,
-                           ws + p.w.mac, ws + p.w.tmac, ws + p.w.msum, mo);
+                           ws + p.w.mac, ws + p.w.tmac, ws + p.w.msum, mo, sk);
     // weight gradients: fc2 and the mixer's jobs (final after the mixer kernel, table view JA) run as extra
     // workgroups of the reverse-recurrence launch (H = 64, bwd4_wgrad_kernel); fc1 / W_ih / W_hh (view JB) after
     // agent_dx; one reduce over the whole table
@@ -1709,14 +1880,14 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
         const int nbwd = (c.R + 3) / 4;
         hipLaunchKernelGGL((bwd4_wgrad_kernel<H>), dim3((unsigned)(nbwd + (ta + 3) / 4)), dim3(256), 0, s, c, bt, p.L,
                            ws + p.w.p_on, ws + p.w.hs, ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, ws + p.w.dq,
-                           ws + p.w.dgi, ws + p.w.dgh, ws + p.w.msum, JA, ws + p.w.slab, nbwd);
+                           ws + p.w.dgi, ws + p.w.dgh, sk, JA, ws + p.w.slab, nbwd);
     } else {
         hipLaunchKernelGGL((agent_bwd4_kernel<H>), dim3((c.R + 3) / 4), dim3(threads), 0, s, c, bt, p.L, ws + p.w.p_on,
                            ws + p.w.hs, ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, ws + p.w.dq, ws + p.w.dgi,
-                           ws + p.w.dgh, ws + p.w.msum);
+                           ws + p.w.dgh, sk);
     }
     hipLaunchKernelGGL((agent_dx_kernel<H>), dim3(ntiles, c.T), dim3(threads), 0, s, c, ws + p.w.wihT, ws + p.w.x,
-                       ws + p.w.dgi, ws + p.w.da, ws + p.w.msum);
+                       ws + p.w.dgi, ws + p.w.da, sk);
     if (fused)
         hipLaunchKernelGGL(mlg::wgrad_block_kernel<16>, dim3((unsigned)((tb + 3) / 4)), dim3(256), 0, s, JB,
                            ws + p.w.slab);
@@ -1730,7 +1901,7 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     hipLaunchKernelGGL(finish_kernel, dim3((unsigned)((n_par + 1023) / 1024)), dim3(1024), 0, s, ws + p.w.part,
                        p.w.n_mix_tiles, ws + p.w.msum, bufs->params, bufs->grads, bufs->square_avg, n_par, cfg->lr,
                        cfg->optim_alpha, cfg->optim_eps, cfg->grad_norm_clip, c.N, bufs->stats, ws + p.w.nrm,
-                       n_red_blocks, bufs->target_sync, bufs->trained_steps);
+                       n_red_blocks, bufs->target_sync, bufs->trained_steps, sk, pj.flag, ntiles, c.full);
     return mlg::check_launch("qlearner_train");
 }
 

@@ -43,6 +43,9 @@ struct BJob {
     // deltas the backward kernels write as zeros): 0 off; 1 item-major rows, item = (row / rpi) % I, (b, t) = (item / T,
     // item % T); 2 t-major rows, t = row / R, b = ((row % R) / NA) % B. Row r is live iff t < mlen[b]. Groups of 8
     // consecutive rows share one (b, t) (rpi, NA and R multiples of 8).
+    // 3 (QMIX learner): liveness per row from a bitmap (`mlen` holds uint32 words, bit row % 32 of word row / 32; a
+    // 32-row step's liveness is one word, no division and no table walk in the kernel). Chunks stay contiguous, so
+    // every sum keeps its order. Dead rows are never loaded: neither their deltas nor their x rows need to exist.
     int skip, rpi, I, T, R, NA, B;
     const float* mlen;
 };
@@ -92,6 +95,12 @@ inline BJob bjob_items(BJob j, const float* mlen, int rpi, int I, int T) {
     return j;
 }
 // t-major rows: R rows per step, row r of a step belongs to episode (r / NA) % B
+// per-row liveness (BJob::skip 3): bit row % 32 of bits[row / 32], (rows + 31) / 32 words
+inline BJob bjob_row_bits(BJob j, const uint32_t* bits) {
+    j.skip = 3;
+    j.mlen = reinterpret_cast<const float*>(bits);
+    return j;
+}
 inline BJob bjob_steps(BJob j, const float* mlen, int R, int NA, int B) {
     j.skip = 2;
     j.mlen = mlen;
@@ -120,12 +129,13 @@ __device__ __forceinline__ int find_bjob(const BJobsT<MJ>& J, int task) {
 
 // the 8 rows rr + 8g .. rr + 8g + 7 of a lane: delta columns m0 .. m0 + 3 into a, x columns k0 .. k0 + 3 into b
 // (zeros for a dead group / rows past rend / columns past M, K)
-__device__ __forceinline__ void wgrad_load_step(const BJob& jb, int rr, int g, bool glive, int rend, int m0, int k0,
+// gm: bit t = row rr + 8g + t is live
+__device__ __forceinline__ void wgrad_load_step(const BJob& jb, int rr, int g, unsigned gm, int rend, int m0, int k0,
                                                 bool va, bool vb, float (&a)[8][4], float (&b)[8][4]) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
         const int row = rr + 8 * g + t;
-        const bool rv = glive && row < rend;
+        const bool rv = ((gm >> t) & 1u) && row < rend;
         const float* dr = jb.delta + (int64_t)row * jb.ldd + m0;
         const float* xr = jb.x + (int64_t)row * jb.ldx + k0;
         if (rv && va) {
@@ -217,7 +227,7 @@ __device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __r
     // jobs that skip dead rows deal their 32-row steps to the chunks round-robin (chunk ch takes steps ch, ch +
     // chunks, ...): the live rows (a prefix of every episode) then spread evenly over the job's waves instead of
     // leaving whole chunks with all the work; other jobs keep contiguous chunks
-    const bool strided = jb.skip != 0;
+    const bool strided = jb.skip == 1 || jb.skip == 2, rowmode = jb.skip == 3;
     const int s0 = strided ? ch : r0 >> 5, s1 = !act ? s0 : strided ? (jb.rows + 31) >> 5 : (r1 + 31) >> 5;
     const int ds = strided ? jb.chunks : 1, rend = strided ? jb.rows : r1;
     // rows with zero deltas add exactly zero: a lane's 8-row group of them loads nothing (zeros), a step with no live
@@ -226,13 +236,19 @@ __device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __r
     // does no integer division. With <= 64 episodes the episode lengths sit in a register (episode e in lane e).
     const int nst = act ? (s1 - s0 + ds - 1) / ds : 0;
     const int nep = jb.skip == 1 ? jb.I / jb.T : jb.B;
-    const bool mreg = jb.skip && nep <= 64;
+    const bool mreg = strided && nep <= 64;
     const float mlv = (mreg && lane < nep) ? jb.mlen[lane] : 0.f;
     int win = -1;
     uint64_t any = 0, mg = 0;  // steps of the window with a live group; this lane's group's live steps
+    unsigned m32 = 0;          // rowmode: the live rows of this lane's step of the window (bit k = row k of the step)
+    auto rows_live32 = [&](int row0) -> unsigned {  // the step's word of the bitmap, cut at the chunk's end
+        const unsigned m = reinterpret_cast<const uint32_t*>(jb.mlen)[row0 >> 5];
+        const int left = rend - row0;
+        return left >= 32 ? m : (left <= 0 ? 0u : m & ((1u << left) - 1u));
+    };
     auto group_live = [&](int row) -> bool {
         bool gv = row < rend;
-        if (jb.skip) {
+        if (strided) {
             int eb, et;
             if (jb.skip == 1) {
                 const int item = (row / jb.rpi) % jb.I;
@@ -254,11 +270,16 @@ __device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __r
                 const int li = (win << 6) + lane;
                 const int rl = (s0 + li * ds) << 5;
                 const bool inr = li < nst;
-                // group_live first: its lane shuffle runs with every lane active
-                const uint64_t b0 = __ballot(group_live(rl) && inr), b1 = __ballot(group_live(rl + 8) && inr),
-                               b2 = __ballot(group_live(rl + 16) && inr), b3 = __ballot(group_live(rl + 24) && inr);
-                any = b0 | b1 | b2 | b3;
-                mg = g == 0 ? b0 : g == 1 ? b1 : g == 2 ? b2 : b3;
+                if (rowmode) {
+                    m32 = inr ? rows_live32(rl) : 0u;
+                    any = __ballot(m32 != 0u);
+                } else {
+                    // group_live first: its lane shuffle runs with every lane active
+                    const uint64_t b0 = __ballot(group_live(rl) && inr), b1 = __ballot(group_live(rl + 8) && inr),
+                                   b2 = __ballot(group_live(rl + 16) && inr), b3 = __ballot(group_live(rl + 24) && inr);
+                    any = b0 | b1 | b2 | b3;
+                    mg = g == 0 ? b0 : g == 1 ? b1 : g == 2 ? b2 : b3;
+                }
             }
             const uint64_t rem = any & (~0ull << (i & 63));
             if (rem) return (win << 6) + __builtin_ctzll(rem);
@@ -266,9 +287,14 @@ __device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __r
         }
         return nst;
     };
-    auto live_of = [&](int i) -> bool { return (mg >> (i & 63)) & 1; };  // i in the current window
+    // the live rows of step i (i in the current window; wave-uniform call): all 32 rows of the step in rowmode, else
+    // this lane's 8-row group as a whole
+    auto step_mask = [&](int i) -> unsigned {
+        if (rowmode) return (unsigned)__shfl((int)m32, i & 63);
+        return ((mg >> (i & 63)) & 1) ? 0xFFu << (8 * g) : 0u;
+    };
     int i = next_live(0);
-    bool gl = i < nst && live_of(i);
+    unsigned gl = i < nst ? step_mask(i) : 0u;
     if constexpr (GLDS) {
         // one step ahead through LDS: the next live step's 16 row loads go global -> LDS (global_load_lds, 16 bytes
         // per lane, this wave's 16 KB of `lbuf`) while this step's products run from VGPRs (a register copy of the
@@ -277,12 +303,14 @@ __device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __r
         // rows / columns).
         if (__all(va && vb)) {
             floatx4(*stg)[64] = lbuf[w];
-            auto issue = [&](int ii, bool gv) {
+            auto issue = [&](int ii, unsigned sm) {
                 const int rr = (s0 + ii * ds) << 5;
+                // dead rows load a row that is there: row 0, or in rowmode the step's first live row
+                const int64_t safe = (rowmode && sm) ? rr + __builtin_ctz(sm) : 0;
 #pragma unroll
                 for (int t = 0; t < 8; ++t) {
                     const int row = rr + 8 * g + t;
-                    const int64_t rs = (gv && row < rend) ? row : 0;
+                    const int64_t rs = (((sm >> (8 * g + t)) & 1u) && row < rend) ? row : safe;
                     __builtin_amdgcn_global_load_lds((const void*)(jb.delta + rs * jb.ldd + m0),
                                                      (__attribute__((address_space(3))) void*)&stg[t][0], 16, 0, 0);
                     __builtin_amdgcn_global_load_lds((const void*)(jb.x + rs * jb.ldx + k0),
@@ -292,13 +320,13 @@ __device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __r
             if (i < nst) issue(i, gl);
             while (i < nst) {
                 const int in = next_live(i + 1);
-                const bool gn = in < nst && live_of(in);
+                const unsigned gn = in < nst ? step_mask(in) : 0u;
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 const int rr = (s0 + i * ds) << 5;
                 float a[8][4], b[8][4];
 #pragma unroll
                 for (int t = 0; t < 8; ++t) {
-                    const bool rv = gl && rr + 8 * g + t < rend;
+                    const bool rv = ((gl >> (8 * g + t)) & 1u) && rr + 8 * g + t < rend;
                     const floatx4 va4 = stg[t][lane], vb4 = stg[8 + t][lane];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -316,10 +344,10 @@ __device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __r
     }
     while (i < nst) {
         float a[8][4], b[8][4];
-        wgrad_load_step(jb, (s0 + i * ds) << 5, g, gl, rend, m0, k0, va, vb, a, b);
+        wgrad_load_step(jb, (s0 + i * ds) << 5, g, (gl >> (8 * g)) & 0xFFu, rend, m0, k0, va, vb, a, b);
         wgrad_mfma_step(a, b, acc, bsum);
         i = next_live(i + 1);
-        gl = i < nst && live_of(i);
+        gl = i < nst ? step_mask(i) : 0u;
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {

@@ -1,6 +1,7 @@
 """QLearner.train / REFILLearner.train (MODE=refil) microbenchmark on the bench's shapes: 5v5 medium_1h_4t (refil:
 refil_8, 3-8 agents) rollouts (ENVS envs, episode_limit 100) fill a device replay ring, then REPS train() calls on
 batch_size 32 samples read in place (the bench's path).
+EP_STEP=N advances episode_num by N per call (0: the target network is never updated).
 Prints mean ms per train() (HIP events on the learner's stream) and the loss of the last call, so variant libraries
 (MLG_LIB=...) can be A/B-compared; run under rocprofv3 --kernel-trace --stats for the per-kernel split."""
 import json
@@ -23,6 +24,9 @@ overrides = [f"batch_size_run={ENVS}", "runner=parallel", "buffer_cpu_only=False
              "learner_log_interval=1000000000", "log_interval=1000000000", "runner_log_interval=1000000000",
              "test_interval=1000000000000", "t_max=1000000000000", "show_exp_parameters=False"]
 MODE = os.environ.get("MODE", "qmix")
+# episodes gathered between two train() calls: the episode_num of call r is (r + 1) * EP_STEP, so a value >=
+# target_update_interval (bench.py's runs: batch_size_run = 4096 >= 200) has every call end with a target update
+EP_STEP = int(os.environ.get("EP_STEP", "0"))
 if MODE == "refil":
     overrides = [o.replace("medium_1h_4t", "refil_8") for o in overrides]
     cfg = build_config("refil", "ma_entity", overrides=overrides, device_index=0)
@@ -44,7 +48,7 @@ torch.cuda.synchronize()
 ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(REPS)]
 for r in range(REPS):
     ev[r][0].record()
-    lrn.train(samples[r], 10 ** 6, 0)
+    lrn.train(samples[r], 10 ** 6, (r + 1) * EP_STEP)
     ev[r][1].record()
 torch.cuda.synchronize()
 ms = [a.elapsed_time(b) for a, b in ev]
