@@ -23,7 +23,9 @@
  *   mlg_select_actions EpsilonGreedyActionSelector.select src/marl/components/action_selectors.py:44-62
  *   mlg_pack_agent     (layout step feeding the above; no reference counterpart)
  *   mlg_qmix_forward   QMixer.forward               src/marl/modules/mixers/qmix.py:41-59
- *   mlg_refil_*        REFIL (config 5): see the REFIL section below
+ *   mlg_agent_backward / mlg_qmix_backward  loss.backward() through the two above, one step / one call at a time
+ *                      (src/marl/learners/q_learner.py:47-52,103 with any loss)
+ *   mlg_refil_*      REFIL (config 5): see the REFIL section below
  *   mlg_qlearner_*     QLearner.train               src/marl/learners/q_learner.py:34-131
  *                      + clip_grad_norm_ + RMSprop.step (q_learner.py:104-105, learner.py:25-31)
  */
@@ -170,6 +172,32 @@ typedef struct {
 } MlgQMixParams;
 int mlg_qmix_forward(const MlgQMixParams *p, const float *agent_qs /*[R][N]*/, const float *states /*[R][S]*/,
                      float *q_tot /*[R]*/, int32_t R, void *stream);
+
+/* ---- Backward of one agent step / one mixer call (autograd of torch.ops.maleague.drqn_forward / qmix_forward) ----
+ * For learners written the reference's way (unroll mac.forward over t, mix, build any loss, loss.backward():
+ * src/marl/learners/q_learner.py:47-52,103): PyTorch chains the steps, these entry points differentiate one step.
+ * Each recomputes its step's activations from the step's inputs (nothing is kept from the forward), writes row deltas
+ * to `workspace` (mlg_*_backward_workspace_floats(dims, R) floats, 16-byte aligned, any contents) and reduces the
+ * weight gradients in a fixed order: results are deterministic. dparams is overwritten, not accumulated; R == 0
+ * zeroes it. The *_workspace_floats calls are host only and return -1 (message in mlg_last_error()) on bad dims.
+ *
+ * mlg_agent_backward differentiates DRQNAgentNetwork.forward (src/marl/modules/agents/drqn_agent.py:29-35; torch
+ * GRUCell, gates r, z, n). `packed` must be the mlg_pack_agent() block of `p`. h_in NULL = zeros (as the forward),
+ * gq [R][A] / gh_out [R][H] NULL = zero upstream gradient, d_inputs [R][d_in] / d_h_in [R][H] NULL = not wanted.
+ * dparams: fc1.weight, fc1.bias, gru.weight_ih, gru.weight_hh, gru.bias_ih, gru.bias_hh, fc2.weight, fc2.bias
+ * (named_parameters() order, as the learner's flat vectors below). packed, h_in, gh_out, d_h_in 16-byte aligned. */
+int64_t mlg_agent_backward_workspace_floats(const MlgAgentDims *d, int32_t R);
+int mlg_agent_backward(const MlgAgentDims *d, const MlgAgentParams *p, const float *packed, const float *inputs,
+                       const float *h_in, const float *gq, const float *gh_out, float *d_inputs, float *d_h_in,
+                       float *dparams, float *workspace, int32_t R, void *stream);
+/* mlg_qmix_backward differentiates QMixer.forward (src/marl/modules/mixers/qmix.py:41-59) with respect to agent_qs
+ * and every hypernet weight and bias (not the states): g_qtot [R] -> d_agent_qs [R][N]; abs backward is sign with
+ * sign(0) = 0, ELU backward 1 for pre > 0 else exp(pre). dparams in named_parameters() order: two layers as the
+ * learner's mixer vector below; one layer hyper_w_1.{weight [N*E][S], bias}, hyper_w_final.{weight [E][S], bias},
+ * hyper_b_1.{weight, bias}, V.{0.weight, 0.bias, 2.weight, 2.bias}. */
+int64_t mlg_qmix_backward_workspace_floats(const MlgQMixParams *p, int32_t R);
+int mlg_qmix_backward(const MlgQMixParams *p, const float *agent_qs, const float *states, const float *g_qtot,
+                      float *d_agent_qs, float *dparams, float *workspace, int32_t R, void *stream);
 
 /* ---- QLearner.train (q_learner.py:34-131) as one fused device pipeline --------------------------
  * Flat parameter vectors follow the nn.Module named_parameters() order:

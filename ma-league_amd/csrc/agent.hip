@@ -91,50 +91,54 @@ __global__ void select_actions_kernel(const float* __restrict__ q, const int32_t
     if (is_greedy) is_greedy[r] = greedy;
 }
 
-// ---- QMixer forward (qmix.py:41-59), one thread per row; used by QMixer.forward outside training ----
-struct QMixP {
-    MlgQMixParams p;
-};
-
+// ---- QMixer forward (qmix.py:41-59); used by QMixer.forward outside the fused learner ----
 __device__ float lin_row(const float* w, const float* b, const float* x, int K, int o) {
     float acc = b[o];
     for (int k = 0; k < K; ++k) acc = fmaf(w[(int64_t)o * K + k], x[k], acc);
     return acc;
 }
 
-__global__ void qmix_forward_kernel(MlgQMixParams p, const float* __restrict__ qs, const float* __restrict__ states,
-                                    float* __restrict__ out, int R) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= R) return;
-    const int N = p.n_agents, S = p.state_dim, E = p.embed_dim, HE = p.hypernet_embed;
-    const float* s = states + (int64_t)r * S;
+// One wave per row, lanes over a layer's output features, the row's vectors in LDS (floats: S + 2 HE + 3 E). Every
+// sum runs over its terms in index order whatever the lane, the last one (over e) in lane 0.
+__global__ void __launch_bounds__(64) qmix_forward_kernel(MlgQMixParams p, const float* __restrict__ qs,
+                                                         const float* __restrict__ states, float* __restrict__ out,
+                                                         int R) {
+    extern __shared__ float lds[];
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const int N = p.n_agents, S = p.state_dim, E = p.embed_dim;
+    const bool two = p.hypernet_layers == 2;
+    const int HE = two ? p.hypernet_embed : 0;
+    float* s = lds;       // [S] the row's state
+    float* h1 = s + S;    // [HE] relu(hyper_w_1.0 s)
+    float* hf = h1 + HE;  // [HE] relu(hyper_w_final.0 s)
+    float* hid = hf + HE; // [E] elu(q . |W1(s)| + b1(s))
+    float* wf = hid + E;  // [E] |hyper_w_final(s)|
+    float* hv = wf + E;   // [E] relu(V.0 s)
     const float* q = qs + (int64_t)r * N;
-    float hid[64];
-    float hb[256];
-    // hidden = elu(q . |W1(s)| + b1(s))
-    if (p.hypernet_layers == 2)
-        for (int k = 0; k < HE; ++k) hb[k] = fmaxf(lin_row(p.hw1_0w, p.hw1_0b, s, S, k), 0.f);
-    for (int e = 0; e < E; ++e) {
+    for (int k = lane; k < S; k += 64) s[k] = states[(int64_t)r * S + k];
+    __syncthreads();
+    for (int k = lane; k < HE; k += 64) {
+        h1[k] = fmaxf(lin_row(p.hw1_0w, p.hw1_0b, s, S, k), 0.f);
+        hf[k] = fmaxf(lin_row(p.hwf_0w, p.hwf_0b, s, S, k), 0.f);
+    }
+    for (int e = lane; e < E; e += 64) hv[e] = fmaxf(lin_row(p.v0_w, p.v0_b, s, S, e), 0.f);
+    __syncthreads();
+    for (int e = lane; e < E; e += 64) {
         float acc = 0.f;
         for (int n = 0; n < N; ++n) {
             const int o = n * E + e;
-            const float w = p.hypernet_layers == 2 ? lin_row(p.hw1_2w, p.hw1_2b, hb, HE, o) : lin_row(p.hw1_0w, p.hw1_0b, s, S, o);
+            const float w = two ? lin_row(p.hw1_2w, p.hw1_2b, h1, HE, o) : lin_row(p.hw1_0w, p.hw1_0b, s, S, o);
             acc = fmaf(q[n], fabsf(w), acc);
         }
         const float pre = acc + lin_row(p.hb1_w, p.hb1_b, s, S, e);
         hid[e] = pre > 0.f ? pre : expm1f(pre);
+        wf[e] = fabsf(two ? lin_row(p.hwf_2w, p.hwf_2b, hf, HE, e) : lin_row(p.hwf_0w, p.hwf_0b, s, S, e));
     }
-    if (p.hypernet_layers == 2)
-        for (int k = 0; k < HE; ++k) hb[k] = fmaxf(lin_row(p.hwf_0w, p.hwf_0b, s, S, k), 0.f);
+    __syncthreads();
+    if (lane != 0) return;
     float y = 0.f;
-    for (int e = 0; e < E; ++e) {
-        const float w = p.hypernet_layers == 2 ? lin_row(p.hwf_2w, p.hwf_2b, hb, HE, e) : lin_row(p.hwf_0w, p.hwf_0b, s, S, e);
-        y = fmaf(hid[e], fabsf(w), y);
-    }
-    float hv[64];
-    for (int e = 0; e < E; ++e) hv[e] = fmaxf(lin_row(p.v0_w, p.v0_b, s, S, e), 0.f);
-    const float v = lin_row(p.v2_w, p.v2_b, hv, E, 0);
-    out[r] = y + v;
+    for (int e = 0; e < E; ++e) y = fmaf(hid[e], wf[e], y);
+    out[r] = y + lin_row(p.v2_w, p.v2_b, hv, E, 0);
 }
 
 }  // namespace
@@ -215,11 +219,14 @@ extern "C" int mlg_select_actions(const float* q, const int32_t* avail, int32_t 
 
 extern "C" int mlg_qmix_forward(const MlgQMixParams* p, const float* agent_qs, const float* states, float* q_tot,
                                 int32_t R, void* stream) {
-    MLG_REQUIRE(p && agent_qs && states && q_tot, "qmix_forward: null pointer");
+    MLG_REQUIRE(p && agent_qs && states && q_tot && R >= 0, "qmix_forward: bad arguments");
     MLG_REQUIRE(p->embed_dim <= 64 && p->hypernet_embed <= 256, "qmix_forward: embed dims too large");
     MLG_REQUIRE(p->hypernet_layers == 1 || p->hypernet_layers == 2, "qmix_forward: hypernet_layers must be 1 or 2");
     if (R == 0) return 0;
-    hipLaunchKernelGGL(qmix_forward_kernel, dim3((R + 127) / 128), dim3(128), 0, (hipStream_t)stream, *p, agent_qs, states,
+    const int HE = p->hypernet_layers == 2 ? p->hypernet_embed : 0;
+    const size_t lds = sizeof(float) * ((size_t)p->state_dim + 2 * (size_t)HE + 3 * (size_t)p->embed_dim);
+    MLG_REQUIRE(p->state_dim >= 1 && lds <= 48 * 1024, "qmix_forward: state_dim too large for one row in LDS");
+    hipLaunchKernelGGL(qmix_forward_kernel, dim3((unsigned)R), dim3(64), lds, (hipStream_t)stream, *p, agent_qs, states,
                        q_tot, R);
     return mlg::check_launch("qmix_forward_kernel");
 }

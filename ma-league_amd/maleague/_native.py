@@ -123,6 +123,10 @@ SIGNATURES = {
     "mlg_mac_forward": (ctypes.c_int, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "mlg_select_actions": (ctypes.c_int, [_P, _P, _I, _I, _I, _P, _P, _I, ctypes.c_float, _P, _P, _P]),
     "mlg_qmix_forward": (ctypes.c_int, [_P, _P, _P, _P, _I, _P]),
+    "mlg_agent_backward_workspace_floats": (ctypes.c_int64, [_P, _I]),
+    "mlg_agent_backward": (ctypes.c_int, [_P] * 11 + [_I, _P]),
+    "mlg_qmix_backward_workspace_floats": (ctypes.c_int64, [_P, _I]),
+    "mlg_qmix_backward": (ctypes.c_int, [_P] * 7 + [_I, _P]),
     "mlg_qlearner_param_counts": (ctypes.c_int64, [_P, _P, _P]),
     "mlg_qlearner_workspace_floats": (ctypes.c_int64, [_P]),
     "mlg_qlearner_inline_rows": (ctypes.c_int, []),

@@ -51,6 +51,11 @@ class BasicMAC(MultiAgentController):
         if self.hidden_states is None:
             raise HiddenStateNotInitialized()
         B, N, H = ep_batch.batch_size, self.n_agents, self.args.rnn_hidden_dim
+        if self._wants_grad():
+            # differentiable path: hidden_states carries the graph across steps
+            q, h = self.agent(self._build_inputs(ep_batch, t), self.hidden_states)
+            self.hidden_states = h
+            return q.view(B, N, self.n_actions)
         mb, keep = mlg_batch(ep_batch, required=("obs", "actions_onehot"))
         h_in = self.hidden_states.reshape(B * N, H).float().contiguous()
         q = torch.empty(B, N, self.n_actions, device=h_in.device)
@@ -61,6 +66,29 @@ class BasicMAC(MultiAgentController):
         del keep
         self.hidden_states = h_out
         return q
+
+    def enable_autograd(self, flag: bool = True):
+        """Opt in to a differentiable forward (DRQNAgentNetwork.enable_autograd): in grad mode forward(ep_batch, t)
+        then builds the agent inputs with torch ops and calls the agent module, so a loss over the unrolled
+        outputs backpropagates through time. Under no_grad, or when not enabled, forward stays the fused
+        mlg_mac_forward call."""
+        self.agent.enable_autograd(flag)
+        return self
+
+    def _wants_grad(self) -> bool:
+        wants = getattr(self.agent, "wants_grad", None)
+        return wants is not None and wants(self.hidden_states)
+
+    def _build_inputs(self, batch, t):
+        """[obs_t | onehot(a_{t-1}) | eye(N)] as [B * N, d_in] (basic_controller.py:80-92)."""
+        B, N = batch.batch_size, self.n_agents
+        inputs = [batch["obs"][:, t]]
+        if self.args.obs_last_action:
+            oh = batch["actions_onehot"]
+            inputs.append(torch.zeros_like(oh[:, t]) if t == 0 else oh[:, t - 1])
+        if self.args.obs_agent_id:
+            inputs.append(torch.eye(N, device=inputs[0].device).unsqueeze(0).expand(B, -1, -1))
+        return torch.cat([x.reshape(B * N, -1).float() for x in inputs], dim=1)
 
     def update_trained_steps(self, update):
         self.agent.add_trained_steps(update)

@@ -73,6 +73,7 @@ class DRQNAgentNetwork(AgentNetwork):
         self._packed_key = None
         self._dirty = 0
         self._h0 = None
+        self._autograd = bool(getattr(args, "native_autograd", False))
 
     # ---- kernel plumbing --------------------------------------------------------------------
     def dims(self) -> _native.MlgAgentDims:
@@ -121,9 +122,31 @@ class DRQNAgentNetwork(AgentNetwork):
             self._h0 = w.new_zeros(1, self.args.rnn_hidden_dim)
         return self._h0
 
+    def enable_autograd(self, flag: bool = True):
+        """Opt in to a differentiable forward (also from ``args.native_autograd``): in grad mode, with a parameter
+        or an input requiring grad, forward goes through ``maleague::drqn_forward`` with the live parameters and
+        ``loss.backward()`` reaches them (HIP backward, ``mlg_agent_backward``). Off by default: forward then
+        returns plain tensors as before. Values are bit-identical either way."""
+        self._autograd = bool(flag)
+        return self
+
+    def _live_params(self):
+        """The parameters in named_parameters() order (AGENT_ORDER of learners/q_learner.py)."""
+        return [self.fc1.weight, self.fc1.bias, self.gru.weight_ih, self.gru.weight_hh, self.gru.bias_ih,
+                self.gru.bias_hh, self.fc2.weight, self.fc2.bias]
+
+    def wants_grad(self, *tensors) -> bool:
+        """The routing condition of the differentiable path."""
+        return (self._autograd and torch.is_grad_enabled()
+                and (any(p.requires_grad for p in self._live_params())
+                     or any(t is not None and t.requires_grad for t in tensors)))
+
     def forward(self, inputs, hidden_state):
         H = self.args.rnn_hidden_dim
         x = inputs.float().contiguous()
         h_in = hidden_state.reshape(-1, H).float().contiguous()
         from ...ops import struct_fields
+        if self.wants_grad(inputs, hidden_state):
+            params = [p.float().contiguous() for p in self._live_params()]
+            return torch.ops.maleague.drqn_forward(params, self.packed(), x, h_in, struct_fields(self.dims()))
         return torch.ops.maleague.agent_forward(self.packed(), x, h_in, struct_fields(self.dims()))

@@ -15,6 +15,14 @@ raise on host tensors like every product path.
 | ``maleague::refil_attention``        | ``mlg_refil_attention``   | EntityAttentionLayer.forward (attention.py:24-79)   |
 | ``maleague::refil_mixer_forward``    | ``mlg_refil_mixer_forward`` | FlexQMixer.forward (flex_qmix.py:73-117)          |
 | ``maleague::refil_agent_step``       | ``mlg_refil_agent_forward`` | EntityAttentionRNNAgent.forward, one step (entity_rnn_agent.py:32-65) |
+| ``maleague::drqn_forward``           | ``mlg_agent_forward``     | DRQNAgentNetwork.forward with the live parameters as inputs (differentiable) |
+| ``maleague::drqn_backward``          | ``mlg_agent_backward``    | its backward: one cell step (loss.backward(), q_learner.py:103) |
+| ``maleague::qmix_backward``          | ``mlg_qmix_backward``     | backward of ``qmix_forward`` w.r.t. agent_qs and the parameters |
+
+``drqn_forward`` and ``qmix_forward`` carry autograd formulas (``torch.library.register_autograd``) that call the
+two backward ops; the backward ops have none, so double backward raises an error naming them. Gradients for
+``packed``, ``dims`` and the mixer's ``states`` are ``None`` (states that require grad are refused). The modules
+route through the differentiable ops only after ``enable_autograd()``.
 
 The rollout and learner entry points (``mlg_rollout*``, ``mlg_qlearner_train``, ``mlg_refil_train``) take the
 replay ring, env state and optimizer state as in-place structs and stay direct calls of the stepper / learner
@@ -168,5 +176,151 @@ def _refil_agent_step_fake(packed, entities, obs_mask, entity_mask, h_in, dims):
     return entities.new_empty(R, dims[0], dims[3]), entities.new_empty(R, dims[0], dims[7])
 
 
+# ---- autograd: the agent step and the mixer call as differentiable ops ---------------------------------------
+def _aligned(t: Optional[Tensor]) -> Optional[Tensor]:
+    """Contiguous, on a 16-byte boundary (the kernels read rows of H floats as 16-byte vectors)."""
+    if t is None:
+        return None
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _workspace(name: str, like: Tensor, *args) -> Tensor:
+    n = getattr(_native.load(require_gpu=True), name)(*args)
+    if n < 0:
+        raise _native.NativeError(f"{name} failed: {_native.load().mlg_last_error().decode()}")
+    return like.new_empty(max(int(n), 4))
+
+
+def _agent_numels(dims: List[int]) -> List[int]:
+    """Sizes of the 8 agent parameters in named_parameters() order (AGENT_ORDER of learners/q_learner.py)."""
+    A, H, d_in = dims[1], dims[3], dims[4]
+    return [H * d_in, H, 3 * H * H, 3 * H * H, 3 * H, 3 * H, A * H, A]
+
+
+@custom_op("maleague::drqn_forward", mutates_args=())
+def drqn_forward(params: List[Tensor], packed: Tensor, inputs: Tensor, h_in: Tensor, dims: List[int]
+                 ) -> Tuple[Tensor, Tensor]:
+    """``agent_forward`` with the 8 live parameters (AGENT_ORDER: fc1.weight, fc1.bias, gru.weight_ih,
+    gru.weight_hh, gru.bias_ih, gru.bias_hh, fc2.weight, fc2.bias) as inputs autograd can reach. The kernel reads
+    ``packed``, which the caller guarantees is the pack of ``params``: values are bit-identical to ``agent_forward``."""
+    d = _native.MlgAgentDims(*[int(v) for v in dims])
+    R = inputs.shape[0]
+    q = inputs.new_empty(R, d.n_actions)
+    h_out = inputs.new_empty(R, d.hidden)
+    _native.call("mlg_agent_forward", _native.byref(d), _native.ptr(packed), _native.ptr(inputs), _native.ptr(h_in),
+                 _native.ptr(q), _native.ptr(h_out), R, _stream(inputs))
+    return q, h_out
+
+
+@register_fake("maleague::drqn_forward")
+def _drqn_forward_fake(params, packed, inputs, h_in, dims):
+    R = inputs.shape[0]
+    return inputs.new_empty(R, dims[1]), inputs.new_empty(R, dims[3])
+
+
+@custom_op("maleague::drqn_backward", mutates_args=())
+def drqn_backward(params: List[Tensor], packed: Tensor, inputs: Tensor, h_in: Tensor, gq: Optional[Tensor],
+                  gh_out: Optional[Tensor], dims: List[int]) -> Tuple[Tensor, Tensor, Tensor]:
+    """Backward of one ``drqn_forward`` step (``mlg_agent_backward``): gq [R, A] / gh_out [R, H] (None = zero) ->
+    (d_inputs [R, d_in], d_h_in [R, H], dflat: the 8 parameter gradients, flat, in AGENT_ORDER)."""
+    d = _native.MlgAgentDims(*[int(v) for v in dims])
+    R = inputs.shape[0]
+    keep = [p.contiguous() for p in params]
+    fc1w, fc1b, wih, whh, bih, bhh, fc2w, fc2b = [_native.ptr(p) for p in keep]
+    cparams = _native.MlgAgentParams(fc1w, fc1b, wih, bih, whh, bhh, fc2w, fc2b)
+    inputs, h_in = inputs.contiguous(), _aligned(h_in)
+    gq = None if gq is None else gq.contiguous()
+    gh_out = _aligned(gh_out)
+    d_inputs = torch.empty_like(inputs)
+    d_h_in = inputs.new_empty(R, d.hidden)
+    dflat = inputs.new_empty(sum(_agent_numels(dims)))
+    ws = _workspace("mlg_agent_backward_workspace_floats", inputs, _native.byref(d), R)
+    _native.call("mlg_agent_backward", _native.byref(d), _native.byref(cparams), _native.ptr(packed),
+                 _native.ptr(inputs), _native.ptr(h_in), _native.ptr(gq), _native.ptr(gh_out), _native.ptr(d_inputs),
+                 _native.ptr(d_h_in), _native.ptr(dflat), _native.ptr(ws), R, _stream(inputs))
+    return d_inputs, d_h_in, dflat
+
+
+@register_fake("maleague::drqn_backward")
+def _drqn_backward_fake(params, packed, inputs, h_in, gq, gh_out, dims):
+    R = inputs.shape[0]
+    return torch.empty_like(inputs), inputs.new_empty(R, dims[3]), inputs.new_empty(sum(_agent_numels(dims)))
+
+
+def _split(dflat: Tensor, like: List[Tensor], needed) -> List[Optional[Tensor]]:
+    """dflat as per-parameter views (zero-size entries -- absent layers -- and unneeded ones get None)."""
+    out, off = [], 0
+    for t, need in zip(like, needed):
+        n = t.numel()
+        out.append(dflat[off:off + n].view(t.shape) if need and n else None)
+        off += n
+    return out
+
+
+def _drqn_setup(ctx, inputs, output):
+    params, packed, x, h_in, dims = inputs
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(*params, packed, x, h_in)
+    ctx.dims = [int(v) for v in dims]
+
+
+def _drqn_backward(ctx, gq, gh_out):
+    *params, packed, x, h_in = ctx.saved_tensors
+    if gq is None and gh_out is None:
+        return [None] * len(params), None, None, None, None
+    d_inputs, d_h_in, dflat = torch.ops.maleague.drqn_backward(list(params), packed, x, h_in, gq, gh_out, ctx.dims)
+    need = ctx.needs_input_grad
+    return (_split(dflat, list(params), need[0]), None, d_inputs if need[2] else None,
+            d_h_in if need[3] else None, None)
+
+
+torch.library.register_autograd("maleague::drqn_forward", _drqn_backward, setup_context=_drqn_setup)
+
+
+@custom_op("maleague::qmix_backward", mutates_args=())
+def qmix_backward(params: List[Tensor], agent_qs: Tensor, states: Tensor, g_qtot: Tensor, dims: List[int]
+                  ) -> Tuple[Tensor, Tensor]:
+    """Backward of ``qmix_forward`` (``mlg_qmix_backward``): g_qtot [R] -> (d_agent_qs [R, N], dflat: the gradients of
+    the non-empty ``params`` in their order, flat). States get no gradient."""
+    ps = [t.contiguous() for t in params]
+    p = _native.MlgQMixParams(*[_opt(t) for t in ps], *[int(v) for v in dims])
+    R = agent_qs.shape[0]
+    agent_qs, states, g_qtot = agent_qs.contiguous(), states.contiguous(), g_qtot.contiguous()
+    d_qs = torch.empty_like(agent_qs)
+    dflat = agent_qs.new_empty(sum(t.numel() for t in ps))
+    ws = _workspace("mlg_qmix_backward_workspace_floats", agent_qs, _native.byref(p), R)
+    _native.call("mlg_qmix_backward", _native.byref(p), _native.ptr(agent_qs), _native.ptr(states),
+                 _native.ptr(g_qtot), _native.ptr(d_qs), _native.ptr(dflat), _native.ptr(ws), R, _stream(agent_qs))
+    return d_qs, dflat
+
+
+@register_fake("maleague::qmix_backward")
+def _qmix_backward_fake(params, agent_qs, states, g_qtot, dims):
+    return torch.empty_like(agent_qs), agent_qs.new_empty(sum(t.numel() for t in params))
+
+
+STATE_GRAD_ERROR = ("maleague::qmix_forward: gradients with respect to the states are not implemented "
+                    "(pass states that do not require grad)")
+
+
+def _qmix_setup(ctx, inputs, output):
+    params, agent_qs, states, dims = inputs
+    if states.requires_grad:
+        raise _native.NativeError(STATE_GRAD_ERROR)
+    ctx.save_for_backward(*params, agent_qs, states)
+    ctx.dims = [int(v) for v in dims]
+
+
+def _qmix_backward(ctx, g_qtot):
+    *params, agent_qs, states = ctx.saved_tensors
+    d_qs, dflat = torch.ops.maleague.qmix_backward(list(params), agent_qs, states, g_qtot, ctx.dims)
+    need = ctx.needs_input_grad
+    return _split(dflat, list(params), need[0]), d_qs if need[1] else None, None, None
+
+
+torch.library.register_autograd("maleague::qmix_forward", _qmix_backward, setup_context=_qmix_setup)
+
+
 OPS = ("agent_forward", "select_actions", "qmix_forward", "refil_attention", "refil_mixer_forward",
-       "refil_agent_step")
+       "refil_agent_step", "drqn_forward", "drqn_backward", "qmix_backward")
