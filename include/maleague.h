@@ -206,7 +206,19 @@ int mlg_qmix_backward(const MlgQMixParams *p, const float *agent_qs, const float
  *   qmix (hypernet_layers 2): hyper_w_1.{0.weight [HE][S], 0.bias, 2.weight [N*E][HE], 2.bias},
  *          hyper_w_final.{0.weight [HE][S], 0.bias, 2.weight [E][HE], 2.bias}, hyper_b_1.{weight [E][S], bias},
  *          V.{0.weight [E][S], 0.bias, 2.weight [1][E], 2.bias}
- * params/grads/square_avg = [agent | mixer]; target_params likewise (the target networks). */
+ *   qmix (hypernet_layers 1, the reference QMixer's fallback, qmix.py:17): hyper_w_1.{weight [N*E][S], bias},
+ *          hyper_w_final.{weight [E][S], bias}, hyper_b_1.{weight [E][S], bias},
+ *          V.{0.weight [E][S], 0.bias, 2.weight [1][E], 2.bias} (the order mlg_qmix_backward documents)
+ *   vdn, none (IQL): no mixer parameters, n_mixer = 0: the vectors hold the agent alone
+ * params/grads/square_avg = [agent | mixer]; target_params likewise (the target networks).
+ * Supported: mixer 0 / 1 / 2; for qmix hypernet_layers 1 or 2, mixing_embed_dim E in {16, 32, 64} and, with two
+ * layers, hypernet_embed HE in {32, 64, 128} (one layer ignores HE); N <= 32; H in {32, 64, 128}. Anything else
+ * is refused (-1 / nonzero, mlg_last_error() names the key and the supported values).
+ * IQL (mixer 0, q_learner.py:55-98 without the mixing): td[b,t,n] = Q_chosen[b,t,n] - (r[b,t] + gamma (1 -
+ * term[b,t]) target[b,t+1,n]) with the per-agent double-Q / masked-max target of VDN/QMIX; the mask is expanded
+ * over the agents, mask_elems = N sum(mask): loss = sum(mask td^2) / mask_elems, td_error_abs = sum|mask td| /
+ * mask_elems, q_taken_mean and target_mean divide by mask_elems * N (the reference's double division, kept).
+ * stats[5] = mask_elems, stats[6] = count_nonzero of the expanded mask; trained_steps grows by the latter. */
 typedef struct {
     int32_t B, T, N, A, d_obs, H, S, E, HE, hypernet_layers;
     int32_t mixer; /* 0 none (IQL), 1 vdn, 2 qmix */

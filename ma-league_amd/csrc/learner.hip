@@ -17,6 +17,22 @@
 // rows past the episode's last unmasked transition, and the whole target pass while the target parameters are a
 // bit copy of the online ones. MLG_LEARNER_FULL=1 (read per call) runs every row to max_t_filled and both nets.
 // Tensors saved for backward are t-major: [T][R][F] with R = B * N agent rows (r = b * N + n).
+//
+// Mixers (MlgLearnerCfg.mixer / hypernet_layers; everything else is refused by check_cfg):
+//   0 none (IQL)   iql_td: td[b,t,n] = Q_chosen[b,t,n] - (r[b,t] + gamma (1 - term[b,t]) target[b,t+1,n]), the target
+//                  per agent as for VDN/QMIX. The reference expands the mask over the agents (q_learner.py:89-98), so
+//                  every denominator is mask_elems = N sum(mask): loss = sum(mask td^2) / mask_elems, td_error_abs
+//                  likewise; q_taken_mean and target_mean divide by mask_elems * N (the reference's double division,
+//                  kept). stats[5] = mask_elems, stats[6] = count_nonzero of the expanded mask = N count_nonzero(mask),
+//                  which is also what trained_steps grows by. n_mixer = 0: no mixer pack, no mixer jobs.
+//   1 vdn          mix_td (sum over agents)
+//   2 qmix         hypernet_layers 2: mixing_embed_dim E in {16, 32, 64}, hypernet_embed HE in {32, 64, 128}. E = 32,
+//                  HE = 64 keeps its prefetching / split forms (MixerPF, rec4_mixpre + mix_td2); the other widths run
+//                  the generic one-kernel mix_td<HE, E>.
+//                  hypernet_layers 1 (qmix.py:17, the reference's fallback): hyper_w_1 = Linear(S, N E) and
+//                  hyper_w_final = Linear(S, E) read the state directly; mix_td1<E>, E in {16, 32, 64}. Flat order
+//                  hyper_w_1.{weight, bias}, hyper_w_final.{weight, bias}, hyper_b_1.{weight, bias},
+//                  V.{0.weight, 0.bias, 2.weight, 2.bias}.
 #include <algorithm>
 
 #include "agent_device.h"
@@ -52,17 +68,20 @@ __host__ __device__ inline AgentOffs agent_offs(int H, int d_in, int A) {
 struct MixOffs {
     int64_t w1_0w, w1_0b, w1_2w, w1_2b, wf_0w, wf_0b, wf_2w, wf_2b, b1w, b1b, v0w, v0b, v2w, v2b, total;
 };
-__host__ __device__ inline MixOffs mix_offs(int N, int S, int E, int HE) {
+// One layer: w1_0 / wf_0 are hyper_w_1 [N E][S] and hyper_w_final [E][S] themselves; the .2 entries are empty.
+__host__ __device__ inline MixOffs mix_offs(int N, int S, int E, int HE, int layers) {
     MixOffs o;
     int64_t p = 0;
-    o.w1_0w = p; p += (int64_t)HE * S;
-    o.w1_0b = p; p += HE;
-    o.w1_2w = p; p += (int64_t)N * E * HE;
-    o.w1_2b = p; p += (int64_t)N * E;
-    o.wf_0w = p; p += (int64_t)HE * S;
-    o.wf_0b = p; p += HE;
-    o.wf_2w = p; p += (int64_t)E * HE;
-    o.wf_2b = p; p += E;
+    const bool two = layers != 1;
+    const int64_t r0 = two ? HE : (int64_t)N * E, r1 = two ? HE : E;
+    o.w1_0w = p; p += r0 * S;
+    o.w1_0b = p; p += r0;
+    o.w1_2w = p; p += two ? (int64_t)N * E * HE : 0;
+    o.w1_2b = p; p += two ? (int64_t)N * E : 0;
+    o.wf_0w = p; p += r1 * S;
+    o.wf_0b = p; p += r1;
+    o.wf_2w = p; p += two ? (int64_t)E * HE : 0;
+    o.wf_2b = p; p += two ? E : 0;
     o.b1w = p; p += (int64_t)E * S;
     o.b1b = p; p += E;
     o.v0w = p; p += (int64_t)E * S;
@@ -74,20 +93,25 @@ __host__ __device__ inline MixOffs mix_offs(int N, int S, int E, int HE) {
 }
 
 // ---- packed mixer block: m1 = [w1h | wfh | b1 | vh] rows over padded state, transposes, padded V.2 ----
+// One layer: the rows that read the state are m1 = [hyper_w_1 (N E rows) | hyper_w_final | b1 | vh]; a2T and f2T are
+// empty. r0 / r1 = rows of m1's first two blocks (HE, HE or N E, E).
 struct MixPack {
-    int L1, Sp, NE;
+    int L1, Sp, NE, r0, r1;
     int64_t m1, mb1, a2T, f2T, v2p, bv2p, total;
 };
-__host__ __device__ inline MixPack mix_pack(int N, int S, int E, int HE) {
+__host__ __device__ inline MixPack mix_pack(int N, int S, int E, int HE, int layers) {
     MixPack m;
-    m.L1 = 2 * HE + 2 * E;
-    m.Sp = (S + 15) / 16 * 16;
+    const bool two = layers != 1;
     m.NE = N * E;
+    m.r0 = two ? HE : m.NE;
+    m.r1 = two ? HE : E;
+    m.L1 = m.r0 + m.r1 + 2 * E;
+    m.Sp = (S + 15) / 16 * 16;
     int64_t p = 0;
     m.m1 = p; p += (int64_t)m.L1 * m.Sp;
     m.mb1 = p; p += m.L1;
-    m.a2T = p; p += (int64_t)HE * m.NE;
-    m.f2T = p; p += (int64_t)HE * E;
+    m.a2T = p; p += two ? (int64_t)HE * m.NE : 0;
+    m.f2T = p; p += two ? (int64_t)HE * E : 0;
     m.v2p = p; p += (int64_t)16 * E;
     m.bv2p = p; p += 16;
     m.total = mlg_align4(p);
@@ -142,21 +166,22 @@ __host__ __device__ inline int64_t a4(int64_t v) { return mlg_align4(v); }
 __device__ __forceinline__ float pack_mixer_elem(const MixPack& mp, const MixOffs& mo, const float* __restrict__ P,
                                                  int64_t i, int S, int E, int HE) {
     float v = 0.f;
+    const int r0 = mp.r0, r01 = mp.r0 + mp.r1;  // HE, 2 HE (one layer: N E, N E + E)
     if (i < mp.mb1) {
         const int r = (int)(i / mp.Sp), c = (int)(i % mp.Sp);
         if (c < S) {
-            if (r < HE) v = P[mo.w1_0w + (int64_t)r * S + c];
-            else if (r < 2 * HE) v = P[mo.wf_0w + (int64_t)(r - HE) * S + c];
-            else if (r < 2 * HE + E) v = P[mo.b1w + (int64_t)(r - 2 * HE) * S + c];
-            else v = P[mo.v0w + (int64_t)(r - 2 * HE - E) * S + c];
+            if (r < r0) v = P[mo.w1_0w + (int64_t)r * S + c];
+            else if (r < r01) v = P[mo.wf_0w + (int64_t)(r - r0) * S + c];
+            else if (r < r01 + E) v = P[mo.b1w + (int64_t)(r - r01) * S + c];
+            else v = P[mo.v0w + (int64_t)(r - r01 - E) * S + c];
         }
     } else if (i < mp.a2T) {
         const int r = (int)(i - mp.mb1);
-        if (r < HE) v = P[mo.w1_0b + r];
-        else if (r < 2 * HE) v = P[mo.wf_0b + r - HE];
-        else if (r < 2 * HE + E) v = P[mo.b1b + r - 2 * HE];
-        else v = P[mo.v0b + r - 2 * HE - E];
-    } else if (i < mp.f2T) {  // a2T [HE][NE] = w1_2w^T
+        if (r < r0) v = P[mo.w1_0b + r];
+        else if (r < r01) v = P[mo.wf_0b + r - r0];
+        else if (r < r01 + E) v = P[mo.b1b + r - r01];
+        else v = P[mo.v0b + r - r01 - E];
+    } else if (i < mp.f2T) {  // a2T [HE][NE] = w1_2w^T (two layers only)
         const int64_t k = i - mp.a2T;
         const int r = (int)(k / mp.NE), c = (int)(k % mp.NE);
         v = P[mo.w1_2w + (int64_t)c * HE + r];
@@ -786,32 +811,39 @@ __device__ __forceinline__ float row_sum16(float v) {  // sum over the 16 lanes 
 }
 
 // chosen / target per-agent values of row (b, t) (q_learner.py:55, 68-75)
+__device__ __forceinline__ void gather_q1(const LCfg& c, const MlgBatch& bt, const float* mac, const float* tmac, int b,
+                                          int t, int n, int& act, float& cq, float& tq) {
+    const int N = c.N, A = c.A, R = c.R;
+    const int r = b * N + n;
+    const int a = (int)bt.actions[(bslot(bt, b) * bt.T1 + t) * N + n];
+    act = a;
+    cq = mac[((int64_t)t * R + r) * A + a];
+    const int32_t* av = bt.avail + (bslot(bt, b) * bt.T1 + t + 1) * N * A + (int64_t)n * A;
+    const float* qn = mac + ((int64_t)(t + 1) * R + r) * A;
+    const float* tn = tmac + ((int64_t)(t + 1) * R + r) * A;
+    if (c.double_q) {
+        float bv = 0.f;
+        int bi = 0;
+        for (int k = 0; k < A; ++k) {
+            const float v = av[k] ? qn[k] : -9999999.f;
+            if (k == 0 || v > bv) { bv = v; bi = k; }
+        }
+        tq = av[bi] ? tn[bi] : -9999999.f;
+    } else {
+        float bv = 0.f;
+        for (int k = 0; k < A; ++k) {
+            const float v = av[k] ? tn[k] : -9999999.f;
+            if (k == 0 || v > bv) bv = v;
+        }
+        tq = bv;
+    }
+}
+
 __device__ __forceinline__ void gather_q(const LCfg& c, const MlgBatch& bt, const float* mac, const float* tmac, int b, int t,
                                          float* cq, float* tq) {
-    const int N = c.N, A = c.A, R = c.R;
-    for (int n = 0; n < N; ++n) {
-        const int r = b * N + n;
-        const int a = (int)bt.actions[(bslot(bt, b) * bt.T1 + t) * N + n];
-        cq[n] = mac[((int64_t)t * R + r) * A + a];
-        const int32_t* av = bt.avail + (bslot(bt, b) * bt.T1 + t + 1) * N * A + (int64_t)n * A;
-        const float* qn = mac + ((int64_t)(t + 1) * R + r) * A;
-        const float* tn = tmac + ((int64_t)(t + 1) * R + r) * A;
-        if (c.double_q) {
-            float bv = 0.f;
-            int bi = 0;
-            for (int k = 0; k < A; ++k) {
-                const float v = av[k] ? qn[k] : -9999999.f;
-                if (k == 0 || v > bv) { bv = v; bi = k; }
-            }
-            tq[n] = av[bi] ? tn[bi] : -9999999.f;
-        } else {
-            float bv = 0.f;
-            for (int k = 0; k < A; ++k) {
-                const float v = av[k] ? tn[k] : -9999999.f;
-                if (k == 0 || v > bv) bv = v;
-            }
-            tq[n] = bv;
-        }
+    for (int n = 0; n < c.N; ++n) {
+        int a;
+        gather_q1(c, bt, mac, tmac, b, t, n, a, cq[n], tq[n]);
     }
 }
 
@@ -1166,6 +1198,262 @@ __global__ void __launch_bounds__(128) mix_td_kernel(LCfg c, MlgBatch bt, MixPtr
             const int a = (int)bt.actions[(bslot(bt, b) * bt.T1 + t) * N + n];
             o.d2[((int64_t)t * c.R + r) * c.A + a] = dq[n];
         }
+    }
+}
+
+// ================================================================================================
+// QMixer with one-layer hypernetworks (qmix.py:17-19) on one 16-row tile: hyper_w_1, hyper_w_final, hyper_b_1 and V.0
+// all read the state row. The rows of m1 behind hyper_w_1's N E are l1 = [wf (pre-abs) | b1 | vh (post ReLU)];
+// hyper_w_1's own N E outputs (up to 32 agents x 64 features per row) are never held: w1pre() computes one 16-feature
+// chunk of one agent from the state when the forward and again when the backward needs it, as Mixer does.
+template <int E>
+struct Mixer1 {
+    static constexpr int TE = E / 16, L1T = 3 * TE;
+    static constexpr int OWF = 0, OB1 = TE, OVH = 2 * TE;
+
+    __device__ static void layer1(const MixPtrs& M, const MixPack& mp, int S, const float* s, floatx4 (&l1)[L1T], int lane) {
+        const int col = lane & 15, g = lane >> 4;
+        const int r0 = mp.NE;
+#pragma unroll
+        for (int mt = 0; mt < L1T; ++mt) l1[mt] = ld4(M.mb1 + r0 + mt * 16 + 4 * g);
+        for (int kc = 0; kc < mp.Sp / 16; ++kc) {
+            const floatx4 sv = load_chunk(s, kc * 16 + 4 * g, S);
+#pragma unroll
+            for (int mt = 0; mt < L1T; ++mt)
+                l1[mt] = mfma_chunk(ld4(M.m1 + (int64_t)(r0 + mt * 16 + col) * mp.Sp + kc * 16 + 4 * g), sv, l1[mt]);
+        }
+#pragma unroll
+        for (int mt = OVH; mt < L1T; ++mt) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) l1[mt][q] = fmaxf(l1[mt][q], 0.f);
+        }
+    }
+
+    // pre-abs hyper_w_1 output for agent n, chunk cc (features n*E + cc*16 ..), from the state row
+    __device__ static floatx4 w1pre(const MixPtrs& M, const MixPack& mp, int S, const float* s, int n, int cc, int lane) {
+        const int col = lane & 15, g = lane >> 4;
+        floatx4 acc = ld4(M.mb1 + n * E + cc * 16 + 4 * g);
+        const float* wrow = M.m1 + (int64_t)(n * E + cc * 16 + col) * mp.Sp + 4 * g;
+        for (int kc = 0; kc < mp.Sp / 16; ++kc)
+            acc = mfma_chunk(ld4(wrow + kc * 16), load_chunk(s, kc * 16 + 4 * g, S), acc);
+        return acc;
+    }
+
+    __device__ static float vval(const MixPtrs& M, const floatx4 (&l1)[L1T], int lane) {
+        const int col = lane & 15, g = lane >> 4;
+        floatx4 acc = ld4(M.bv2p + 4 * g);
+        const float* wrow = M.v2p + (int64_t)col * E + 4 * g;
+#pragma unroll
+        for (int kc = 0; kc < TE; ++kc) acc = mfma_chunk(ld4(wrow + kc * 16), l1[OVH + kc], acc);
+        return __shfl(acc[0], col);  // feature 0 lives in lane group 0, reg 0
+    }
+
+    // forward: y per row (identical in the 4 lanes of a row); l1[OWF ..] are the pre-abs hyper_w_final outputs
+    __device__ static float forward(const MixPtrs& M, const MixPack& mp, int S, int N, const float* s, const float* qrow,
+                                    floatx4 (&l1)[L1T], floatx4 (&pre)[TE], floatx4 (&hid)[TE], int lane) {
+        layer1(M, mp, S, s, l1, lane);
+#pragma unroll
+        for (int cc = 0; cc < TE; ++cc) pre[cc] = l1[OB1 + cc];
+        for (int n = 0; n < N; ++n) {
+            const float qn = qrow[n];
+#pragma unroll
+            for (int cc = 0; cc < TE; ++cc) {
+                const floatx4 wp = w1pre(M, mp, S, s, n, cc, lane);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pre[cc][q] += qn * fabsf(wp[q]);
+            }
+        }
+        float part = 0.f;
+#pragma unroll
+        for (int cc = 0; cc < TE; ++cc) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                hid[cc][q] = pre[cc][q] > 0.f ? pre[cc][q] : expm1f(pre[cc][q]);
+                part += hid[cc][q] * fabsf(l1[OWF + cc][q]);
+            }
+        }
+        part += __shfl_xor(part, 16);
+        part += __shfl_xor(part, 32);
+        return part + vval(M, l1, lane);
+    }
+};
+
+// mix_td_kernel for one-layer hypernetworks: the same two waves per 16-row tile (wave 0 the target mixer, wave 1 the
+// online forward, TD and backward), the same loss partials and dq / d2 deltas. The hypernetworks have no hidden layer
+// to carry a gradient back through: the weight-gradient deltas are the pre-abs hyper outputs' own (da2 [RM][N E] for
+// hyper_w_1, df2 [RM][E] for hyper_w_final, d1 = [b1 | vh] [RM][2 E]), all against the state row; l1act [RM][E] keeps
+// V's hidden activations for V.2.
+template <int E>
+__global__ void __launch_bounds__(128) mix_td1_kernel(LCfg c, MlgBatch bt, MixPtrs Mon, MixPtrs Mtg, MixPack mp,
+                                                     const float* __restrict__ mac, const float* __restrict__ tmac_,
+                                                     const float* __restrict__ msum_p, MixOut o, Skip sk) {
+    using Mx = Mixer1<E>;
+    __shared__ float tgt_sh[16];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
+    const int rm = blockIdx.x * 16 + col;
+    const int Tm = c.T - 1;
+    const bool valid = rm < c.RM;
+    const int b = valid ? rm / Tm : 0, t = valid ? rm % Tm : 0;
+    const int N = c.N, S = c.S, NE = N * E;
+    // dead transitions as in mix_td_kernel: zeros for their Qs and state, nothing stored, exact zeros into the sums
+    const bool live = valid && t < (int)sk.mlen[b];
+    if (!__any(live)) {  // both waves of the tile alike
+        if (wv == 1 && lane < 4) o.part[(int64_t)blockIdx.x * 4 + lane] = 0.f;
+        return;
+    }
+    const bool tr = target_runs(c, sk);  // else the online buffers hold the target's bits
+    const float* tmac = tr ? tmac_ : mac;
+    const MixPtrs& Mt = tr ? Mtg : Mon;
+    float cq[MAXN], tq[MAXN];
+    for (int n = 0; n < N; ++n) cq[n] = tq[n] = 0.f;
+    if (live) gather_q(c, bt, mac, tmac, b, t, cq, tq);
+    const float m = live ? mask_at(bt, b, t) : 0.f;  // reference truncation: mlen <= t_eff - 1
+    const float rwd = valid ? bt.reward[bslot(bt, b) * bt.T1 + t] : 0.f;
+    const float term = valid ? (float)bt.terminated[bslot(bt, b) * bt.T1 + t] : 0.f;
+    const float msum = msum_p[0];
+    const float* s0 = live ? bt.state + (bslot(bt, b) * bt.T1 + t) * S : nullptr;
+    const float* s1 = live ? bt.state + (bslot(bt, b) * bt.T1 + t + 1) * S : nullptr;
+    float qtot = 0.f;
+    floatx4 l1[Mx::L1T], pre[Mx::TE], hid[Mx::TE];
+    if (wv == 0) {
+        const float tv = Mx::forward(Mt, mp, S, N, s1, tq, l1, pre, hid, lane);
+        if (g == 0) tgt_sh[col] = tv;
+    } else {
+        qtot = Mx::forward(Mon, mp, S, N, s0, cq, l1, pre, hid, lane);
+    }
+    __syncthreads();
+    if (wv == 0) return;
+    const float tgt = tgt_sh[col];
+    const float y = rwd + c.gamma * (1.f - term) * tgt;  // q_learner.py:86
+    const float mtd = (qtot - y) * m;                     // :89-95
+    const float dy = 2.f * mtd * m / msum;                // d loss / d q_tot
+    {
+        float p0 = g == 0 ? mtd * mtd : 0.f, p1 = g == 0 ? fabsf(mtd) : 0.f;
+        float p2 = g == 0 ? qtot * m : 0.f, p3 = g == 0 ? y * m : 0.f;
+        p0 = row_sum16(p0);
+        p1 = row_sum16(p1);
+        p2 = row_sum16(p2);
+        p3 = row_sum16(p3);
+        if (lane == 0) {
+            float* pp = o.part + (int64_t)blockIdx.x * 4;
+            pp[0] = p0;
+            pp[1] = p1;
+            pp[2] = p2;
+            pp[3] = p3;
+        }
+    }
+    // ---- QMixer backward (autograd of qmix.py:41-59) ----
+    floatx4 dpre[Mx::TE], dwf[Mx::TE];
+#pragma unroll
+    for (int cc = 0; cc < Mx::TE; ++cc) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float wf = l1[Mx::OWF + cc][q];
+            const float dh = dy * fabsf(wf);
+            const float sg = wf > 0.f ? 1.f : (wf < 0.f ? -1.f : 0.f);
+            dwf[cc][q] = dy * hid[cc][q] * sg;
+            dpre[cc][q] = pre[cc][q] > 0.f ? dh : dh * (hid[cc][q] + 1.f);
+        }
+    }
+    float dq[MAXN];
+    for (int n = 0; n < N; ++n) {
+        float part = 0.f;
+#pragma unroll
+        for (int cc = 0; cc < Mx::TE; ++cc) {
+            const floatx4 wp = Mx::w1pre(Mon, mp, S, s0, n, cc, lane);  // MFMA: every lane, outside the store guard
+            floatx4 dlt;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                part += fabsf(wp[q]) * dpre[cc][q];
+                const float sg = wp[q] > 0.f ? 1.f : (wp[q] < 0.f ? -1.f : 0.f);
+                dlt[q] = cq[n] * dpre[cc][q] * sg;
+            }
+            if (live) *reinterpret_cast<floatx4*>(o.da2 + (int64_t)rm * NE + n * E + cc * 16 + 4 * g) = dlt;
+        }
+        part += __shfl_xor(part, 16);
+        part += __shfl_xor(part, 32);
+        dq[n] = part;
+    }
+    if (live) {
+        float* d1 = o.d1 + (int64_t)rm * 2 * E;
+#pragma unroll
+        for (int cc = 0; cc < Mx::TE; ++cc) {  // b1, vh, hyper_w_final, V's hidden activations
+            *reinterpret_cast<floatx4*>(d1 + cc * 16 + 4 * g) = dpre[cc];
+            const floatx4 wv2 = ld4(Mon.v2p + cc * 16 + 4 * g);
+            floatx4 v;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = l1[Mx::OVH + cc][q] > 0.f ? dy * wv2[q] : 0.f;
+            *reinterpret_cast<floatx4*>(d1 + E + cc * 16 + 4 * g) = v;
+            *reinterpret_cast<floatx4*>(o.df2 + (int64_t)rm * E + cc * 16 + 4 * g) = dwf[cc];
+            *reinterpret_cast<floatx4*>(o.l1act + (int64_t)rm * E + cc * 16 + 4 * g) = l1[Mx::OVH + cc];
+        }
+        if (g == 0) {
+            o.dv2[rm] = dy;
+            for (int k = 0; k < S; ++k) o.srow[(int64_t)rm * S + k] = s0[k];
+            for (int n = 0; n < N; ++n) {  // dQ per agent row (t-major) and its one-hot expansion for dW2
+                const int r = b * N + n;
+                o.dq[(int64_t)t * c.R + r] = dq[n];
+                const int a = (int)bt.actions[(bslot(bt, b) * bt.T1 + t) * N + n];
+                o.d2[((int64_t)t * c.R + r) * c.A + a] = dq[n];
+            }
+        }
+    }
+}
+
+// IQL (mixer 0): no mixing, one TD error per (b, t, agent) against the agent's own target, the mask expanded over the
+// agents (msum_p[0] * N = mask_elems divides the loss; stored to msum_p[2], which finish_kernel then takes as its mask
+// sum, so every statistic's denominator, stats[5], stats[6] and trained_steps follow the expanded mask). One wave per
+// 16 (b, t) rows, as the mixer kernels' tiles:
+// lane (col, g) takes row col's agents g, g + 4, ... in order; the four groups of a row and then the 16 rows are summed
+// in a fixed order into the tile's four partials. Writes the same sparse dq / d2 deltas as the mixer kernels.
+__global__ void __launch_bounds__(64) iql_td_kernel(LCfg c, MlgBatch bt, const float* __restrict__ mac,
+                                                   const float* __restrict__ tmac_, float* __restrict__ msum_p,
+                                                   MixOut o, Skip sk) {
+    const int lane = threadIdx.x, col = lane & 15, g = lane >> 4;
+    const float melems = msum_p[0] * (float)c.N;  // sum of the expanded mask (q_learner.py:92)
+    if (blockIdx.x == 0 && lane == 0) msum_p[2] = melems;  // finish_kernel's mask sum for this call (msum[2] is free)
+    const int rm = blockIdx.x * 16 + col;
+    const int Tm = c.T - 1;
+    const bool valid = rm < c.RM;
+    const int b = valid ? rm / Tm : 0, t = valid ? rm % Tm : 0;
+    const bool live = valid && t < (int)sk.mlen[b];  // dead transitions: mask 0, exact zeros, nothing stored
+    if (!__any(live)) {
+        if (lane < 4) o.part[(int64_t)blockIdx.x * 4 + lane] = 0.f;
+        return;
+    }
+    const float* tmac = target_runs(c, sk) ? tmac_ : mac;  // else the online buffer holds the target's bits
+    float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+    if (live) {
+        const float m = mask_at(bt, b, t);
+        const float rwd = bt.reward[bslot(bt, b) * bt.T1 + t];
+        const float term = (float)bt.terminated[bslot(bt, b) * bt.T1 + t];
+        for (int n = g; n < c.N; n += 4) {
+            int a;
+            float cq, tq;
+            gather_q1(c, bt, mac, tmac, b, t, n, a, cq, tq);
+            const float y = rwd + c.gamma * (1.f - term) * tq;  // q_learner.py:86
+            const float mtd = (cq - y) * m;                      // :89-95
+            const float dy = 2.f * mtd * m / melems;             // d loss / d Q_chosen[b, t, n]
+            p0 += mtd * mtd;
+            p1 += fabsf(mtd);
+            p2 += cq * m;
+            p3 += y * m;
+            const int64_t row = (int64_t)t * c.R + b * c.N + n;
+            o.dq[row] = dy;
+            o.d2[row * c.A + a] = dy;
+        }
+    }
+    float p[4] = {p0, p1, p2, p3};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        p[k] += __shfl_xor(p[k], 16);
+        p[k] += __shfl_xor(p[k], 32);
+        p[k] = row_sum16(p[k]);
+    }
+    if (lane == 0) {
+        float* pp = o.part + (int64_t)blockIdx.x * 4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pp[k] = p[k];
     }
 }
 
@@ -1600,6 +1888,7 @@ struct Plan {
     MixPack mp;
     WsLayout w;
     int64_t n_agent, n_mixer;
+    int layers;  // qmix hypernet_layers (1 or 2)
 };
 
 int check_cfg(const MlgLearnerCfg* c) {
@@ -1611,11 +1900,14 @@ int check_cfg(const MlgLearnerCfg* c) {
     MLG_REQUIRE((int64_t)c->T * c->B * c->N * 3 * c->H < (int64_t)1 << 29,
                 "learner: T*B*N*3H=%lld floats exceeds the 2 GB buffer-store range",
                 (long long)c->T * c->B * c->N * 3 * c->H);
-    MLG_REQUIRE(c->mixer == 1 || c->mixer == 2, "learner: mixer must be vdn or qmix (IQL is not built)");
+    MLG_REQUIRE(c->mixer >= 0 && c->mixer <= 2, "learner: mixer=%d unsupported (0 none, 1 vdn, 2 qmix)", c->mixer);
     if (c->mixer == 2) {
-        MLG_REQUIRE(c->hypernet_layers == 2, "learner: qmix hypernet_layers=%d unsupported (2)", c->hypernet_layers);
-        MLG_REQUIRE(c->E == 32 && c->HE == 64, "learner: qmix mixing_embed_dim=32, hypernet_embed=64 supported (got %d, %d)",
-                    c->E, c->HE);
+        MLG_REQUIRE(c->hypernet_layers == 1 || c->hypernet_layers == 2, "learner: qmix hypernet_layers=%d unsupported (1, 2)",
+                    c->hypernet_layers);
+        MLG_REQUIRE(c->E == 16 || c->E == 32 || c->E == 64, "learner: qmix mixing_embed_dim=%d unsupported (16, 32, 64)",
+                    c->E);
+        MLG_REQUIRE(c->hypernet_layers == 1 || c->HE == 32 || c->HE == 64 || c->HE == 128,
+                    "learner: qmix hypernet_embed=%d unsupported (32, 64, 128)", c->HE);
     }
     return 0;
 }
@@ -1643,16 +1935,18 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
     c.RM = cfg->B * (cfg->T - 1);
     c.gamma = cfg->gamma;
     c.full = getenv("MLG_LEARNER_FULL") != nullptr;  // read per call, so a test can set it
+    p.layers = cfg->mixer == 2 ? cfg->hypernet_layers : 2;
     MlgAgentDims d{cfg->d_obs, cfg->A, cfg->N, cfg->H, c.d_in, cfg->obs_last_action, cfg->obs_agent_id};
     p.L = make_agent_layout(d);
     p.ao = agent_offs(c.H, c.d_in, c.A);
-    p.mo = mix_offs(c.N, c.S, c.E, c.HE);
-    p.mp = mix_pack(c.N, c.S, c.E, c.HE);
+    p.mo = mix_offs(c.N, c.S, c.E, c.HE, p.layers);
+    p.mp = mix_pack(c.N, c.S, c.E, c.HE, p.layers);
     p.n_agent = p.ao.total;
     p.n_mixer = c.mixer == 2 ? p.mo.total : 0;
     WsLayout& w = p.w;
     const int64_t T = c.T, R = c.R, H = c.H, RM = c.RM;
-    const int L1 = 2 * c.HE + 2 * c.E;
+    const bool one = p.layers == 1;  // mix_td1_kernel's rows: d1 = [b1 | vh], l1act = V's hidden activations
+    const int L1 = one ? 2 * c.E : 2 * c.HE + 2 * c.E;
     int64_t o = 0;
     auto take = [&](int64_t n) { int64_t r = o; o += a4(n); return r; };
     w.p_on = take(p.L.total);
@@ -1678,7 +1972,7 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
     w.dgh = take(T * R * 3 * H);
     w.da = take(T * R * H);
     w.srow = take(RM * c.S);
-    w.l1act = take(RM * L1);
+    w.l1act = take(RM * (one ? c.E : L1));
     w.d1 = take(RM * L1);
     w.da2 = take(RM * c.N * c.E);
     w.df2 = take(RM * c.E);
@@ -1719,7 +2013,19 @@ WJobs make_jobs(Plan& p, float* ws, float* grads, int64_t* slab_floats, int* n_t
     J.j[J.n++] = mlg::bjob(at(p.w.d2), c.A, at(p.w.hs) ? at(p.w.hs) + (int64_t)c.R * H : nullptr, H, gp(a.fc2w), gp(a.fc2b),
                      c.A, H, TR);
     const int n_agent_jobs = J.n;
-    if (c.mixer == 2) {
+    if (c.mixer == 2 && p.layers == 1) {  // every delta against the state row; V.2 against V's hidden activations
+        const MixOffs& m = p.mo;
+        const int64_t G0 = p.n_agent;
+        auto mg = [&](int64_t off) { return G ? G + G0 + off : (float*)nullptr; };
+        const float* d1 = at(p.w.d1);
+        auto off = [&](const float* base, int64_t k) { return base ? base + k : (const float*)nullptr; };
+        const int NE = c.N * c.E;
+        J.j[J.n++] = mlg::bjob(at(p.w.da2), NE, at(p.w.srow), c.S, mg(m.w1_0w), mg(m.w1_0b), NE, c.S, RM);
+        J.j[J.n++] = mlg::bjob(at(p.w.df2), c.E, at(p.w.srow), c.S, mg(m.wf_0w), mg(m.wf_0b), c.E, c.S, RM);
+        J.j[J.n++] = mlg::bjob(off(d1, 0), 2 * c.E, at(p.w.srow), c.S, mg(m.b1w), mg(m.b1b), c.E, c.S, RM);
+        J.j[J.n++] = mlg::bjob(off(d1, c.E), 2 * c.E, at(p.w.srow), c.S, mg(m.v0w), mg(m.v0b), c.E, c.S, RM);
+        J.j[J.n++] = mlg::bjob(at(p.w.dv2), 1, at(p.w.l1act), c.E, mg(m.v2w), mg(m.v2b), 1, c.E, RM);
+    } else if (c.mixer == 2) {
         const MixOffs& m = p.mo;
         const int64_t G0 = p.n_agent;
         auto mg = [&](int64_t off) { return G ? G + G0 + off : (float*)nullptr; };
@@ -1784,7 +2090,8 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     // split mixer (default for the FAST shapes): the hypernetwork forward rides in the recurrence launch
     // (rec4_mixpre_kernel), mix_td2_kernel does the rest. VDN runs the one-kernel mix_td; MLG_MIX_GENERIC=1
     // forces its generic form (the path of the other shapes; read per call, so a test can set it)
-    const bool fast_mix = p.mp.Sp <= 64 && c.N <= MIXPF_N && c.A <= MIXPF_A && !getenv("MLG_MIX_GENERIC");
+    const bool dflt_mix = c.mixer == 1 || (c.mixer == 2 && p.layers == 2 && c.E == 32 && c.HE == 64);
+    const bool fast_mix = dflt_mix && p.mp.Sp <= 64 && c.N <= MIXPF_N && c.A <= MIXPF_A && !getenv("MLG_MIX_GENERIC");
     const int threads = (c.H / 16) * 64;
     const bool split_mix = c.mixer == 2 && fast_mix && threads % 128 == 0;
     pj.d2 = ws + p.w.d2;  // d2 is sparse: zero it (and dq) every call
@@ -1857,15 +2164,38 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
                        ws + p.w.p_tg, ws + p.w.hs, ws + p.w.hs_tg, ws + p.w.mac, ws + p.w.tmac, sk);
     MixOut mo{ws + p.w.srow, ws + p.w.l1act, ws + p.w.d1, ws + p.w.da2, ws + p.w.df2, ws + p.w.dv2,
               ws + p.w.dq, ws + p.w.d2, ws + p.w.part};
-    if (split_mix) {
+#define MLG_MIX_LAUNCH(K)                                                                                       \
+    hipLaunchKernelGGL((K), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, Mtg, p.mp, ws + p.w.mac, ws + p.w.tmac, \
+                       ws + p.w.msum, mo, sk)
+    if (c.mixer == 0) {
+        hipLaunchKernelGGL(iql_td_kernel, dim3(p.w.n_mix_tiles), dim3(64), 0, s, c, bt, ws + p.w.mac, ws + p.w.tmac,
+                           ws + p.w.msum, mo, sk);
+    } else if (split_mix) {
         hipLaunchKernelGGL((mix_td2_kernel<64, 32>), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, ws + p.w.mac,
                            ws + p.w.tmac, ws + p.w.msum, hy, mo, sk);
-    } else if (fast_mix)
-        hipLaunchKernelGGL((mix_td_kernel<64, 32, true>), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, Mtg, p.mp,
-                           ws + p.w.mac, ws + p.w.tmac, ws + p.w.msum, mo, sk);
-    else
-        hipLaunchKernelGGL((mix_td_kernel<64, 32>), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, Mtg, p.mp,
-                           ws + p.w.mac, ws + p.w.tmac, ws + p.w.msum, mo, sk);
+    } else if (fast_mix) {
+        MLG_MIX_LAUNCH((mix_td_kernel<64, 32, true>));
+    } else if (c.mixer == 2 && p.layers == 1) {  // widths checked by check_cfg
+        if (c.E == 16) MLG_MIX_LAUNCH(mix_td1_kernel<16>);
+        else if (c.E == 32) MLG_MIX_LAUNCH(mix_td1_kernel<32>);
+        else MLG_MIX_LAUNCH(mix_td1_kernel<64>);
+    } else if (dflt_mix) {
+        MLG_MIX_LAUNCH((mix_td_kernel<64, 32>));
+    } else {  // the other widths: the generic one-kernel form only
+        const int key = c.HE * 1000 + c.E;
+        switch (key) {
+            case 32016: MLG_MIX_LAUNCH((mix_td_kernel<32, 16>)); break;
+            case 32032: MLG_MIX_LAUNCH((mix_td_kernel<32, 32>)); break;
+            case 32064: MLG_MIX_LAUNCH((mix_td_kernel<32, 64>)); break;
+            case 64016: MLG_MIX_LAUNCH((mix_td_kernel<64, 16>)); break;
+            case 64064: MLG_MIX_LAUNCH((mix_td_kernel<64, 64>)); break;
+            case 128016: MLG_MIX_LAUNCH((mix_td_kernel<128, 16>)); break;
+            case 128032: MLG_MIX_LAUNCH((mix_td_kernel<128, 32>)); break;
+            case 128064: MLG_MIX_LAUNCH((mix_td_kernel<128, 64>)); break;
+            default: return mlg::fail("learner: no mixer kernel for hypernet_embed=%d mixing_embed_dim=%d", c.HE, c.E);
+        }
+    }
+#undef MLG_MIX_LAUNCH
     // weight gradients: fc2 and the mixer's jobs (final after the mixer kernel, table view JA) run as extra
     // workgroups of the reverse-recurrence launch (H = 64, bwd4_wgrad_kernel); fc1 / W_ih / W_hh (view JB) after
     // agent_dx; one reduce over the whole table
@@ -1899,7 +2229,7 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
                        ws + p.w.slab, ws + p.w.nrm);
     const int64_t n_par = p.n_agent + p.n_mixer;
     hipLaunchKernelGGL(finish_kernel, dim3((unsigned)((n_par + 1023) / 1024)), dim3(1024), 0, s, ws + p.w.part,
-                       p.w.n_mix_tiles, ws + p.w.msum, bufs->params, bufs->grads, bufs->square_avg, n_par, cfg->lr,
+                       p.w.n_mix_tiles, ws + p.w.msum + (c.mixer == 0 ? 2 : 0), bufs->params, bufs->grads, bufs->square_avg, n_par, cfg->lr,
                        cfg->optim_alpha, cfg->optim_eps, cfg->grad_norm_clip, c.N, bufs->stats, ws + p.w.nrm,
                        n_red_blocks, bufs->target_sync, bufs->trained_steps, sk, pj.flag, ntiles, c.full);
     return mlg::check_launch("qlearner_train");

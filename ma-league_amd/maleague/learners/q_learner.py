@@ -1,4 +1,4 @@
-"""QMIX/VDN Q-learner (API of src/marl/learners/learner.py:6-79 and q_learner.py:15-147).
+"""QMIX/VDN/IQL Q-learner (API of src/marl/learners/learner.py:6-79 and q_learner.py:15-147).
 
 train() is one call into the fused gfx950 pipeline (mlg_qlearner_train): online + target BPTT unrolls,
 double-Q targets, mixer forward/backward, masked TD loss, all weight gradients, clip_grad_norm_ and the
@@ -22,6 +22,9 @@ AGENT_ORDER = ["fc1.weight", "fc1.bias", "gru.weight_ih", "gru.weight_hh", "gru.
 QMIX_ORDER = ["hyper_w_1.0.weight", "hyper_w_1.0.bias", "hyper_w_1.2.weight", "hyper_w_1.2.bias",
               "hyper_w_final.0.weight", "hyper_w_final.0.bias", "hyper_w_final.2.weight", "hyper_w_final.2.bias",
               "hyper_b_1.weight", "hyper_b_1.bias", "V.0.weight", "V.0.bias", "V.2.weight", "V.2.bias"]
+# hypernet_layers 1 (the reference QMixer's fallback, qmix.py:17): the hypernets are single Linear layers
+QMIX1_ORDER = ["hyper_w_1.weight", "hyper_w_1.bias", "hyper_w_final.weight", "hyper_w_final.bias",
+               "hyper_b_1.weight", "hyper_b_1.bias", "V.0.weight", "V.0.bias", "V.2.weight", "V.2.bias"]
 
 
 class FlatParams:
@@ -100,8 +103,9 @@ class QLearner(Learner):
             raise RuntimeError(f"agent parameter order {names} != kernel layout {AGENT_ORDER}")
         if isinstance(self.mixer, QMixer):
             names = [n for n, _ in self.mixer.named_parameters()]
-            if names != QMIX_ORDER:
-                raise RuntimeError(f"mixer parameter order {names} != kernel layout {QMIX_ORDER}")
+            order = QMIX1_ORDER if self.mixer.hypernet_layers == 1 else QMIX_ORDER
+            if names != order:
+                raise RuntimeError(f"mixer parameter order {names} != kernel layout {order}")
 
     def build_optimizer(self):
         self._check_order()

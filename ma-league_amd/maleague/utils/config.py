@@ -75,6 +75,12 @@ BUILTIN = {
         "epsilon_anneal_time": 50000, "runner": "episode", "buffer_size": 5000, "target_update_interval": 200,
         "agent_output_type": "q", "learner": "q", "double_q": True, "mixer": "vdn", "name": "vdn",
     },
+    # src/config/algs/iql.yaml: an empty mixer (None) and the learner key "q_learner" (learners.REGISTRY aliases it)
+    "algs/iql": {
+        "action_selector": "epsilon_greedy", "epsilon_start": 1.0, "epsilon_finish": 0.05,
+        "epsilon_anneal_time": 50000, "runner": "episode", "buffer_size": 5000, "target_update_interval": 200,
+        "agent_output_type": "q", "learner": "q_learner", "double_q": True, "mixer": None, "name": "iql",
+    },
 }
 
 

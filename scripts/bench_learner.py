@@ -1,6 +1,7 @@
 """QLearner.train / REFILLearner.train (MODE=refil) microbenchmark on the bench's shapes: 5v5 medium_1h_4t (refil:
 refil_8, 3-8 agents) rollouts (ENVS envs, episode_limit 100) fill a device replay ring, then REPS train() calls on
-batch_size 32 samples read in place (the bench's path).
+batch_size 32 samples read in place (the bench's path). MODE=iql / vdn select those algorithms; extra key=value
+arguments are config overrides (e.g. hypernet_layers=1 mixing_embed_dim=64), so any mixer shape is timed the same way.
 EP_STEP=N advances episode_num by N per call (0: the target network is never updated).
 Prints mean ms per train() (HIP events on the learner's stream) and the loss of the last call, so variant libraries
 (MLG_LIB=...) can be A/B-compared; run under rocprofv3 --kernel-trace --stats for the per-kernel split."""
@@ -31,7 +32,9 @@ if MODE == "refil":
     overrides = [o.replace("medium_1h_4t", "refil_8") for o in overrides]
     cfg = build_config("refil", "ma_entity", overrides=overrides, device_index=0)
 else:
-    cfg = build_config("qmix", "ma", overrides=overrides, device_index=0)
+    if MODE not in ("qmix", "iql", "vdn"):
+        raise SystemExit(f"MODE={MODE!r}: qmix, iql, vdn or refil")
+    cfg = build_config(MODE, "ma", overrides=overrides + sys.argv[1:], device_index=0)
 np.random.seed(0)
 torch.manual_seed(0)
 args = to_args(cfg)
