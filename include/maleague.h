@@ -321,6 +321,45 @@ int mlg_refil_mixer_forward(const MlgRefilDims *d, const float *packed, const fl
                             const uint8_t *entity_mask, const uint8_t *w_mask, const uint8_t *i_mask,
                             int32_t softmax_mixing_weights, float *q_tot, int32_t R, void *stream);
 
+/* ---- Backward of the REFIL layer ops (autograd of torch.ops.maleague.refil_attention / entity_agent_forward) ----
+ * For REFIL learners written the reference's way (src/marl/learners/refil_learner.py:102-218: unroll the MAC, gather,
+ * build a loss, loss.backward()). Same contract as mlg_agent_backward above: each call recomputes its forward from the
+ * step's inputs, writes row activations and deltas to `workspace` (*_workspace_floats floats, 16-byte aligned, any
+ * contents) and reduces every weight and bias gradient in a fixed order (no float atomics: bitwise reproducible).
+ * dparams is overwritten; bs == 0 / R == 0 zeroes it and launches nothing. Entities and masks get no gradient. The
+ * *_workspace_floats calls are host only and return -1 (message in mlg_last_error()) on bad dims.
+ *
+ * mlg_refil_attention_backward differentiates EntityAttentionLayer.forward (src/marl/modules/layers/attention.py:24-79;
+ * shapes as mlg_refil_attention): gy [bs][nq][64] -> dx [bs][ne][64] and dparams = in_trans.weight [192][64],
+ * out_trans.weight [64][64], out_trans.bias [64]. Post-masked query rows pass no gradient; a query row whose every key
+ * is pre-masked contributes zero (attention.py:59). workspace, w_in, w_out and dx 16-byte aligned. */
+int64_t mlg_refil_attention_backward_workspace_floats(int32_t bs, int32_t ne, int32_t nq, int32_t n_heads);
+int mlg_refil_attention_backward(const float *w_in, const float *w_out, const float *b_out, const float *x,
+                                 const uint8_t *pre_mask, const uint8_t *post_mask, const float *gy, int32_t bs,
+                                 int32_t ne, int32_t nq, int32_t n_heads, float *dx, float *dparams, float *workspace,
+                                 void *stream);
+/* mlg_refil_mixer_backward differentiates FlexQMixer.forward (src/marl/modules/mixers/flex_qmix.py:73-117; inputs as
+ * mlg_refil_mixer_forward, `packed` the mlg_refil_pack_mixer() block of the parameters), plain or with imagine groups,
+ * abs or softmax mixing weights: g_qtot [R] -> d_agent_qs (the shape of agent_qs) and dparams, the 4 x 7 hypernet
+ * parameters in the flat order of mlg_refil_pack_mixer. `imagine` of the workspace query: nonzero when the call passes
+ * w_mask / i_mask. workspace and packed 16-byte aligned. */
+int64_t mlg_refil_mixer_backward_workspace_floats(const MlgRefilDims *d, int32_t R, int32_t imagine);
+int mlg_refil_mixer_backward(const MlgRefilDims *d, const float *packed, const float *agent_qs, const float *entities,
+                             const uint8_t *entity_mask, const uint8_t *w_mask, const uint8_t *i_mask,
+                             int32_t softmax_mixing_weights, const float *g_qtot, float *d_agent_qs, float *dparams,
+                             float *workspace, int32_t R, void *stream);
+/* mlg_refil_agent_backward differentiates one EntityAttentionRNNAgent.forward step
+ * (src/marl/modules/agents/entity_rnn_agent.py:32-65; inputs as mlg_refil_agent_forward, `packed` the
+ * mlg_refil_pack_agent() block of the parameters): gq [R][NA][A] / gh_out [R][NA][64] (NULL = zero upstream gradient)
+ * -> d_h_in [R][NA][64] (NULL = not wanted) and dparams, the 13 parameters in the flat order of mlg_refil_pack_agent.
+ * q of an entity-masked agent is 0, so its gq row reaches nothing; its GRU still runs, so its gh_out row reaches h_in,
+ * fc2.bias and the GRU weights. workspace, packed, h_in, gh_out and d_h_in 16-byte aligned. */
+int64_t mlg_refil_agent_backward_workspace_floats(const MlgRefilDims *d, int32_t R);
+int mlg_refil_agent_backward(const MlgRefilDims *d, const float *packed, const float *entities,
+                             const uint8_t *obs_mask, const uint8_t *entity_mask, const float *h_in, const float *gq,
+                             const float *gh_out, float *d_h_in, float *dparams, float *workspace, int32_t R,
+                             void *stream);
+
 /* REFILLearner.train (src/marl/learners/refil_learner.py:102-218) as one device pipeline: EntityMAC unrolls of the
  * plain / within / interact copies + target, FlexQMixer (flex_qmix.py:55-117) plain + imagined mixing, double-Q
  * targets, the lambda-mixed TD loss, all gradients, clip_grad_norm_ and RMSprop.

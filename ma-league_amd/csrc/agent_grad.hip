@@ -15,15 +15,6 @@ namespace {
 
 using GJobs = mlg::BJobsT<16>;
 
-__device__ __forceinline__ void st4(float* p, floatx4 v) { *reinterpret_cast<floatx4*>(p) = v; }
-
-// Column m of four consecutive weight rows k0 .. k0 + 3: the A operand of a transposed product (out = W^T . delta),
-// K slots in the order of the D layout (feature 16c + 4g + r at step (c, r)).
-__device__ __forceinline__ floatx4 ld_col4(const float* w, int64_t k0, int ld, int m) {
-    const float* p = w + k0 * ld + m;
-    return floatx4{p[0], p[ld], p[2 * (int64_t)ld], p[3 * (int64_t)ld]};
-}
-
 // ---- agent step --------------------------------------------------------------------------------------------------
 // workspace rows (all [R][...], written by the row pass, read by the wgrad jobs)
 struct AgentGradWs {
@@ -373,15 +364,8 @@ int check_qmix_dims(const MlgQMixParams* p, const char* what) {
     return 0;
 }
 
-// the wgrad launch and its fixed-order reduce over a laid-out table
-int run_jobs(const GJobs& J, int n_tasks, int64_t n_red, float* slab, float* nrm, hipStream_t s, const char* what) {
-    hipLaunchKernelGGL(mlg::wgrad_block_kernel<16>, dim3((unsigned)((n_tasks + 3) / 4)), dim3(256), 0, s, J, slab);
-    hipLaunchKernelGGL(mlg::wgrad_block_reduce_kernel<16>, dim3((unsigned)((n_red + 255) / 256)), dim3(256), 0, s, J,
-                       slab, nrm);
-    return mlg::check_launch(what);
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+using mlg::aligned16;
+using mlg::run_jobs;
 
 }  // namespace
 

@@ -34,6 +34,8 @@ inline int check_launch(const char* what) {
     return 0;
 }
 
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
 // A second stream on the device of the caller's stream `s`, for learner kernels that run beside the main chain (forked
 // and joined with the events; one stream and four events per device, created on first use, never destroyed).
 // nullptr -- the caller then runs everything on `s` -- when `s`'s device is not the current device (the side stream

@@ -882,6 +882,8 @@ __global__ void __launch_bounds__(64) refil_agent_step_kernel(RAgent L, const fl
 
 }  // namespace
 
+int check_refil_dims(const MlgRefilDims* d) { return check_dims(d); }  // for refil_grad.hip
+
 extern "C" int mlg_refil_debug_set_stamps(void* ptr) {
 #ifdef MLG_STAMPS
     unsigned long long* p = (unsigned long long*)ptr;

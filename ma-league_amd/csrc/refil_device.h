@@ -467,6 +467,34 @@ __device__ __forceinline__ void attn_bwd(const float* qkv, const float* P, int n
     }
 }
 
+// ---- FlexQMixer mixing helpers (lane = embed index e of a 32-lane half), shared by the learner and the backward ----
+__device__ __forceinline__ float sum32(float v) {  // sum over lanes 0..31 (every lane of the half gets it)
+#pragma unroll
+    for (int m = 1; m < 32; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ float max32(float v) {
+#pragma unroll
+    for (int m = 1; m < 32; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ float sgnf(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
+__device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : expm1f(x); }
+__device__ __forceinline__ float elu_d(float x) { return x > 0.f ? 1.f : expf(x); }
+
+// mixing weight transform over the embed dim (lane = e): |x| or softmax (flex_qmix.py:96-99,103-106)
+__device__ __forceinline__ float mw(float x, int softmax) {
+    if (!softmax) return fabsf(x);
+    const float m = max32(x);
+    const float ex = expf(x - m);
+    return ex / sum32(ex);
+}
+// backward of mw given the forward output y and input x
+__device__ __forceinline__ float mw_bwd(float dy, float y, float x, int softmax) {
+    if (!softmax) return dy * sgnf(x);
+    return y * (dy - sum32(y * dy));
+}
+
 // ---- GRUCell on one 16-row tile, x and h in registers (D layout), PyTorch gate order r, z, n ------------
 // brz = b_ih + b_hh for r, z (pre-summed). h updated in place.
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }

@@ -276,6 +276,8 @@ static int check_mixer_dims(const MlgRefilDims* d) {
     return 0;
 }
 
+int check_refil_mixer_dims(const MlgRefilDims* d) { return check_mixer_dims(d); }  // for refil_grad.hip
+
 extern "C" int64_t mlg_refil_packed_mixer_size(const MlgRefilDims* d) {
     if (check_mixer_dims(d)) return -1;
     return 4 * make_rhyper(d->entity_shape + (d->entity_last_action ? d->n_actions : 0)).total;

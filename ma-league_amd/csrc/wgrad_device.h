@@ -7,6 +7,16 @@
 // finish kernels turn into the clipped RMSprop step (clip_rmsprop_step).
 #pragma once
 #include "mlg_device.h"
+#include "mlg_host.h"
+
+// helpers of the stand-alone backward row passes (agent_grad.hip, refil_grad.hip)
+__device__ __forceinline__ void st4(float* p, floatx4 v) { *reinterpret_cast<floatx4*>(p) = v; }
+// Column m of four consecutive weight rows k0 .. k0 + 3: the A operand of a transposed product (out = W^T . delta),
+// K slots in the order of the D layout (feature 16c + 4g + r at step (c, r)).
+__device__ __forceinline__ floatx4 ld_col4(const float* w, int64_t k0, int ld, int m) {
+    const float* p = w + k0 * ld + m;
+    return floatx4{p[0], p[ld], p[2 * (int64_t)ld], p[3 * (int64_t)ld]};
+}
 
 namespace mlg {
 
@@ -470,6 +480,16 @@ inline int64_t layout_bjobs(BJobsT<MJ>& J, int* n_tasks, int64_t* n_red, int64_t
     *slab_part = mlg_align4(slab);
     // norm partials: one per reduce block, + 4 for a table reduced as two views (bjob_view: one more block at most)
     return mlg_align4(slab) + mlg_align4((red + 255) / 256) + 4;
+}
+
+// the wgrad launch and its fixed-order reduce over a laid-out table (host)
+template <int MJ>
+inline int run_jobs(const BJobsT<MJ>& J, int n_tasks, int64_t n_red, float* slab, float* nrm, hipStream_t s,
+                    const char* what) {
+    hipLaunchKernelGGL(wgrad_block_kernel<MJ>, dim3((unsigned)((n_tasks + 3) / 4)), dim3(256), 0, s, J, slab);
+    hipLaunchKernelGGL(wgrad_block_reduce_kernel<MJ>, dim3((unsigned)((n_red + 255) / 256)), dim3(256), 0, s, J, slab,
+                       nrm);
+    return check_launch(what);
 }
 
 // jobs [q0, q1) of a laid-out table as a table of their own (tasks renumbered from 0, slab positions kept): the

@@ -140,6 +140,12 @@ SIGNATURES = {
     "mlg_refil_packed_mixer_size": (ctypes.c_int64, [_P]),
     "mlg_refil_pack_mixer": (ctypes.c_int, [_P, _P, _P, _P]),
     "mlg_refil_mixer_forward": (ctypes.c_int, [_P] * 7 + [_I, _P, _I, _P]),
+    "mlg_refil_attention_backward_workspace_floats": (ctypes.c_int64, [_I] * 4),
+    "mlg_refil_attention_backward": (ctypes.c_int, [_P] * 7 + [_I] * 4 + [_P] * 4),
+    "mlg_refil_mixer_backward_workspace_floats": (ctypes.c_int64, [_P, _I, _I]),
+    "mlg_refil_mixer_backward": (ctypes.c_int, [_P] * 7 + [_I] + [_P] * 4 + [_I, _P]),
+    "mlg_refil_agent_backward_workspace_floats":(ctypes.c_int64, [_P, _I]),
+    "mlg_refil_agent_backward": (ctypes.c_int, [_P] * 11 + [_I, _P]),
     "mlg_refil_param_counts": (ctypes.c_int64, [_P, _P, _P]),
     "mlg_refil_workspace_floats": (ctypes.c_int64, [_P]),
     "mlg_refil_train": (ctypes.c_int, [_P, _P, _P]),

@@ -32,6 +32,22 @@ class EntityAttentionRNNAgent(AgentNetwork):
         self._packed = None
         self._packed_key = None
         self._dirty = 0
+        self._autograd = bool(getattr(args, "native_autograd", False))
+
+    def enable_autograd(self, on: bool = True):
+        """Opt in to a differentiable forward (also from ``args.native_autograd``): in grad mode, with a parameter or
+        the hidden state requiring grad, every step goes through ``maleague::entity_agent_forward`` with the live
+        parameters and ``loss.backward()`` reaches them through time (HIP backward, ``mlg_refil_agent_backward``).
+        Entities and masks get no gradient. Off by default: forward then returns plain tensors as before. Values are
+        bit-identical either way."""
+        self._autograd = bool(on)
+        return self
+
+    def wants_grad(self, *tensors) -> bool:
+        """The routing condition of the differentiable path."""
+        return (getattr(self, "_autograd", False) and torch.is_grad_enabled()
+                and (any(p.requires_grad for p in self.parameters())
+                     or any(t is not None and t.requires_grad for t in tensors)))
 
     # ---- kernel plumbing --------------------------------------------------------------------
     def dims(self) -> _native.MlgRefilDims:
@@ -103,8 +119,20 @@ class EntityAttentionRNNAgent(AgentNetwork):
         hs = torch.empty(bs, ts, na, H, device=dev)
         d = self.dims()
         P = self.packed()
-        from ...ops import refil_agent_step, struct_fields
+        from ...ops import ENTITY_GRAD_ERROR, entity_agent_forward, refil_agent_step, struct_fields
         dl = struct_fields(d)
+        if self.wants_grad(hidden_state, entities):
+            if entities.requires_grad:
+                raise _native.NativeError(ENTITY_GRAD_ERROR.format(op="entity_agent_forward"))
+            params = [p.float().contiguous() for p in self.parameters()]
+            qs, hl = [], []
+            for t in range(ts):
+                qt, h = entity_agent_forward(params, P, ent[:, t].contiguous(), om[:, t].contiguous(),
+                                             em[:, t].contiguous(), h, dl)
+                qs.append(qt)
+                hl.append(h)
+            return torch.stack(qs, dim=1), torch.stack(hl, dim=1)
+        ent, h = ent.detach(), h.detach()
         for t in range(ts):
             et, ot, mt = ent[:, t].contiguous(), om[:, t].contiguous(), em[:, t].contiguous()
             qt, ht = refil_agent_step(P, et, ot, mt, h, dl)

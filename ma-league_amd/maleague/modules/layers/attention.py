@@ -24,6 +24,21 @@ class EntityAttentionLayer(nn.Module):
         self.register_buffer("scale_factor", torch.scalar_tensor(self.head_dim, device=dev).sqrt())
         self.in_trans = nn.Linear(self.in_dim, self.embed_dim * 3, bias=False, device=dev)
         self.out_trans = nn.Linear(self.embed_dim, self.out_dim, device=dev)
+        self._autograd = bool(getattr(args, "native_autograd", False))
+
+    def enable_autograd(self, on: bool = True):
+        """Opt in to a differentiable forward (also from ``args.native_autograd``): in grad mode, with a parameter or
+        ``entities`` requiring grad, the parameters enter ``maleague::refil_attention`` live and ``loss.backward()``
+        reaches them and ``entities`` (HIP backward, ``mlg_refil_attention_backward``). Off by default: forward
+        then returns plain tensors as before. Values are bit-identical either way."""
+        self._autograd = bool(on)
+        return self
+
+    def wants_grad(self, *tensors) -> bool:
+        """The routing condition of the differentiable path."""
+        return (getattr(self, "_autograd", False) and torch.is_grad_enabled()
+                and (any(p.requires_grad for p in self.parameters())
+                     or any(t is not None and t.requires_grad for t in tensors)))
 
     def forward(self, entities, pre_mask=None, post_mask=None, ret_attn_logits=None):
         """entities [bs, ne, in]; pre_mask [bs, >=nq, >=ne] (True/1 = masked); post_mask [bs, nq] -> [bs, nq, out]."""
@@ -35,8 +50,12 @@ class EntityAttentionLayer(nn.Module):
         x = entities.float().contiguous()
         pre = pre_mask[:, :nq, :ne].to(torch.uint8).contiguous()
         post = post_mask.to(torch.uint8).contiguous()
+        from ...ops import refil_attention
+        if self.wants_grad(entities):
+            return refil_attention(self.in_trans.weight.float().contiguous(), self.out_trans.weight.float().contiguous(),
+                                   self.out_trans.bias.float().contiguous(), x, pre, post, int(self.n_heads))
+        x = x.detach()
         w_in = self.in_trans.weight.detach().float().contiguous()
         w_out = self.out_trans.weight.detach().float().contiguous()
         b_out = self.out_trans.bias.detach().float().contiguous()
-        from ...ops import refil_attention
         return refil_attention(w_in, w_out, b_out, x, pre, post, int(self.n_heads))

@@ -40,6 +40,22 @@ class FlexQMixer(nn.Module):
         self.V = AttentionHyperNet(args, mode="scalar")
         if getattr(args, "mixer_non_lin", "elu") != "elu":
             raise NotImplementedError("mixer_non_lin: only elu (the default) is built")
+        self._autograd = bool(getattr(args, "native_autograd", False))
+
+    def enable_autograd(self, on: bool = True):
+        """Opt in to a differentiable forward (also from ``args.native_autograd``): in grad mode, with a parameter or
+        ``agent_qs`` requiring grad, the parameters enter ``maleague::flex_qmix_forward`` live and
+        ``loss.backward()`` reaches them and ``agent_qs`` (HIP backward, ``mlg_refil_mixer_backward``). Entities
+        and masks get no gradient. Off by default: forward then returns plain tensors as before. Values are
+        bit-identical either way."""
+        self._autograd = bool(on)
+        return self
+
+    def wants_grad(self, *tensors) -> bool:
+        """The routing condition of the differentiable path."""
+        return (getattr(self, "_autograd", False) and torch.is_grad_enabled()
+                and (any(p.requires_grad for p in self.parameters())
+                     or any(t is not None and t.requires_grad for t in tensors)))
 
     def _dims(self):
         a = self.args
@@ -68,7 +84,15 @@ class FlexQMixer(nn.Module):
         if imagine_groups is not None:
             wm = imagine_groups[0].reshape(R, ne, ne).to(torch.uint8).contiguous()
             im = imagine_groups[1].reshape(R, ne, ne).to(torch.uint8).contiguous()
-        from ...ops import refil_mixer_forward, struct_fields
+        from ...ops import ENTITY_GRAD_ERROR, flex_qmix_forward, refil_mixer_forward, struct_fields
+        if self.wants_grad(agent_qs, entities):
+            if entities.requires_grad:
+                raise _native.NativeError(ENTITY_GRAD_ERROR.format(op="flex_qmix_forward"))
+            params = [p.float().contiguous() for p in self.parameters()]
+            out = flex_qmix_forward(params, packed, qs, ent, em, wm, im, int(bool(self.args.softmax_mixing_weights)),
+                                    struct_fields(d))
+            return out.view(bs, T, 1)
+        qs, ent = qs.detach(), ent.detach()
         out = refil_mixer_forward(packed, qs, ent, em, wm, im, int(bool(self.args.softmax_mixing_weights)),
                                   struct_fields(d))
         return out.view(bs, T, 1)

@@ -18,11 +18,17 @@ raise on host tensors like every product path.
 | ``maleague::drqn_forward``           | ``mlg_agent_forward``     | DRQNAgentNetwork.forward with the live parameters as inputs (differentiable) |
 | ``maleague::drqn_backward``          | ``mlg_agent_backward``    | its backward: one cell step (loss.backward(), q_learner.py:103) |
 | ``maleague::qmix_backward``          | ``mlg_qmix_backward``     | backward of ``qmix_forward`` w.r.t. agent_qs and the parameters |
+| ``maleague::refil_attention_backward`` | ``mlg_refil_attention_backward`` | backward of ``refil_attention`` w.r.t. x and the parameters |
+| ``maleague::flex_qmix_forward``      | ``mlg_refil_mixer_forward`` | FlexQMixer.forward with the live parameters as inputs (differentiable) |
+| ``maleague::flex_qmix_backward``     | ``mlg_refil_mixer_backward`` | its backward w.r.t. agent_qs and the parameters (refil_learner.py:102-218) |
+| ``maleague::entity_agent_forward``   | ``mlg_refil_agent_forward`` | EntityAttentionRNNAgent.forward, one step, with the live parameters as inputs (differentiable) |
+| ``maleague::entity_agent_backward``  | ``mlg_refil_agent_backward`` | its backward w.r.t. h_in and the parameters |
 
-``drqn_forward`` and ``qmix_forward`` carry autograd formulas (``torch.library.register_autograd``) that call the
-two backward ops; the backward ops have none, so double backward raises an error naming them. Gradients for
-``packed``, ``dims`` and the mixer's ``states`` are ``None`` (states that require grad are refused). The modules
-route through the differentiable ops only after ``enable_autograd()``.
+``drqn_forward``, ``qmix_forward``, ``refil_attention``, ``flex_qmix_forward`` and ``entity_agent_forward`` carry
+autograd formulas (``torch.library.register_autograd``) that call the backward ops; the backward ops have none, so
+double backward raises an error naming them. Gradients for ``packed``, ``dims``, the masks, the QMIX mixer's
+``states`` and the REFIL ops' ``entities`` are ``None`` (states / entities that require grad are refused). The
+modules route through the differentiable ops only after ``enable_autograd()``.
 
 The rollout and learner entry points (``mlg_rollout*``, ``mlg_qlearner_train``, ``mlg_refil_train``) take the
 replay ring, env state and optimizer state as in-place structs and stay direct calls of the stepper / learner
@@ -322,5 +328,206 @@ def _qmix_backward(ctx, g_qtot):
 torch.library.register_autograd("maleague::qmix_forward", _qmix_backward, setup_context=_qmix_setup)
 
 
+# ---- autograd: the REFIL layer ops ------------------------------------------------------------------------------
+ENTITY_GRAD_ERROR = ("maleague::{op}: gradients with respect to the entities are not implemented "
+                     "(pass entities that do not require grad)")
+
+
+@custom_op("maleague::refil_attention_backward", mutates_args=())
+def refil_attention_backward(w_in: Tensor, w_out: Tensor, b_out: Tensor, x: Tensor, pre_mask: Tensor,
+                             post_mask: Tensor, gy: Tensor, n_heads: int) -> Tuple[Tensor, Tensor]:
+    """Backward of ``refil_attention`` (``mlg_refil_attention_backward``): gy [bs, nq, 64] -> (dx [bs, ne, 64], dflat:
+    the gradients of in_trans.weight, out_trans.weight, out_trans.bias, flat)."""
+    bs, ne, _ = x.shape
+    nq = post_mask.shape[1]
+    w_in, w_out, b_out = _aligned(w_in), _aligned(w_out), b_out.contiguous()
+    x, gy = x.contiguous(), gy.contiguous()
+    pre_mask, post_mask = pre_mask.contiguous(), post_mask.contiguous()
+    dx = torch.empty_like(x)
+    dflat = x.new_empty(w_in.numel() + w_out.numel() + b_out.numel())
+    ws = _workspace("mlg_refil_attention_backward_workspace_floats", x, int(bs), int(ne), int(nq), int(n_heads))
+    _native.call("mlg_refil_attention_backward", _native.ptr(w_in), _native.ptr(w_out), _native.ptr(b_out),
+                 _native.ptr(x), _native.ptr(pre_mask), _native.ptr(post_mask), _native.ptr(gy), int(bs), int(ne),
+                 int(nq), int(n_heads), _native.ptr(dx), _native.ptr(dflat), _native.ptr(ws), _stream(x))
+    return dx, dflat
+
+
+@register_fake("maleague::refil_attention_backward")
+def _refil_attention_backward_fake(w_in, w_out, b_out, x, pre_mask, post_mask, gy, n_heads):
+    return torch.empty_like(x), x.new_empty(w_in.numel() + w_out.numel() + b_out.numel())
+
+
+def _attention_setup(ctx, inputs, output):
+    w_in, w_out, b_out, x, pre_mask, post_mask, n_heads = inputs
+    ctx.save_for_backward(w_in, w_out, b_out, x, pre_mask, post_mask)
+    ctx.n_heads = int(n_heads)
+
+
+def _attention_backward(ctx, gy):
+    w_in, w_out, b_out, x, pre_mask, post_mask = ctx.saved_tensors
+    dx, dflat = torch.ops.maleague.refil_attention_backward(w_in, w_out, b_out, x, pre_mask, post_mask, gy,
+                                                            ctx.n_heads)
+    need = ctx.needs_input_grad
+    dw_in, dw_out, db_out = _split(dflat, [w_in, w_out, b_out], need[:3])
+    return dw_in, dw_out, db_out, dx if need[3] else None, None, None, None
+
+
+torch.library.register_autograd("maleague::refil_attention", _attention_backward, setup_context=_attention_setup)
+
+
+@custom_op("maleague::flex_qmix_forward", mutates_args=())
+def flex_qmix_forward(params: List[Tensor], packed: Tensor, agent_qs: Tensor, entities: Tensor, entity_mask: Tensor,
+                      w_mask: Optional[Tensor], i_mask: Optional[Tensor], softmax_mixing_weights: int,
+                      dims: List[int]) -> Tensor:
+    """``refil_mixer_forward`` with the 28 live FlexQMixer parameters (named_parameters() order: hyper_w_1,
+    hyper_w_final, hyper_b_1, V; each fc1.weight, fc1.bias, attn.in_trans.weight, attn.out_trans.weight,
+    attn.out_trans.bias, fc2.weight, fc2.bias) as inputs autograd can reach. The kernel reads ``packed``, which the
+    caller guarantees is the pack of ``params``: values are bit-identical to ``refil_mixer_forward``."""
+    d = _refil_dims(dims)
+    R = agent_qs.shape[0]
+    out = agent_qs.new_empty(R)
+    _native.call("mlg_refil_mixer_forward", _native.byref(d), _native.ptr(packed), _native.ptr(agent_qs),
+                 _native.ptr(entities), _native.ptr(entity_mask), _opt(w_mask), _opt(i_mask),
+                 int(softmax_mixing_weights), _native.ptr(out), R, _stream(agent_qs))
+    return out
+
+
+@register_fake("maleague::flex_qmix_forward")
+def _flex_qmix_forward_fake(params, packed, agent_qs, entities, entity_mask, w_mask, i_mask, softmax_mixing_weights,
+                            dims):
+    return agent_qs.new_empty(agent_qs.shape[0])
+
+
+@custom_op("maleague::flex_qmix_backward", mutates_args=())
+def flex_qmix_backward(params: List[Tensor], packed: Tensor, agent_qs: Tensor, entities: Tensor, entity_mask: Tensor,
+                       w_mask: Optional[Tensor], i_mask: Optional[Tensor], g_qtot: Tensor,
+                       softmax_mixing_weights: int, dims: List[int]) -> Tuple[Tensor, Tensor]:
+    """Backward of ``flex_qmix_forward`` (``mlg_refil_mixer_backward``): g_qtot [R] -> (d_agent_qs, the shape of
+    agent_qs; dflat: the 28 parameter gradients, flat, in the order of ``params``). Entities and masks get none."""
+    d = _refil_dims(dims)
+    R = agent_qs.shape[0]
+    agent_qs, entities, entity_mask = agent_qs.contiguous(), entities.contiguous(), entity_mask.contiguous()
+    w_mask = None if w_mask is None else w_mask.contiguous()
+    i_mask = None if i_mask is None else i_mask.contiguous()
+    g_qtot = g_qtot.contiguous()
+    d_qs = torch.empty_like(agent_qs)
+    dflat = agent_qs.new_empty(sum(p.numel() for p in params))
+    ws = _workspace("mlg_refil_mixer_backward_workspace_floats", agent_qs, _native.byref(d), R,
+                    int(w_mask is not None))
+    _native.call("mlg_refil_mixer_backward", _native.byref(d), _native.ptr(packed), _native.ptr(agent_qs),
+                 _native.ptr(entities), _native.ptr(entity_mask), _native.ptr(w_mask), _native.ptr(i_mask),
+                 int(softmax_mixing_weights), _native.ptr(g_qtot), _native.ptr(d_qs), _native.ptr(dflat),
+                 _native.ptr(ws), R, _stream(agent_qs))
+    return d_qs, dflat
+
+
+@register_fake("maleague::flex_qmix_backward")
+def _flex_qmix_backward_fake(params, packed, agent_qs, entities, entity_mask, w_mask, i_mask, g_qtot,
+                             softmax_mixing_weights, dims):
+    return torch.empty_like(agent_qs), agent_qs.new_empty(sum(p.numel() for p in params))
+
+
+def _flex_qmix_setup(ctx, inputs, output):
+    params, packed, agent_qs, entities, entity_mask, w_mask, i_mask, softmax, dims = inputs
+    if entities.requires_grad:
+        raise _native.NativeError(ENTITY_GRAD_ERROR.format(op="flex_qmix_forward"))
+    ctx.imagine = w_mask is not None and i_mask is not None
+    masks = [w_mask, i_mask] if ctx.imagine else []
+    ctx.save_for_backward(*params, packed, agent_qs, entities, entity_mask, *masks)
+    ctx.n_params = len(params)
+    ctx.softmax = int(softmax)
+    ctx.dims = [int(v) for v in dims]
+
+
+def _flex_qmix_backward(ctx, g_qtot):
+    saved = list(ctx.saved_tensors)
+    params, (packed, agent_qs, entities, entity_mask), masks = (saved[:ctx.n_params],
+                                                               saved[ctx.n_params:ctx.n_params + 4],
+                                                               saved[ctx.n_params + 4:])
+    w_mask, i_mask = masks if ctx.imagine else (None, None)
+    d_qs, dflat = torch.ops.maleague.flex_qmix_backward(params, packed, agent_qs, entities, entity_mask, w_mask,
+                                                        i_mask, g_qtot, ctx.softmax, ctx.dims)
+    need = ctx.needs_input_grad
+    return _split(dflat, params, need[0]), None, d_qs if need[2] else None, None, None, None, None, None, None
+
+
+torch.library.register_autograd("maleague::flex_qmix_forward", _flex_qmix_backward, setup_context=_flex_qmix_setup)
+
+
+@custom_op("maleague::entity_agent_forward", mutates_args=())
+def entity_agent_forward(params: List[Tensor], packed: Tensor, entities: Tensor, obs_mask: Tensor,
+                         entity_mask: Tensor, h_in: Tensor, dims: List[int]) -> Tuple[Tensor, Tensor]:
+    """``refil_agent_step`` with the 13 live EntityAttentionRNNAgent parameters (named_parameters() order: fc1.weight,
+    fc1.bias, attn.in_trans.weight, attn.out_trans.weight, attn.out_trans.bias, fc2.weight, fc2.bias,
+    rnn.weight_ih, rnn.weight_hh, rnn.bias_ih, rnn.bias_hh, fc3.weight, fc3.bias) as inputs autograd can reach. The
+    kernel reads ``packed``, which the caller guarantees is the pack of ``params``: values are bit-identical to
+    ``refil_agent_step``."""
+    d = _refil_dims(dims)
+    R = entities.shape[0]
+    q = entities.new_empty(R, d.n_agents, d.n_actions)
+    h = entities.new_empty(R, d.n_agents, d.rnn_hidden_dim)
+    _native.call("mlg_refil_agent_forward", _native.byref(d), _native.ptr(packed), _native.ptr(entities),
+                 _native.ptr(obs_mask), _native.ptr(entity_mask), _native.ptr(h_in), _native.ptr(q), _native.ptr(h),
+                 int(R), _stream(entities))
+    return q, h
+
+
+@register_fake("maleague::entity_agent_forward")
+def _entity_agent_forward_fake(params, packed, entities, obs_mask, entity_mask, h_in, dims):
+    R = entities.shape[0]
+    return entities.new_empty(R, dims[0], dims[3]), entities.new_empty(R, dims[0], dims[7])
+
+
+@custom_op("maleague::entity_agent_backward", mutates_args=())
+def entity_agent_backward(params: List[Tensor], packed: Tensor, entities: Tensor, obs_mask: Tensor,
+                          entity_mask: Tensor, h_in: Tensor, gq: Optional[Tensor], gh_out: Optional[Tensor],
+                          dims: List[int]) -> Tuple[Tensor, Tensor]:
+    """Backward of one ``entity_agent_forward`` step (``mlg_refil_agent_backward``): gq [R, NA, A] / gh_out
+    [R, NA, H] (None = zero) -> (d_h_in [R, NA, H], dflat: the 13 parameter gradients, flat, in the order of
+    ``params``). Entities and masks get none."""
+    d = _refil_dims(dims)
+    R = entities.shape[0]
+    entities, obs_mask, entity_mask = entities.contiguous(), obs_mask.contiguous(), entity_mask.contiguous()
+    h_in, gh_out = _aligned(h_in), _aligned(gh_out)
+    gq = None if gq is None else gq.contiguous()
+    d_h_in = entities.new_empty(R, d.n_agents, d.rnn_hidden_dim)
+    dflat = entities.new_empty(sum(p.numel() for p in params))
+    ws = _workspace("mlg_refil_agent_backward_workspace_floats", entities, _native.byref(d), R)
+    _native.call("mlg_refil_agent_backward", _native.byref(d), _native.ptr(packed), _native.ptr(entities),
+                 _native.ptr(obs_mask), _native.ptr(entity_mask), _native.ptr(h_in), _native.ptr(gq),
+                 _native.ptr(gh_out), _native.ptr(d_h_in), _native.ptr(dflat), _native.ptr(ws), R, _stream(entities))
+    return d_h_in, dflat
+
+
+@register_fake("maleague::entity_agent_backward")
+def _entity_agent_backward_fake(params, packed, entities, obs_mask, entity_mask, h_in, gq, gh_out, dims):
+    return (entities.new_empty(entities.shape[0], dims[0], dims[7]),
+            entities.new_empty(sum(p.numel() for p in params)))
+
+
+def _entity_agent_setup(ctx, inputs, output):
+    params, packed, entities, obs_mask, entity_mask, h_in, dims = inputs
+    if entities.requires_grad:
+        raise _native.NativeError(ENTITY_GRAD_ERROR.format(op="entity_agent_forward"))
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(*params, packed, entities, obs_mask, entity_mask, h_in)
+    ctx.dims = [int(v) for v in dims]
+
+
+def _entity_agent_backward(ctx, gq, gh_out):
+    *params, packed, entities, obs_mask, entity_mask, h_in = ctx.saved_tensors
+    if gq is None and gh_out is None:
+        return [None] * len(params), None, None, None, None, None, None
+    d_h_in, dflat = torch.ops.maleague.entity_agent_backward(list(params), packed, entities, obs_mask, entity_mask,
+                                                             h_in, gq, gh_out, ctx.dims)
+    need = ctx.needs_input_grad
+    return _split(dflat, list(params), need[0]), None, None, None, None, d_h_in if need[5] else None, None
+
+
+torch.library.register_autograd("maleague::entity_agent_forward", _entity_agent_backward,
+                                setup_context=_entity_agent_setup)
+
+
 OPS = ("agent_forward", "select_actions", "qmix_forward", "refil_attention", "refil_mixer_forward",
-       "refil_agent_step", "drqn_forward", "drqn_backward", "qmix_backward")
+       "refil_agent_step", "drqn_forward", "drqn_backward", "qmix_backward", "refil_attention_backward",
+       "flex_qmix_forward", "flex_qmix_backward", "entity_agent_forward", "entity_agent_backward")
