@@ -25,6 +25,8 @@
  *   mlg_qmix_forward   QMixer.forward               src/marl/modules/mixers/qmix.py:41-59
  *   mlg_agent_backward / mlg_qmix_backward  loss.backward() through the two above, one step / one call at a time
  *                      (src/marl/learners/q_learner.py:47-52,103 with any loss)
+ *   mlg_crossplay_rollout  JointPolicyCorrelationEvaluationRun.evaluate_instances (all pairs in one launch)
+ *                      src/runs/evaluation/jpc_eval_run.py:62-89
  *   mlg_refil_*      REFIL (config 5): see the REFIL section below
  *   mlg_qlearner_*     QLearner.train               src/marl/learners/q_learner.py:34-131
  *                      + clip_grad_norm_ + RMSprop.step (q_learner.py:104-105, learner.py:25-31)
@@ -411,6 +413,57 @@ int mlg_refil_debug_set_stamps(void *ptr); /* same for mlg_refil_rollout: [grid]
  * else WIN / LOSS by won[b][0]; GAMES += B when count_games (the reference never counts GAMES). One launch. */
 int mlg_league_record_runs(const int32_t *won, const int32_t *draw, int32_t B, float *entry, int32_t count_games,
                            void *stream);
+
+/* ---- Cross-play evaluation (joint-policy correlation, src/runs/evaluation/jpc_eval_run.py:62-89): every
+ * (home policy, away policy, roster) pair of a league pool in ONE greedy rollout launch that writes no EpisodeBatch.
+ * Pair k plays E episodes; env (k, e) runs exactly as env index e with episode counter episode0 of a test-mode
+ * mlg_rollout_selfplay under specs[pair.spec] (key mlg_env_key(seed, e), counters mlg_ctr(episode0, t, ..)): every
+ * pair sees the same E spawn draws, no MlgEnvState is read or advanced, and the per-env results are bit-identical to
+ * that self-play run on the fp32 (v1) kernel. A workgroup owns 16 envs of one pair (grid n_pairs * ceil(E / 16)) and
+ * reads its two policies from packed_pool by index. The obs / avail rows of the current step stay in LDS; when the
+ * one-step obs of 16 envs does not fit (or MLG_CROSSPLAY_OBS_WORKSPACE=1) they live in `workspace`, one step per
+ * workgroup. Nothing scales with episode_limit. */
+typedef struct {
+    int32_t home, away; /* rows of packed_pool */
+    int32_t spec;       /* index into specs */
+} MlgCrossplayPair;
+
+typedef struct {
+    const float *packed_pool;           /* device [n_pool][mlg_packed_agent_size(dims)], 16-byte aligned */
+    int32_t n_pool;
+    int32_t n_pairs;
+    const MlgCrossplayPair *pairs;      /* device [n_pairs]: what the launch reads (uploaded by the caller) */
+    const MlgCrossplayPair *host_pairs; /* HOST copy of the same table: validated (indices in range), never launched */
+    const MlgEnvSpec *specs;            /* device [n_specs]: what the launch reads */
+    const MlgEnvSpec *host_specs;       /* HOST copy: each a valid two-policy-team spec; all agree on U, n_agents,
+                                           n_actions, grid, episode_limit, stochastic, policy_team and seed (team /
+                                           role / melee / agent_unit may differ: composed rosters) */
+    int32_t n_specs;
+    int32_t E;                          /* episodes per pair (any E >= 1) */
+    uint32_t episode0;
+    float *workspace;                   /* mlg_crossplay_workspace_floats() floats, 16-byte aligned, any contents */
+    int64_t workspace_floats;           /* floats `workspace` holds (checked against what the launch needs) */
+    /* per-env results [n_pairs * E], semantics of MlgRunInfo after mlg_rollout_selfplay */
+    int32_t *ep_len;
+    float *ret, *ret_away;
+    int32_t *won;                       /* [n_pairs * E][2], home first */
+    int32_t *draw;
+    /* [n_pairs][8]: games, home wins, away wins, draws, sum ret home, sum ret away, sum ep_len, 0. Win / loss / draw
+     * as mlg_league_record_runs (draw if the env says so or both / neither won). Reduced by a second kernel of the same
+     * call in a fixed order (bitwise reproducible, no atomics): lane l of 64 adds the envs e = l, l + 64, ... in
+     * ascending order starting from 0, then the 64 partial sums are added in ascending lane order starting from 0. */
+    float *summary;
+} MlgCrossplay;
+
+/* dims describe ONE side's MAC, as for mlg_rollout_selfplay. Host only; -1 (mlg_last_error()) on bad dims. */
+int64_t mlg_crossplay_workspace_floats(const MlgAgentDims *dims, int32_t n_pairs, int32_t E);
+int mlg_crossplay_rollout(const MlgAgentDims *dims, const MlgCrossplay *c, void *stream);
+
+/* Packs P flat agent parameter rows (named_parameters() order: fc1.weight, fc1.bias, gru.weight_ih, gru.weight_hh,
+ * gru.bias_ih, gru.bias_hh, fc2.weight, fc2.bias; row p at flat + p * row_stride floats) into packed_pool
+ * [P][mlg_packed_agent_size(dims)]; each row equals mlg_pack_agent() of the same parameters. One launch. */
+int mlg_pack_agent_pool(const MlgAgentDims *dims, const float *flat, int64_t row_stride, int32_t P,
+                        float *packed_pool, void *stream);
 
 const char *mlg_last_error(void);
 const char *mlg_version(void);

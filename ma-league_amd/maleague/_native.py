@@ -108,6 +108,19 @@ class MlgRefilLearnerBufs(ctypes.Structure):
                                                                            "host_rows"]]
 
 
+class MlgCrossplayPair(ctypes.Structure):
+    _fields_ = [("home", ctypes.c_int32), ("away", ctypes.c_int32), ("spec", ctypes.c_int32)]
+
+
+class MlgCrossplay(ctypes.Structure):
+    _fields_ = [("packed_pool", ctypes.c_void_p), ("n_pool", ctypes.c_int32), ("n_pairs", ctypes.c_int32),
+                ("pairs", ctypes.c_void_p), ("host_pairs", ctypes.c_void_p), ("specs", ctypes.c_void_p),
+                ("host_specs", ctypes.c_void_p), ("n_specs", ctypes.c_int32), ("E", ctypes.c_int32),
+                ("episode0", ctypes.c_uint32), ("workspace", ctypes.c_void_p), ("workspace_floats", ctypes.c_int64),
+                ("ep_len", ctypes.c_void_p), ("ret", ctypes.c_void_p), ("ret_away", ctypes.c_void_p),
+                ("won", ctypes.c_void_p), ("draw", ctypes.c_void_p), ("summary", ctypes.c_void_p)]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
 # name -> (restype, argtypes); mirrors include/maleague.h one for one.
@@ -154,6 +167,9 @@ SIGNATURES = {
     "mlg_refil_debug_set_stamps": (ctypes.c_int, [_P]),
     "mlg_league_record_runs": (ctypes.c_int, [_P, _P, _I, _P, _I, _P]),
     "mlg_refil_draw_groups": (ctypes.c_int, [_I, _I, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
+    "mlg_crossplay_workspace_floats": (ctypes.c_int64, [_P, _I, _I]),
+    "mlg_crossplay_rollout": (ctypes.c_int, [_P, _P, _P]),
+    "mlg_pack_agent_pool": (ctypes.c_int, [_P, _P, ctypes.c_int64, _I, _P, _P]),
     "mlg_last_error": (ctypes.c_char_p, []),
     "mlg_version": (ctypes.c_char_p, []),
 }

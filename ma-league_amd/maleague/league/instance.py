@@ -178,6 +178,41 @@ class LeagueInstance:
             n += 1
         return n
 
+    def evaluate_pool(self, episodes: int, pids=None):
+        """Cross-play evaluation of the league's pool (league.evaluation): every player and stored historical snapshot
+        (or ``pids``) as home against every one of them as away, greedy, ``episodes`` games per pair, each side with
+        the roster ``team_of`` gives it, all pairs of this rank in one launch. With a process group rank r plays
+        ``pairs[r::world]`` and the per-cell totals are summed over the ranks (host-staged under gloo, as
+        sync_payoff). Returns the CrossPlayResult (rows / columns in ``pids`` order) and logs
+        ``league_eval_win_rate_mean`` per home pid. The training payoff is not touched."""
+        from .evaluation import CrossPlayEvaluator, CrossPlayResult, build_pairs
+        lg = self.league
+        if lg.current is None:
+            raise RuntimeError("evaluate_pool: the league's agent pool is empty (no exchange yet)")
+        if pids is None:
+            pids = list(range(lg.n)) + sorted(h for h, _, _ in lg.historical_meta)
+        pids = [int(p) for p in pids]
+        known = set(range(lg.n)) | {h for h, _, _ in lg.historical_meta}
+        if not set(pids) <= known:
+            raise KeyError(f"evaluate_pool: pids {sorted(set(pids) - known)} are neither players nor stored snapshots")
+        # a pid is its row in [current | historical] (params_of)
+        table = build_pairs(pids, pids, self.team_of if self.teams is not None else None)
+        if getattr(self, "_evaluator", None) is None:
+            self._evaluator = CrossPlayEvaluator(self.experiment.args, lg.device)
+        mine = table[lg.rank::lg.world] if lg._dist else table
+        totals = self._evaluator.evaluate([lg.current, lg.historical], mine, episodes).totals
+        if lg._dist:
+            if lg._host_staged() or lg.device.type != "cuda":
+                dist.all_reduce(totals, op=dist.ReduceOp.SUM)
+            else:
+                dev = totals.to(lg.device)
+                dist.all_reduce(dev, op=dist.ReduceOp.SUM)
+                totals = dev.cpu()
+        result = CrossPlayResult(totals)
+        for r, pid in enumerate(pids):
+            self.logger.log_stat("league_eval_win_rate_mean", float(result.win_rate[r].mean()), pid)
+        return result
+
     def run(self, league_iterations: int, iterations_per_match: int, pretrain_iterations: int = 0):
         self.pretrain_vs_ai(pretrain_iterations)
         for _ in range(league_iterations):

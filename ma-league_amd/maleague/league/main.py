@@ -26,6 +26,10 @@ stop decision is rank 0's, broadcast before every league iteration, so the colle
 ``--league-iterations`` / ``--match-iterations`` / ``--pretrain-iterations`` bound those phases by iteration counts
 instead (tests, benchmarks).
 
+Evaluation: ``--league_eval_episodes=N`` (a config key, default 0 = off) runs ``LeagueInstance.evaluate_pool`` once
+after the last league iteration: every player and stored snapshot against every other, greedy, N games per pair in
+one launch per rank (league.evaluation); the tables land in the summary's ``league_eval``.
+
 Output: rank 0 writes ``<local_results_path>/league_<token>/league_config.json`` (arguments + every player's team,
 role and device) and ``payoff.json`` and prints the payoff per team like ``CentralWorker._print_payoff``
 (``central_worker.py:123-131``); the last stdout line is a JSON summary.
@@ -192,6 +196,7 @@ def main(argv=None) -> dict:
     player_teams = [teams[i] for i in team_idx]
     cfg["seed"] = seed + rank  # per-instance seed (experiment_process.py:102-107)
     cfg["matchmaking"] = matchmaking
+    cfg["league_eval_seed"] = seed  # one env seed for every rank's share of the evaluation pairs (equal terms)
     args = to_args(cfg)
 
     from maleague.league import DistributedLeague, LeagueInstance, PayoffEntry
@@ -240,6 +245,15 @@ def main(argv=None) -> dict:
                             "away_codes": inst.away_team.codes() if inst.away_team is not None else None})
             iters += 1
         lg.sync_payoff()
+        eval_episodes = int(cfg.get("league_eval_episodes", 0) or 0)
+        if eval_episodes > 0 and lg.current is not None:  # greedy cross-play of the whole pool, once, at the end
+            res = inst.evaluate_pool(eval_episodes)
+            summary["league_eval"] = {"episodes": eval_episodes,
+                                      "pids": list(range(world)) + sorted(h for h, _, _ in lg.historical_meta),
+                                      "games": res.games.tolist(), "win_rate": res.win_rate.tolist(),
+                                      "mean_return_home": res.mean_return_home.tolist(),
+                                      "mean_return_away": res.mean_return_away.tolist(),
+                                      "mean_ep_len": res.mean_ep_len.tolist()}
         if use_gpu:
             torch.cuda.synchronize(dev)
         summary.update({"league_iterations": iters, "t_env": int(inst.experiment.stepper.t_env),
