@@ -28,6 +28,13 @@
  *   mlg_crossplay_rollout  JointPolicyCorrelationEvaluationRun.evaluate_instances (all pairs in one launch)
  *                      src/runs/evaluation/jpc_eval_run.py:62-89
  *   mlg_refil_*      REFIL (config 5): see the REFIL section below
+ *   mlg_policy_probs   MultiAgentController._softmax src/marl/controllers/multi_agent_controller.py:78-99
+ *   mlg_select_multinomial MultinomialActionSelector.select src/marl/components/action_selectors.py:11-32
+ *   mlg_rollout_policy ParallelStepper.run with a pi_logits MAC (the two above inside mlg_rollout's run)
+ *   mlg_coma_critic_train COMALearner._train_critic  src/marl/learners/coma_learner.py:10-21,121-169
+ *                      + COMACritic                  src/marl/modules/critics/coma.py:22-73
+ *   mlg_coma_target_update the target-critic update  src/marl/learners/coma_learner.py:104-106
+ *   mlg_coma_policy_loss the COMA actor loss         src/marl/learners/coma_learner.py:75-96
  *   mlg_qlearner_*     QLearner.train               src/marl/learners/q_learner.py:34-131
  *                      + clip_grad_norm_ + RMSprop.step (q_learner.py:104-105, learner.py:25-31)
  */
@@ -464,6 +471,91 @@ int mlg_crossplay_rollout(const MlgAgentDims *dims, const MlgCrossplay *c, void 
  * [P][mlg_packed_agent_size(dims)]; each row equals mlg_pack_agent() of the same parameters. One launch. */
 int mlg_pack_agent_pool(const MlgAgentDims *dims, const float *flat, int64_t row_stride, int32_t P,
                         float *packed_pool, void *stream);
+
+/* ---- COMA (algs/coma.yaml): policy output, multinomial selection, critic training, actor loss ------------- */
+/* MultiAgentController._softmax (multi_agent_controller.py:78-99) over R rows of logits [R][A] with avail [R][A]:
+ * with mask_before_softmax unavailable logits count as -1e10 in a max-subtracted fp32 softmax; unless test_mode the
+ * epsilon floor (1 - eps) p + eps / K follows, K = the row's available actions with masking, else A, and with masking
+ * unavailable entries are then 0 (a row with no available action is all 0, never NaN; in test mode the reference
+ * zeroes nothing and such a row is the softmax's 1 / A). The backward gives d logits from g_probs [R][A]; the masked
+ * assignments pass no gradient. */
+int mlg_policy_probs(const float *logits, const int32_t *avail, int32_t R, int32_t A, float epsilon,
+                     int32_t mask_before_softmax, int32_t test_mode, float *probs, void *stream);
+int mlg_policy_probs_backward(const float *logits, const int32_t *avail, const float *g_probs, int32_t R, int32_t A,
+                              float epsilon, int32_t mask_before_softmax, int32_t test_mode, float *d_logits,
+                              void *stream);
+
+/* MultinomialActionSelector.select (action_selectors.py:11-32) with this project's counter RNG instead of torch's
+ * generator: m_k = probs_k where available, else 0; total = the fp32 sum of m_k in ascending k;
+ * u = mlg_u01(mlg_rng(keys[r / n_agents], mlg_ctr(episodes[r / n_agents], t, MLG_PURPOSE_POLICY = 5, r % n_agents)));
+ * the action is the first available k whose running fp32 sum exceeds u * total, else the last available k. greedy
+ * (test_mode and test_greedy): the first available k with the largest m_k. A row with no available action gets 0. */
+int mlg_select_multinomial(const float *probs, const int32_t *avail, int32_t R, int32_t A, int32_t n_agents,
+                           const uint64_t *keys, const uint32_t *episodes, int32_t t, int32_t greedy,
+                           int64_t *actions, void *stream);
+
+/* One full ParallelStepper.run with a pi_logits MAC (BasicMAC.select_actions, basic_controller.py:29-50, with
+ * agent_output_type "pi_logits" and the multinomial selector): mlg_rollout's arguments, run semantics, ring and
+ * full-write modes and MlgRunInfo, on the generic fp32 rollout kernel (H in {32, 64, 128}); per step the agent's
+ * outputs go through the mlg_policy_probs rule (epsilon is the selector's, test_mode drops the floor) and the action
+ * is drawn by the mlg_select_multinomial rule with key mlg_env_key(seed, env), the env's episode counter, the step t
+ * and the agent index; test_mode with test_greedy takes the first-index argmax. One launch. The sums of a row add each
+ * lane's four actions first, then the four lanes in ascending order, then the 16-action tiles in ascending order (the
+ * stand-alone entry points add in ascending k): probabilities agree to rounding, not bitwise. */
+int mlg_rollout_policy(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgentDims *dims, const float *packed,
+                       MlgBatch *batch, MlgRunInfo *info, float epsilon, int32_t test_mode,
+                       int32_t mask_before_softmax, int32_t test_greedy, void *stream);
+
+/* The COMA actor loss (coma_learner.py:75-96), forward and d loss / d pi in one launch. rows = B (T - 1) mask entries,
+ * pi / avail / q_vals [rows][N][A], actions [rows][N], mask [rows]: pi is zeroed where unavailable and renormalised,
+ * baseline = sum pi q, advantage = q_taken - baseline (a constant for the gradient), pi_taken = 1 where mask == 0,
+ * loss = -sum(log pi_taken * advantage * mask) / (N sum mask). out[4] = loss, advantage_mean, the masked mean of max
+ * pi, N sum mask. d_pi [rows][N][A]; an all-unavailable (padding) row has pi = 0 and zero gradient. One workgroup,
+ * every sum in a fixed order. */
+int mlg_coma_policy_loss(const float *pi, const int32_t *avail, const int64_t *actions, const float *q_vals,
+                         const float *mask, int32_t rows, int32_t N, int32_t A, float *out, float *d_pi,
+                         void *stream);
+
+/* COMALearner._train_critic (coma_learner.py:121-169) with COMACritic (critics/coma.py:22-73) and
+ * build_td_lambda_targets (coma_learner.py:10-21) as one queued chain of launches without a host wait.
+ * Flat critic parameters in named_parameters() order: fc1.weight [128][D], fc1.bias, fc2.weight [128][128], fc2.bias,
+ * fc3.weight [A][128], fc3.bias; D = S + d_obs + 2 N A + N. Input row (b, t, n), built in the kernels from the batch
+ * (rows honoured): [state | obs_n | actions_onehot at t with agent n's block zeroed | actions_onehot at t - 1 (zeros
+ * at t = 0) | eye row n]. One call: the target critic over all T steps with the taken targets gathered; the TD(lambda)
+ * recursion; then for t = T - 2 .. 0 one optimizer step (forward at t with the current parameters -> q_vals[:, t],
+ * masked MSE over mask_t expanded to the agents, backward, clip_grad_norm_, RMSprop with lr; no momentum, not
+ * centered), skipped on the device when sum_b mask[b, t] == 0 (q_vals[:, t] = 0). Three launches per step; every
+ * reduction in a fixed order without float atomics: the same inputs give the same bits.
+ * Supported: hidden 128, N <= 32, A <= 96; anything else is refused, mlg_last_error() names the key. */
+typedef struct {
+    int32_t B, T, N, A, d_obs, S, hidden;
+    float lr, optim_eps, grad_norm_clip; /* critic_lr, RMSprop eps, clip */
+    /* doubles, as the reference holds them: lambda gamma, (1 - lambda) gamma and 1 - alpha are formed in double and
+     * rounded to fp32 once, as torch rounds the Python floats it is handed (1.f - 0.99f is not fp32(0.01)) */
+    double gamma, td_lambda, optim_alpha;
+} MlgComaCfg;
+
+typedef struct {
+    MlgBatch batch;             /* B episodes, T timesteps used (batch.T1 = stride) */
+    float *params;              /* [n] updated in place */
+    float *grads;               /* [n] out: the clipped gradients of the last taken step */
+    float *square_avg;          /* [n] RMSprop state */
+    const float *target_params; /* [n] the target critic */
+    float *workspace;           /* mlg_coma_workspace_floats() floats, any contents */
+    float *q_vals;              /* [B][T-1][N][A] out */
+    float *targets;             /* [B][T-1][N] out: the TD(lambda) targets */
+    float *stats;               /* [6] out: sums over the taken steps of loss, grad_norm, td_error_abs, q_taken_mean,
+                                   target_mean; the number of taken steps */
+    int64_t *counters;          /* [2] critic_training_steps (+= taken steps), last_target_update_step */
+} MlgComaBufs;
+
+int64_t mlg_coma_param_count(const MlgComaCfg *c);     /* host only; -1 (mlg_last_error()) on unsupported dims */
+int64_t mlg_coma_workspace_floats(const MlgComaCfg *c); /* host only; -1 likewise */
+int mlg_coma_critic_train(const MlgComaCfg *c, const MlgComaBufs *b, void *stream);
+/* coma_learner.py:104-106 on the device: when (counters[0] - counters[1]) / interval >= 1, target_params = params and
+ * counters[1] = counters[0]. Two launches, no host sync. */
+int mlg_coma_target_update(const float *params, float *target_params, int64_t n, int64_t *counters, int32_t interval,
+                           void *stream);
 
 const char *mlg_last_error(void);
 const char *mlg_version(void);

@@ -121,6 +121,18 @@ class MlgCrossplay(ctypes.Structure):
                 ("won", ctypes.c_void_p), ("draw", ctypes.c_void_p), ("summary", ctypes.c_void_p)]
 
 
+class MlgComaCfg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ["B", "T", "N", "A", "d_obs", "S", "hidden"]] + \
+               [(n, ctypes.c_float) for n in ["lr", "optim_eps", "grad_norm_clip"]] + \
+               [(n, ctypes.c_double) for n in ["gamma", "td_lambda", "optim_alpha"]]
+
+
+class MlgComaBufs(ctypes.Structure):
+    _fields_ = [("batch", MlgBatch)] + [(n, ctypes.c_void_p) for n in ["params", "grads", "square_avg",
+                                                                      "target_params", "workspace", "q_vals",
+                                                                      "targets", "stats", "counters"]]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
 # name -> (restype, argtypes); mirrors include/maleague.h one for one.
@@ -170,6 +182,15 @@ SIGNATURES = {
     "mlg_crossplay_workspace_floats": (ctypes.c_int64, [_P, _I, _I]),
     "mlg_crossplay_rollout": (ctypes.c_int, [_P, _P, _P]),
     "mlg_pack_agent_pool": (ctypes.c_int, [_P, _P, ctypes.c_int64, _I, _P, _P]),
+    "mlg_policy_probs": (ctypes.c_int, [_P, _P, _I, _I, ctypes.c_float, _I, _I, _P, _P]),
+    "mlg_policy_probs_backward": (ctypes.c_int, [_P, _P, _P, _I, _I, ctypes.c_float, _I, _I, _P, _P]),
+    "mlg_select_multinomial": (ctypes.c_int, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+    "mlg_rollout_policy": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _I, _I, _P]),
+    "mlg_coma_policy_loss": (ctypes.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "mlg_coma_param_count": (ctypes.c_int64, [_P]),
+    "mlg_coma_workspace_floats": (ctypes.c_int64, [_P]),
+    "mlg_coma_critic_train": (ctypes.c_int, [_P, _P, _P]),
+    "mlg_coma_target_update": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _I, _P]),
     "mlg_last_error": (ctypes.c_char_p, []),
     "mlg_version": (ctypes.c_char_p, []),
 }

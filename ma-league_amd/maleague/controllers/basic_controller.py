@@ -46,8 +46,8 @@ class BasicMAC(MultiAgentController):
         return self.action_selector.select(agent_outs[bs], avail_actions[bs], t_env, test_mode)
 
     def forward(self, ep_batch, t, test_mode=False):
-        if self.agent_output_type != "q":
-            raise NotImplementedError("pi_logits output (COMA) is out of scope for this build")
+        if self.agent_output_type not in ("q", "pi_logits"):
+            raise NotImplementedError(f"agent_output_type={self.agent_output_type!r} is not supported (q, pi_logits)")
         if self.hidden_states is None:
             raise HiddenStateNotInitialized()
         B, N, H = ep_batch.batch_size, self.n_agents, self.args.rnn_hidden_dim
@@ -55,7 +55,23 @@ class BasicMAC(MultiAgentController):
             # differentiable path: hidden_states carries the graph across steps
             q, h = self.agent(self._build_inputs(ep_batch, t), self.hidden_states)
             self.hidden_states = h
-            return q.view(B, N, self.n_actions)
+            q = q.view(B, N, self.n_actions)
+            return self._softmax(q, ep_batch, t, test_mode) if self.agent_output_type == "pi_logits" else q
+        if self.agent_output_type == "pi_logits":
+            with torch.no_grad():
+                return self._softmax(self._fused_forward(ep_batch, t), ep_batch, t, test_mode)
+        return self._fused_forward(ep_batch, t)
+
+    def _softmax(self, logits, ep_batch, t, test_mode):
+        """MultiAgentController._softmax (multi_agent_controller.py:78-99) as one HIP op: probabilities [B, N, A];
+        epsilon is the action selector's, as in the reference."""
+        avail = ep_batch["avail_actions"][:, t].to(torch.int32)
+        return torch.ops.maleague.policy_probs(logits, avail, float(self.action_selector.epsilon),
+                                               int(bool(getattr(self.args, "mask_before_softmax", True))),
+                                               int(bool(test_mode)))
+
+    def _fused_forward(self, ep_batch, t):
+        B, N, H = ep_batch.batch_size, self.n_agents, self.args.rnn_hidden_dim
         mb, keep = mlg_batch(ep_batch, required=("obs", "actions_onehot"))
         h_in = self.hidden_states.reshape(B * N, H).float().contiguous()
         q = torch.empty(B, N, self.n_actions, device=h_in.device)

@@ -142,6 +142,9 @@ class CrossPlayEvaluator:
     def __init__(self, args, device, episodes_per_launch: Optional[int] = None):
         self.args = args
         self.device = torch.device(device)
+        if getattr(args, "agent_output_type", "q") != "q":
+            raise NotImplementedError("cross-play evaluation plays greedy over Q values: agent_output_type="
+                                      f"{args.agent_output_type!r} is not supported (COMA in the league is out of scope)")
         self.E = int(episodes_per_launch or getattr(args, "league_eval_batch", 512))
         if self.E < 1:
             raise ValueError(f"episodes_per_launch={self.E}")

@@ -1,9 +1,10 @@
-"""Learner registry (reference: src/marl/learners/__init__.py:5-9; COMA/SFS are out of scope; "refil" =
+"""Learner registry (reference: src/marl/learners/__init__.py:5-9; SFS is out of scope; "refil" =
 REFILLearner, unregistered in the reference; "q_learner" is the key the reference's own algs/iql.yaml
 names, which its registry lacks: an alias of "q")."""
+from .coma_learner import COMALearner
 from .q_learner import Learner, QLearner
 from .refil_learner import REFILLearner
 
-REGISTRY = {"q": QLearner, "q_learner": QLearner, "refil": REFILLearner}
+REGISTRY = {"q": QLearner, "q_learner": QLearner, "refil": REFILLearner, "coma": COMALearner}
 
-__all__ = ["Learner", "QLearner", "REFILLearner", "REGISTRY"]
+__all__ = ["COMALearner", "Learner", "QLearner", "REFILLearner", "REGISTRY"]

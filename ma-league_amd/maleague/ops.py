@@ -23,6 +23,10 @@ raise on host tensors like every product path.
 | ``maleague::flex_qmix_backward``     | ``mlg_refil_mixer_backward`` | its backward w.r.t. agent_qs and the parameters (refil_learner.py:102-218) |
 | ``maleague::entity_agent_forward``   | ``mlg_refil_agent_forward`` | EntityAttentionRNNAgent.forward, one step, with the live parameters as inputs (differentiable) |
 | ``maleague::entity_agent_backward``  | ``mlg_refil_agent_backward`` | its backward w.r.t. h_in and the parameters |
+| ``maleague::policy_probs``           | ``mlg_policy_probs``      | MultiAgentController._softmax (multi_agent_controller.py:78-99), differentiable |
+| ``maleague::policy_probs_backward``  | ``mlg_policy_probs_backward`` | its backward w.r.t. the logits               |
+| ``maleague::select_multinomial``     | ``mlg_select_multinomial`` | MultinomialActionSelector.select (action_selectors.py:11-32), counter RNG |
+| ``maleague::coma_policy_loss``       | ``mlg_coma_policy_loss``  | the COMA actor loss (coma_learner.py:75-96), forward and d pi in one launch |
 
 ``drqn_forward``, ``qmix_forward``, ``refil_attention``, ``flex_qmix_forward`` and ``entity_agent_forward`` carry
 autograd formulas (``torch.library.register_autograd``) that call the backward ops; the backward ops have none, so
@@ -528,6 +532,109 @@ torch.library.register_autograd("maleague::entity_agent_forward", _entity_agent_
                                 setup_context=_entity_agent_setup)
 
 
+# ---- COMA: the policy output, multinomial selection and the actor loss -------------------------------------------
+@custom_op("maleague::policy_probs", mutates_args=())
+def policy_probs(logits: Tensor, avail: Tensor, epsilon: float, mask_before_softmax: int, test_mode: int) -> Tensor:
+    """logits [..., A] f32, avail [..., A] int32 -> probabilities [..., A] (``mlg_policy_probs``)."""
+    A = logits.shape[-1]
+    x, av = logits.contiguous(), avail.contiguous()
+    out = torch.empty_like(x)
+    _native.call("mlg_policy_probs", _native.ptr(x), _native.ptr(av), x.numel() // A, A, float(epsilon),
+                 int(mask_before_softmax), int(test_mode), _native.ptr(out), _stream(x))
+    return out
+
+
+@register_fake("maleague::policy_probs")
+def _policy_probs_fake(logits, avail, epsilon, mask_before_softmax, test_mode):
+    return torch.empty_like(logits, memory_format=torch.contiguous_format)
+
+
+@custom_op("maleague::policy_probs_backward", mutates_args=())
+def policy_probs_backward(logits: Tensor, avail: Tensor, g_probs: Tensor, epsilon: float, mask_before_softmax: int,
+                          test_mode: int) -> Tensor:
+    """Backward of ``policy_probs`` (``mlg_policy_probs_backward``): g_probs [..., A] -> d logits [..., A]."""
+    A = logits.shape[-1]
+    x, av, g = logits.contiguous(), avail.contiguous(), g_probs.contiguous()
+    out = torch.empty_like(x)
+    _native.call("mlg_policy_probs_backward", _native.ptr(x), _native.ptr(av), _native.ptr(g), x.numel() // A, A,
+                 float(epsilon), int(mask_before_softmax), int(test_mode), _native.ptr(out), _stream(x))
+    return out
+
+
+@register_fake("maleague::policy_probs_backward")
+def _policy_probs_backward_fake(logits, avail, g_probs, epsilon, mask_before_softmax, test_mode):
+    return torch.empty_like(logits, memory_format=torch.contiguous_format)
+
+
+def _policy_probs_setup(ctx, inputs, output):
+    logits, avail, epsilon, mask, test_mode = inputs
+    ctx.save_for_backward(logits, avail)
+    ctx.cfg = (float(epsilon), int(mask), int(test_mode))
+
+
+def _policy_probs_backward(ctx, g):
+    logits, avail = ctx.saved_tensors
+    return torch.ops.maleague.policy_probs_backward(logits, avail, g, *ctx.cfg), None, None, None, None
+
+
+torch.library.register_autograd("maleague::policy_probs", _policy_probs_backward, setup_context=_policy_probs_setup)
+
+
+@custom_op("maleague::select_multinomial", mutates_args=())
+def select_multinomial(probs: Tensor, avail: Tensor, keys: Tensor, episodes: Tensor, t: int, greedy: int) -> Tensor:
+    """probs [B, N, A] f32, avail [B, N, A] int32, keys [B] int64, episodes [B] int32 -> actions [B, N] int64
+    (``mlg_select_multinomial``: the counter-RNG draw of DESIGN.md §3.7, purpose 5)."""
+    B, N, A = probs.shape
+    actions = torch.empty(B, N, dtype=torch.int64, device=probs.device)
+    _native.call("mlg_select_multinomial", _native.ptr(probs.contiguous()), _native.ptr(avail.contiguous()), B * N, A,
+                 N, _native.ptr(keys), _native.ptr(episodes), int(t), int(greedy), _native.ptr(actions),
+                 _stream(probs))
+    return actions
+
+
+@register_fake("maleague::select_multinomial")
+def _select_multinomial_fake(probs, avail, keys, episodes, t, greedy):
+    return probs.new_empty(probs.shape[0], probs.shape[1], dtype=torch.int64)
+
+
+@custom_op("maleague::coma_policy_loss", mutates_args=())
+def coma_policy_loss(pi: Tensor, avail: Tensor, actions: Tensor, q_vals: Tensor, mask: Tensor
+                     ) -> Tuple[Tensor, Tensor]:
+    """The COMA actor loss (coma_learner.py:75-96; ``mlg_coma_policy_loss``): pi / avail (int32) / q_vals
+    [B, T-1, N, A], actions [B, T-1, N, 1] int64, mask [B, T-1] or [B, T-1, 1] f32 -> (stats [4] = loss,
+    advantage_mean, the masked mean of pi.max, the sum of the expanded mask; d loss / d pi [B, T-1, N, A])."""
+    B, Tm, N, A = pi.shape
+    p, av, q = pi.contiguous(), avail.contiguous(), q_vals.contiguous()
+    ac, mk = actions.contiguous(), mask.contiguous()
+    stats = p.new_empty(4)
+    d_pi = torch.empty_like(p)
+    _native.call("mlg_coma_policy_loss", _native.ptr(p), _native.ptr(av), _native.ptr(ac), _native.ptr(q),
+                 _native.ptr(mk), B * Tm, N, A, _native.ptr(stats), _native.ptr(d_pi), _stream(p))
+    return stats, d_pi
+
+
+@register_fake("maleague::coma_policy_loss")
+def _coma_policy_loss_fake(pi, avail, actions, q_vals, mask):
+    return pi.new_empty(4), torch.empty_like(pi, memory_format=torch.contiguous_format)
+
+
+def _coma_policy_loss_setup(ctx, inputs, output):
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(output[1])
+
+
+def _coma_policy_loss_backward(ctx, g_stats, g_dpi):
+    (d_pi,) = ctx.saved_tensors
+    # only the loss (stats[0]) depends on pi in the reference: the advantage is detached and the other entries are logs
+    g = None if g_stats is None else g_stats[0] * d_pi
+    return g, None, None, None, None
+
+
+torch.library.register_autograd("maleague::coma_policy_loss", _coma_policy_loss_backward,
+                                setup_context=_coma_policy_loss_setup)
+
+
 OPS = ("agent_forward", "select_actions", "qmix_forward", "refil_attention", "refil_mixer_forward",
        "refil_agent_step", "drqn_forward", "drqn_backward", "qmix_backward", "refil_attention_backward",
-       "flex_qmix_forward", "flex_qmix_backward", "entity_agent_forward", "entity_agent_backward")
+       "flex_qmix_forward", "flex_qmix_backward", "entity_agent_forward", "entity_agent_backward",
+       "policy_probs", "policy_probs_backward", "select_multinomial", "coma_policy_loss")

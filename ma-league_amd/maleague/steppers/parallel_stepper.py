@@ -175,6 +175,15 @@ class ParallelStepper(EnvStepper):
     def _rollout(self, mb, run_info, epsilon, test_mode):
         agent = self.home_mac.agent
         st = self.envs.to_c()
+        if getattr(self.home_mac, "agent_output_type", "q") == "pi_logits":
+            # COMA: the softmax / epsilon-floor policy and the multinomial draw run inside the rollout kernel
+            sel = self.home_mac.action_selector
+            _native.call("mlg_rollout_policy", _native.byref(self._cspec), _native.byref(st),
+                         _native.byref(agent.dims()), _native.ptr(agent.packed()), _native.byref(mb),
+                         _native.byref(run_info), float(epsilon), int(bool(test_mode)),
+                         int(bool(getattr(self.home_mac.args, "mask_before_softmax", True))),
+                         int(bool(getattr(sel, "test_greedy", True))), _native.stream_ptr(self.device))
+            return
         _native.call("mlg_rollout", _native.byref(self._cspec), _native.byref(st), _native.byref(agent.dims()),
                      _native.ptr(agent.packed()), _native.byref(mb), _native.byref(run_info), float(epsilon),
                      int(bool(test_mode)), _native.stream_ptr(self.device))

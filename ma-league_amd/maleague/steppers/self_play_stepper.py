@@ -35,6 +35,11 @@ class SelfPlayParallelStepper(ParallelStepper):
     def initialize(self, scheme, groups, preprocess, home_mac, away_mac=None):
         if away_mac is None:
             raise ValueError("self-play needs an away MAC (initialize(..., home_mac, away_mac))")
+        for side, mac in (("home", home_mac), ("away", away_mac)):
+            if getattr(mac, "agent_output_type", "q") != "q":
+                raise NotImplementedError(f"self-play rollouts select epsilon-greedy over Q values: the {side} MAC's "
+                                          f"agent_output_type={mac.agent_output_type!r} is not supported (COMA in "
+                                          "self-play is out of scope)")
         ParallelStepper.initialize(self, scheme, groups, preprocess, home_mac)
         self.away_mac = away_mac
         self._away_buf = None

@@ -81,6 +81,15 @@ BUILTIN = {
         "epsilon_anneal_time": 50000, "runner": "episode", "buffer_size": 5000, "target_update_interval": 200,
         "agent_output_type": "q", "learner": "q_learner", "double_q": True, "mixer": None, "name": "iql",
     },
+    # src/config/algs/coma.yaml (env_args.state_last_action passes through unused: the critic adds the last actions)
+    "algs/coma": {
+        "action_selector": "multinomial", "epsilon_start": 0.5, "epsilon_finish": 0.01,
+        "epsilon_anneal_time": 100000, "mask_before_softmax": False, "runner": "parallel", "buffer_size": 8,
+        "batch_size_run": 8, "batch_size": 8, "env_args": {"state_last_action": False},
+        "target_update_interval": 200, "lr": 0.0005, "critic_lr": 0.0005, "td_lambda": 0.8,
+        "agent_output_type": "pi_logits", "learner": "coma", "critic_q_fn": "coma", "critic_baseline_fn": "coma",
+        "critic_train_mode": "seq", "critic_train_reps": 1, "q_nstep": 0, "name": "coma",
+    },
 }
 
 
