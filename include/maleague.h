@@ -378,7 +378,12 @@ int mlg_refil_agent_backward(const MlgRefilDims *d, const float *packed, const f
 typedef struct {
     int32_t B, T, n_agents, n_entities, entity_shape, n_actions, entity_last_action;
     int32_t attn_embed_dim, attn_n_heads, rnn_hidden_dim, hypernet_embed, mixing_embed_dim;
-    int32_t double_q, softmax_mixing_weights, imagine;
+    int32_t double_q, softmax_mixing_weights;
+    int32_t imagine; /* 1: imagine_entity_attend_rnn (REFIL: plain + within + interact copies, the lambda-mixed loss);
+                        0: entity_attend_rnn (one online copy, the masked TD loss alone; groupA may be NULL and is
+                        never read, stats[1] = 0) */
+    int32_t mixer;   /* 0: flex_qmix; 1: vdn (imagine = 0 only): q_tot = sum of the chosen Q over the agents, the
+                        flat parameters are the agent alone (n_mixer = 0) and no hypernet kernel runs */
     float gamma, lmbda, lr, optim_alpha, optim_eps, grad_norm_clip;
 } MlgRefilLearnerCfg;
 

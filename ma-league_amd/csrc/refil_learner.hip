@@ -20,6 +20,11 @@
 //   finish      clip_grad_norm_ (10), RMSprop, stats (:211-231)
 // Agent rows: r = (c * B + b) * NA + n for copy c (0 plain, 1 within, 2 interact); target rows r = b * NA + n.
 // Items i = b * T + t. Mixer items use t < T - 1 (the other kernels write zeros for t = T - 1).
+// The attention baselines (cfg.imagine = 0: the plain entity agent, refil_learner.py:107-110, :152-155) run the same
+// launches with one online copy (NC = 1, a template parameter of the per-item kernels; rows r = b * NA + n, no group
+// mask, hyper_w_1 with the plain mask only) and mix_td1 in place of mix_td (the masked TD loss, no lambda). With
+// cfg.mixer = 1 (VDNMixer) the flat parameters are the agent alone and no hypernet pack, split, forward, backward
+// or wgrad launch runs.
 #include "mlg_host.h"
 #include "batch_mask_device.h"
 #include "gru4_device.h"
@@ -36,6 +41,7 @@ using RJobs = mlg::BJobsT<MJ>;
 struct RCfg {
     int B, T, T1, NA, NE, ED, D0, K1, A, Ap, I, Ron, Rtg;
     int double_q, softmax;
+    int NC, vdn;  // online agent copies (3: the imagine agent, 1: the plain agent); 1: VDNMixer, no hypernets
     float gamma, lmbda;
 };
 
@@ -59,7 +65,10 @@ struct Plan {
     int64_t n_agent, n_mixer;
 };
 
-__host__ __device__ inline int nvar(int k) { return k == 0 ? 3 : 1; }
+// attention variants of hypernet k: hyper_w_1 runs once per online agent copy (plain | W | I masks)
+template <int NC>
+__host__ __device__ inline int nvar(int k) { return k == 0 ? NC : 1; }
+inline int nvar_of(int k, int nc) { return k == 0 ? nc : 1; }
 
 int check_cfg(const MlgRefilLearnerCfg* c) {
     MLG_REQUIRE(c != nullptr, "null refil learner cfg");
@@ -72,12 +81,19 @@ int check_cfg(const MlgRefilLearnerCfg* c) {
     const int D0 = c->entity_shape + (c->entity_last_action ? c->n_actions : 0);
     MLG_REQUIRE(D0 <= KMAX && c->n_actions >= 1 && c->n_actions <= 32, "refil learner: entity input %d / actions %d",
                 D0, c->n_actions);
-    MLG_REQUIRE(c->imagine == 1, "refil learner: the imagine agent (REFIL) is the built path");
+    MLG_REQUIRE(c->imagine == 0 || c->imagine == 1,
+                "refil learner: imagine=%d (0 = entity_attend_rnn, 1 = imagine_entity_attend_rnn)", c->imagine);
+    MLG_REQUIRE(c->mixer == 0 || c->mixer == 1,
+                "refil learner: mixer=%d (0 = flex_qmix, 1 = vdn; lin_flex_qmix, qmix and no mixer are not built)",
+                c->mixer);
+    MLG_REQUIRE(!(c->imagine == 1 && c->mixer == 1),
+                "refil learner: imagine=1 with mixer=1 (vdn): VDNMixer takes no imagine groups");
     // the recurrences store hs / gates / dGI / dGH through buffer resources (32-bit byte offsets): the largest of
-    // them, (T + 1) x 3B*NA rows x 3*EMB floats, must stay under 2 GiB or its stores would be silently dropped
-    MLG_REQUIRE((int64_t)(c->T + 1) * 3 * c->B * c->n_agents * 3 * EMB < (int64_t)1 << 29,
-                "refil learner: (T+1)*3B*NA*3*EMB=%lld floats exceeds the 2 GB buffer-store range",
-                (long long)(c->T + 1) * 3 * c->B * c->n_agents * 3 * EMB);
+    // them, (T + 1) x copies*B*NA rows x 3*EMB floats, must stay under 2 GiB or its stores would be silently dropped
+    const int nc = c->imagine ? 3 : 1;
+    MLG_REQUIRE((int64_t)(c->T + 1) * nc * c->B * c->n_agents * 3 * EMB < (int64_t)1 << 29,
+                "refil learner: (T+1)*%dB*NA*3*EMB=%lld floats exceeds the 2 GB buffer-store range", nc,
+                (long long)(c->T + 1) * nc * c->B * c->n_agents * 3 * EMB);
     return 0;
 }
 
@@ -95,37 +111,40 @@ Plan make_plan(const MlgRefilLearnerCfg* cfg, int T1) {
     c.K1 = (c.D0 + 15) / 16 * 16;
     c.Ap = (c.A + 15) / 16 * 16;
     c.I = c.B * c.T;
-    c.Ron = 3 * c.B * c.NA;
+    c.NC = cfg->imagine ? 3 : 1;
+    c.vdn = cfg->mixer == 1;
+    c.Ron = c.NC * c.B * c.NA;
     c.Rtg = c.B * c.NA;
     c.double_q = cfg->double_q;
     c.softmax = cfg->softmax_mixing_weights;
     c.gamma = cfg->gamma;
-    c.lmbda = cfg->lmbda;
+    c.lmbda = cfg->imagine ? cfg->lmbda : 0.f;  // the plain agent's loss has no imagined term
     p.La = make_ragent(c.D0, c.A);
     p.Lh = make_rhyper(c.D0);
     p.n_agent = p.La.c_total;
-    p.n_mixer = 4 * p.Lh.c_total;
+    p.n_mixer = c.vdn ? 0 : 4 * p.Lh.c_total;
     WsR& w = p.w;
     int64_t o = 0;
     auto take = [&](int64_t n) { int64_t r = o; o += mlg_align4(n); return r; };
     const int64_t I = c.I, T = c.T, Ron = c.Ron, Rtg = c.Rtg;
     w.pa_on = take(p.La.total);
     w.pa_tg = take(p.La.total);
-    for (int k = 0; k < 4; ++k) w.ph_on[k] = take(p.Lh.total);
-    for (int k = 0; k < 4; ++k) w.ph_tg[k] = take(p.Lh.total);
+    const int64_t hy = c.vdn ? 0 : 1;  // VDN: no hypernet block is allocated
+    for (int k = 0; k < 4; ++k) w.ph_on[k] = take(hy * p.Lh.total);
+    for (int k = 0; k < 4; ++k) w.ph_tg[k] = take(hy * p.Lh.total);
     w.a_woutT = take(EMB * EMB);
     w.a_w2T = take(EMB * EMB);
     w.a_wihT = take(EMB * 3 * EMB);
     for (int k = 0; k < 4; ++k) {
-        w.h_woutT[k] = take(EMB * EMB);
-        w.h_w2T[k] = take(EMB * EM);
+        w.h_woutT[k] = take(hy * EMB * EMB);
+        w.h_w2T[k] = take(hy * EMB * EM);
     }
-    for (int k = 0; k < 10; ++k) w.h_wsp[k] = take(REFIL_HSP);
-    for (int k = 0; k < 5; ++k) w.h_wspT[k] = take(REFIL_HSP);
+    for (int k = 0; k < 10; ++k) w.h_wsp[k] = take(k < 8 ? hy * REFIL_HSP : REFIL_HSP);
+    for (int k = 0; k < 5; ++k) w.h_wspT[k] = take(k < 4 ? hy * REFIL_HSP : REFIL_HSP);
     w.ein = take(I * NE * c.K1);
     w.x1 = take(I * NE * EMB);
     w.qkv = take(I * NE * 3 * EMB);
-    w.P = take(3 * I * 1024);
+    w.P = take((int64_t)c.NC * I * 1024);
     w.o = take(T * Ron * EMB);
     w.x2 = take(T * Ron * EMB);
     w.x3 = take(T * Ron * EMB);
@@ -140,18 +159,18 @@ Plan make_plan(const MlgRefilLearnerCfg* cfg, int T1) {
     w.mac = take(T * Ron * c.A);
     w.tmac = take(T * Rtg * c.A);
     for (int k = 0; k < 4; ++k) {
-        const int V = nvar(k);
-        w.x1m[k] = take(I * NE * EMB);
-        w.qkvm[k] = take(I * NE * 3 * EMB);
-        w.Pm[k] = take((int64_t)V * I * 1024);
-        w.om[k] = take((int64_t)V * I * NAS * EMB);
-        w.x2m[k] = take((int64_t)V * I * NAS * EMB);
-        w.X[k] = take((int64_t)V * I * NAS * EM);
-        w.Xtg[k] = take(I * NAS * EM);
-        w.dX[k] = take((int64_t)V * I * NAS * EM);
-        w.doutm[k] = take((int64_t)V * I * NAS * EMB);
-        w.dqkvm[k] = take(I * NE * 3 * EMB);
-        w.dfc1m[k] = take(I * NE * EMB);
+        const int64_t V = hy * nvar_of(k, c.NC);
+        w.x1m[k] = take(hy * I * NE * EMB);
+        w.qkvm[k] = take(hy * I * NE * 3 * EMB);
+        w.Pm[k] = take(V * I * 1024);
+        w.om[k] = take(V * I * NAS * EMB);
+        w.x2m[k] = take(V * I * NAS * EMB);
+        w.X[k] = take(V * I * NAS * EM);
+        w.Xtg[k] = take(hy * I * NAS * EM);
+        w.dX[k] = take(V * I * NAS * EM);
+        w.doutm[k] = take(V * I * NAS * EMB);
+        w.dqkvm[k] = take(hy * I * NE * 3 * EMB);
+        w.dfc1m[k] = take(hy * I * NE * EMB);
     }
     w.dq = take(T * Ron);
     w.d2 = take(T * Ron * c.A);
@@ -447,13 +466,14 @@ struct Prologue {
     MlgEntityBatch bt;
     float *ein, *msum;
     int nb_a, nb_h, nb_s, nb_t, nb_e;  // blocks per agent pack, hypernet pack, split block, transpose job; ein blocks
+    int n_hp, n_hs, n_hsT;             // hypernet packs (8; VDN 0), in_trans splits (10; 2), in_trans^T splits (5; 1)
     int n_rows_in;                     // > 0: the slot map travels here (host_rows); block 0 stores it to rows_dst
     int32_t* rows_dst;
     int32_t rows_in[MLG_INLINE_ROWS];
 };
 static_assert(sizeof(Prologue) <= 4096, "prologue kernel arguments over 4 KB");
 inline int prologue_blocks(const Prologue& P) {
-    return 1 + 2 * P.nb_a + 8 * P.nb_h + 15 * P.nb_s + P.tj.n * P.nb_t + P.nb_e;
+    return 1 + 2 * P.nb_a + P.n_hp * P.nb_h + (P.n_hs + P.n_hsT) * P.nb_s + P.tj.n * P.nb_t + P.nb_e;
 }
 __global__ void __launch_bounds__(256) prologue_kernel(Prologue P) {
     __shared__ int32_t srows[MLG_INLINE_ROWS];
@@ -477,12 +497,12 @@ __global__ void __launch_bounds__(256) prologue_kernel(Prologue P) {
     blk -= 1;
     if (blk < 2 * P.nb_a) return copy_jobs_body(P.aj, P.ap, blk % P.nb_a, blk / P.nb_a);
     blk -= 2 * P.nb_a;
-    if (blk < 8 * P.nb_h) return copy_jobs_body(P.hj, P.hp, blk % P.nb_h, blk / P.nb_h);
-    blk -= 8 * P.nb_h;
-    if (blk < 10 * P.nb_s) return hyper_split_body(P.hs, blk % P.nb_s, blk / P.nb_s);
-    blk -= 10 * P.nb_s;
-    if (blk < 5 * P.nb_s) return hyper_splitT_body(P.hsT, blk % P.nb_s, blk / P.nb_s);
-    blk -= 5 * P.nb_s;
+    if (blk < P.n_hp * P.nb_h) return copy_jobs_body(P.hj, P.hp, blk % P.nb_h, blk / P.nb_h);
+    blk -= P.n_hp * P.nb_h;
+    if (blk < P.n_hs * P.nb_s) return hyper_split_body(P.hs, blk % P.nb_s, blk / P.nb_s);
+    blk -= P.n_hs * P.nb_s;
+    if (blk < P.n_hsT * P.nb_s) return hyper_splitT_body(P.hsT, blk % P.nb_s, blk / P.nb_s);
+    blk -= P.n_hsT * P.nb_s;
     if (blk < P.tj.n * P.nb_t) return transpose_body(P.tj, blk % P.nb_t, blk / P.nb_t);
     blk -= P.tj.n * P.nb_t;
     ein_body(P.c, bt, P.ein, blk);
@@ -536,7 +556,7 @@ struct AgentPtrs {
     const float* wsp;  // split-bf16 in_trans (hyper_split_kernel layout)
 };
 
-template <int S8>
+template <int S8, int NC>
 __global__ void __launch_bounds__(64) ent_fwd_kernel(RCfg c_arg, MlgEntityBatch bt, const uint8_t* __restrict__ groupA,
                                                      RAgent L_arg, const float* __restrict__ ein, AgentPtrs on,
                                                      AgentPtrs tg, const float* __restrict__ msum) {
@@ -545,13 +565,13 @@ __global__ void __launch_bounds__(64) ent_fwd_kernel(RCfg c_arg, MlgEntityBatch 
     __shared__ float s_ein[NE * LDI];
     __shared__ float s_x1[NE * LDX];
     __shared__ float s_qkv[NE * LDQ];
-    __shared__ float s_o[3][16 * LDX];
-    __shared__ uint32_t s_m[3][2][16];
+    __shared__ float s_o[NC][16 * LDX];
+    __shared__ uint32_t s_m[NC][2][16];
     __shared__ uint32_t s_dead[2];
     const int lane = threadIdx.x;
     const bool online = blockIdx.y == 0;
     const AgentPtrs& A = online ? on : tg;
-    const int ncopy = online ? 3 : 1;
+    const int ncopy = online ? NC : 1;
     const int R = online ? c.Ron : c.Rtg;
     const int i0 = blockIdx.x * 2;
     const int Te = t_eff(msum);
@@ -571,23 +591,25 @@ __global__ void __launch_bounds__(64) ent_fwd_kernel(RCfg c_arg, MlgEntityBatch 
         }
         return;
     }
-    for (int k = lane; k < 3 * 16 * LDX; k += 64) (&s_o[0][0])[k] = 0.f;
+    for (int k = lane; k < NC * 16 * LDX; k += 64) (&s_o[0][0])[k] = 0.f;
     if (lane < 32) {
         const int e = lane >> 4, q = lane & 15, i = i0 + e;
         if (live(i)) {
             const int b = i / c.T, t = i % c.T;
             const uint32_t om = om_row(c, bt, b, t, q);
             s_m[0][e][q] = om;
-            if (online) {
-                uint32_t gA, gB, em0;
-                group_bits(c, bt, groupA, b, gA, gB, em0);
-                const uint32_t it = interact_row(gA, gB, q);
-                s_m[1][e][q] = ((~it) & 0xFFFFu) | om;
-                s_m[2][e][q] = it | om;
+            if constexpr (NC == 3) {
+                if (online) {
+                    uint32_t gA, gB, em0;
+                    group_bits(c, bt, groupA, b, gA, gB, em0);
+                    const uint32_t it = interact_row(gA, gB, q);
+                    s_m[1][e][q] = ((~it) & 0xFFFFu) | om;
+                    s_m[2][e][q] = it | om;
+                }
             }
             if (q == 0) s_dead[e] = dead_bits(c, em_bits(c, bt, b, t));
         } else {
-            for (int cc = 0; cc < 3; ++cc) s_m[cc][e][q] = 0xFFFFu;
+            for (int cc = 0; cc < NC; ++cc) s_m[cc][e][q] = 0xFFFFu;
             if (q == 0) s_dead[e] = 0xFFu;
         }
     }
@@ -729,7 +751,7 @@ struct HypPtrs {
     float* Xtg[4];
 };
 
-template <int S8>
+template <int S8, int NC>
 __global__ void __launch_bounds__(64) hyper_fwd_kernel(RCfg c_arg, MlgEntityBatch bt, const uint8_t* __restrict__ groupA,
                                                        RHyper L_arg, const float* __restrict__ ein, HypPtrs hp,
                                                        const float* __restrict__ msum) {
@@ -753,14 +775,14 @@ __global__ void __launch_bounds__(64) hyper_fwd_kernel(RCfg c_arg, MlgEntityBatc
     const int ts = net ? t + 1 : t;
     const int ie = b * c.T + ts;
     const float* P = net ? hp.Ptg[k] : hp.Pon[k];
-    const int V = net ? 1 : nvar(k);
+    const int V = net ? 1 : nvar<NC>(k);
     if (lane < 16) {
         const int q = lane;
         const uint32_t em = em_bits(c, bt, b, ts);
         const uint32_t dead = dead_bits(c, em);
         // default AttentionHyperNet mask: agent q masked or entity j masked (flex_qmix.py:41-45)
         s_m[0][q] = (q < NAS && ((dead >> q) & 1u)) ? 0xFFFFu : (em & 0xFFFFu);
-        if (V == 3) {
+        if (NC == 3 && V == 3) {
             uint32_t gA, gB, em0;
             group_bits(c, bt, groupA, b, gA, gB, em0);
             const uint32_t it = interact_row(gA, gB, q), ac = active_row(em0, q);
@@ -1046,6 +1068,197 @@ __global__ void __launch_bounds__(64) mix_td_kernel(RCfg c_arg, MlgEntityBatch b
     }
 }
 
+// The plain agent's mixing (one online copy; refil_learner.py:107-110, :152-166): mix_td_kernel without the imagined
+// Q, loss = the masked TD loss alone (no lambda). VDN = 1: VDNMixer (vdn.py:9), q_tot = the sum over the agent
+// columns of the chosen Q, the target the same sum of the (double-)Q target values; no hypernet output is read and
+// no dX written. Same load schedule, reductions and argmax order as mix_td_kernel.
+template <int S8, int VDN>
+__global__ void __launch_bounds__(64) mix_td1_kernel(RCfg c_arg, MlgEntityBatch bt, MixIO io) {
+    const RCfg c = static_cfg<S8>(c_arg);
+    const int Te = (int)io.msum[1];
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x;
+    const int b = i / c.T, t = i % c.T;
+    const int e = lane & 31;
+    const int NA = c.NA;
+    float* part = io.part + (int64_t)i * 8;
+    if (t >= Te - 1 || t >= mix_len(io.msum, b)) {  // as mix_td_kernel: zero partials, dQ rows and (NA % 8) d2 rows
+        if (lane < 8) part[lane] = 0.f;
+        const bool d2z = c.NA % 8 != 0;
+        for (int q = lane; q < c.NA * (c.A + 1); q += 64) {
+            const int n = q / (c.A + 1), a2 = q % (c.A + 1);
+            const int64_t row = (int64_t)t * c.Ron + (int64_t)b * c.NA + n;
+            if (a2 == c.A) io.dq[row] = 0.f;
+            else if (d2z) io.d2[row * c.A + a2] = 0.f;
+        }
+        return;
+    }
+    const int64_t srow = eslot(bt, b) * bt.T1;
+    const int hl = lane >> 5;
+    const int an = lane < NA ? (int)bt.actions[(srow + t) * NA + (lane < NA ? lane : 0)] : 0;
+    const bool emv = lane < c.NE && bt.entity_mask[(srow + t) * c.NE + (lane < c.NE ? lane : 0)] != 0;
+    const float r = bt.reward[srow + t];
+    const float term = (float)bt.terminated[srow + t];
+    const float m = emask_at(bt, b, t);
+    int avv[NAS / 2];
+    float tqv[NAS / 2], mqv[NAS / 2];
+#pragma unroll
+    for (int p = 0; p < NAS / 2; ++p) {
+        const int n = 2 * p + hl, nn = n < NA ? n : 0, aa = e < c.A ? e : 0;
+        avv[p] = bt.avail[((srow + t + 1) * NA + nn) * c.A + aa];
+        tqv[p] = io.tmac[((int64_t)(t + 1) * c.Rtg + (int64_t)b * NA + nn) * c.A + aa];
+        mqv[p] = c.double_q ? io.mac[((int64_t)(t + 1) * c.Ron + (int64_t)b * NA + nn) * c.A + aa] : 0.f;
+    }
+    const int64_t xo = (int64_t)i * NAS * EM + e;
+    float xt[4][NAS], xP[NAS], xwf[NAS], xb1[NAS], xV[NAS];
+    if constexpr (!VDN) {
+#pragma unroll
+        for (int n = 0; n < NAS; ++n) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) xt[k][n] = io.Xtg[k][xo + n * EM];
+            xP[n] = io.X[0][xo + n * EM];
+            xwf[n] = io.X[1][xo + n * EM];
+            xb1[n] = io.X[2][xo + n * EM];
+            xV[n] = io.X[3][xo + n * EM];
+        }
+    }
+    const float caqv = lane < NA ? io.mac[((int64_t)t * c.Ron + (int64_t)b * NA + (lane < NA ? lane : 0)) * c.A + an] : 0.f;
+    const uint32_t dead = dead_bits(c, (~((1u << c.NE) - 1u) & 0xFFFFu) | ((uint32_t)__ballot(emv) & 0xFFFFu));
+    float tmax[NAS];
+#pragma unroll
+    for (int p = 0; p < NAS / 2; ++p) {
+        const int n = 2 * p + hl;
+        const bool ok = n < NA && e < c.A;
+        const float tqm = avv[p] == 0 ? -9999999.f : tqv[p];
+        float res;
+        if (c.double_q) {
+            float bv = ok ? (avv[p] == 0 ? -9999999.f : mqv[p]) : -INFINITY;
+            int bi = ok ? e : 64 + e;
+#pragma unroll
+            for (int s2 = 1; s2 < 32; s2 <<= 1) {
+                const float ov = __shfl_xor(bv, s2);
+                const int oi = __shfl_xor(bi, s2);
+                const bool take = amax_better(ov, oi, bv, bi);
+                bv = take ? ov : bv;
+                bi = take ? oi : bi;
+            }
+            res = __shfl(tqm, hl * 32 + (bi & 31));
+        } else {
+            res = ok ? tqm : __builtin_nanf("");
+#pragma unroll
+            for (int s2 = 1; s2 < 32; s2 <<= 1) res = fmaxf(res, __shfl_xor(res, s2));
+        }
+        tmax[2 * p] = __shfl(res, 0);
+        tmax[2 * p + 1] = __shfl(res, 32);
+    }
+    float caq[NAS];
+    int act[NAS];
+#pragma unroll
+    for (int n = 0; n < NAS; ++n) {
+        act[n] = __shfl(an, n);
+        caq[n] = __shfl(caqv, n);
+    }
+    const float invN = 1.f / (float)NA, invNE = 1.f / ((float)NA * (float)EM);
+    auto col_sum = [&](const float(&x)[NAS]) {
+        float s = 0.f;
+#pragma unroll
+        for (int n = 0; n < NAS; ++n)
+            if (n < NA) s += x[n];
+        return s;
+    };
+    float y_tg, yP, dqP[NAS];
+    const float msum = io.msum[0];
+    if constexpr (VDN) {
+        y_tg = col_sum(tmax);
+        yP = col_sum(caq);
+    } else {
+        float pre = col_sum(xt[2]) * invN;  // b1
+#pragma unroll
+        for (int n = 0; n < NAS; ++n)
+            if (n < NA) pre += tmax[n] * mw(xt[0][n], c.softmax);
+        const float hid = elu_f(pre);
+        const float wft = mw(col_sum(xt[1]) * invN, c.softmax);
+        const float vsum = sum32(col_sum(xt[3]));
+        y_tg = sum32(hid * wft) + vsum * invNE;
+    }
+    float w1P[NAS], preP = 0.f, wf = 0.f, wfpre = 0.f, hidP = 0.f;
+    if constexpr (!VDN) {
+        const float b1 = col_sum(xb1) * invN;
+        wfpre = col_sum(xwf) * invN;
+        wf = mw(wfpre, c.softmax);
+        const float vv = sum32(col_sum(xV)) * invNE;
+        preP = b1;
+#pragma unroll
+        for (int n = 0; n < NAS; ++n) {
+            w1P[n] = 0.f;
+            if (n >= NA) continue;
+            w1P[n] = mw(xP[n], c.softmax);
+            preP += caq[n] * w1P[n];
+        }
+        hidP = elu_f(preP);
+        yP = sum32(hidP * wf) + vv;
+    }
+    const float target = r + c.gamma * (1.f - term) * y_tg;
+    const float tdP = (yP - target) * m;
+    if (lane == 0) {
+        part[0] = tdP * tdP;
+        part[1] = 0.f;
+        part[2] = fabsf(tdP);
+        part[3] = yP * m;
+        part[4] = target * m;
+        part[5] = m;
+        part[6] = 0.f;
+        part[7] = 0.f;
+    }
+    // ---- backward ----
+    const float gP = 2.f * tdP * m / msum;
+    if constexpr (VDN) {
+#pragma unroll
+        for (int n = 0; n < NAS; ++n) dqP[n] = gP;
+    } else {
+        const float dwf = gP * hidP;
+        const float dv = gP;
+        const float dpP = gP * wf * elu_d(preP);
+        const float db1 = dpP;
+        const float dwfpre = mw_bwd(dwf, wf, wfpre, c.softmax);
+        float* dXP = io.dX[0] + (int64_t)i * NAS * EM;
+        float* dXwf = io.dX[1] + (int64_t)i * NAS * EM;
+        float* dXb1 = io.dX[2] + (int64_t)i * NAS * EM;
+        float* dXV = io.dX[3] + (int64_t)i * NAS * EM;
+#pragma unroll
+        for (int n = 0; n < NAS; ++n) {
+            const bool live = n < NA && !((dead >> n) & 1u);
+            float vP = 0.f, vwf = 0.f, vb1 = 0.f, vV = 0.f;
+            if (n < NA) {
+                vP = mw_bwd(caq[n] * dpP, w1P[n], xP[n], c.softmax);
+                vwf = dwfpre * invN;
+                vb1 = db1 * invN;
+                vV = dv * invNE;
+            }
+            dqP[n] = sum32(w1P[n] * dpP);
+            if (lane < 32) {
+                dXP[n * EM + e] = live ? vP : 0.f;
+                dXwf[n * EM + e] = live ? vwf : 0.f;
+                dXb1[n * EM + e] = live ? vb1 : 0.f;
+                dXV[n * EM + e] = live ? vV : 0.f;
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < NAS / 2; ++p) {
+        const int n = 2 * p + hl;
+        if (2 * p >= NA) break;
+        const bool live = n < NA && !((dead >> n) & 1u);
+        const int actn = hl ? act[2 * p + 1] : act[2 * p];
+        const float v = live ? (hl ? dqP[2 * p + 1] : dqP[2 * p]) : 0.f;
+        const int64_t row = (int64_t)t * c.Ron + (int64_t)b * NA + n;
+        if (n < NA) {
+            if (e < c.A) io.d2[row * c.A + e] = e == actn ? v : 0.f;
+            if (e == 0) io.dq[row] = v;
+        }
+    }
+}
+
 // One item's q | k | v rows (NE x 3 EMB, row-major in global) into LDS rows of stride LDQ: all of the lane's 24 loads
 // issued before the first LDS write (a loop over them waited for each group of loads in turn, three round trips).
 __device__ __forceinline__ void qkv_to_lds(const float* __restrict__ src, float* dst, int lane) {
@@ -1081,7 +1294,7 @@ struct HypBwd {
     float* dfc1m[4];
 };
 
-template <int S8>
+template <int S8, int NC>
 __global__ void __launch_bounds__(64) hyper_bwd_kernel(RCfg c_arg, MlgEntityBatch bt, HypBwd hb,
                                                        const float* __restrict__ msum) {
     const RCfg c = static_cfg<S8>(c_arg);
@@ -1092,7 +1305,7 @@ __global__ void __launch_bounds__(64) hyper_bwd_kernel(RCfg c_arg, MlgEntityBatc
     const int lane = threadIdx.x;
     const int i = blockIdx.x, k = blockIdx.y;
     const int b = i / c.T, t = i % c.T;
-    const int V = nvar(k);
+    const int V = nvar<NC>(k);
     const int col = lane & 15, g = lane >> 4;
     // masked mixer item: its deltas are zero and only the wgrad jobs read them, which skip its rows
     if (t >= t_eff(msum) - 1 || t >= mix_len(msum, b)) return;
@@ -1172,11 +1385,11 @@ struct EntBwd {
     float *dfc2, *dout, *dqkv, *dfc1;
 };
 
-template <int S8>
+template <int S8, int NC>
 __global__ void __launch_bounds__(64) ent_bwd_kernel(RCfg c_arg, MlgEntityBatch bt, EntBwd eb,
                                                      const float* __restrict__ msum) {
     const RCfg c = static_cfg<S8>(c_arg);
-    __shared__ float s_do[3][16 * LDX];
+    __shared__ float s_do[NC][16 * LDX];
     __shared__ float s_qkv[NE * LDQ];
     __shared__ float s_dqkv[NE * LDQ];
     __shared__ float s_ds[NH * 16 * NE];
@@ -1200,7 +1413,7 @@ __global__ void __launch_bounds__(64) ent_bwd_kernel(RCfg c_arg, MlgEntityBatch 
     const uint32_t dead = s_dead[0] | (s_dead[1] << 8);
     const bool rdead = (dead >> col) & 1u;
     const bool any = live(i0) || live(i0 + 1);
-    for (int cc = 0; cc < 3; ++cc) {
+    for (int cc = 0; cc < NC; ++cc) {
         const int64_t ro = (int64_t)t * c.Ron + ((int64_t)cc * c.B + b) * c.NA + n;
         if (!any) {
             if (row_ok && c.NA % 8 != 0) {  // t-major rows the wgrad jobs cannot skip (bjob_steps needs NA % 8 == 0)
@@ -1252,7 +1465,7 @@ __global__ void __launch_bounds__(64) ent_bwd_kernel(RCfg c_arg, MlgEntityBatch 
         load_relu_rows(eb.x1 + ((int64_t)ii * NE + col) * EMB, x1v, lane);
         qkv_to_lds(eb.qkv + (int64_t)ii * NE * 3 * EMB, s_qkv, lane);
         wave_sync();
-        for (int cc = 0; cc < 3; ++cc) {
+        for (int cc = 0; cc < NC; ++cc) {
             const float* Pv = eb.Pw + ((int64_t)cc * c.I + ii) * 1024;
             if (cc == 0) attn_bwd<false>(s_qkv, Pv, c.NA, s_do[cc] + ee * NAS * LDX, LDX, s_ds, s_dqkv, lane);
             else attn_bwd<true>(s_qkv, Pv, c.NA, s_do[cc] + ee * NAS * LDX, LDX, s_ds, s_dqkv, lane);
@@ -1340,10 +1553,10 @@ RJobs make_jobs(Plan& p, float* ws, float* grads, int64_t* slab_floats, int* n_t
     J.j[J.n++] = steps(mlg::bjob(at(p.w.dgh), 3 * EMB, at(p.w.hs_on), EMB, gp(a.c_whh), gp(a.c_bhh), 3 * EMB, EMB, TR));
     J.j[J.n++] = steps(mlg::bjob(at(p.w.d2), c.A, ws ? ws + p.w.hs_on + (int64_t)c.Ron * EMB : nullptr, EMB,
                                  gp(a.c_w3), gp(a.c_b3), c.A, EMB, TR));
-    for (int k = 0; k < 4; ++k) {  // REFIL_HYPER_JOBS jobs, the table's last
+    for (int k = 0; k < 4 && !c.vdn; ++k) {  // REFIL_HYPER_JOBS jobs, the table's last (VDN: none)
         const RHyper& h = p.Lh;
         const int64_t G0 = p.n_agent + (int64_t)k * h.c_total;
-        const int rows = nvar(k) * c.I * NAS;
+        const int rows = nvar_of(k, c.NC) * c.I * NAS;
         J.j[J.n++] = items(mlg::bjob(at(p.w.dfc1m[k]), EMB, at(p.w.ein), c.K1, gp(G0 + h.c_w1), gp(G0 + h.c_b1), EMB, c.D0,
                                      I16), NE);
         J.j[J.n++] = items(mlg::bjob(at(p.w.dqkvm[k]), 3 * EMB, at(p.w.x1m[k]), EMB, gp(G0 + h.c_win), nullptr, 3 * EMB,
@@ -1393,7 +1606,8 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
     tr(params + La.c_wout, ws + w.a_woutT, EMB, EMB);
     tr(params + La.c_w2, ws + w.a_w2T, EMB, EMB);
     tr(params + La.c_wih, ws + w.a_wihT, 3 * EMB, EMB);
-    for (int k = 0; k < 4; ++k) {
+    const bool hyp = !c.vdn;  // VDN: the flat vectors hold the agent alone, no hypernet job reads past it
+    for (int k = 0; k < 4 && hyp; ++k) {
         const int64_t G0 = p.n_agent + (int64_t)k * p.Lh.c_total;
         P.hp.src[2 * k] = params + G0;
         P.hp.dst[2 * k] = ws + w.ph_on[k];
@@ -1404,23 +1618,26 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
     }
     MLG_REQUIRE(!tr_bad, "refil learner: transpose job table over capacity or job larger than the grid");
     HSplit& hs = P.hs;
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < 4 && hyp; ++k) {
         const int64_t G0 = p.n_agent + (int64_t)k * p.Lh.c_total;
         hs.src[k] = params + G0 + p.Lh.c_win;
         hs.src[k + 4] = tparams + G0 + p.Lh.c_win;
         hs.dst[k] = ws + w.h_wsp[k];
         hs.dst[k + 4] = ws + w.h_wsp[k + 4];
     }
-    hs.src[8] = params + La.c_win;
-    hs.src[9] = tparams + La.c_win;
-    hs.dst[8] = ws + w.h_wsp[8];
-    hs.dst[9] = ws + w.h_wsp[9];
-    for (int k = 0; k < 4; ++k) {
+    P.n_hp = hyp ? 8 : 0;
+    P.n_hs = hyp ? 10 : 2;  // the agent's two blocks close the table
+    P.n_hsT = hyp ? 5 : 1;
+    hs.src[P.n_hs - 2] = params + La.c_win;
+    hs.src[P.n_hs - 1] = tparams + La.c_win;
+    hs.dst[P.n_hs - 2] = ws + w.h_wsp[8];
+    hs.dst[P.n_hs - 1] = ws + w.h_wsp[9];
+    for (int k = 0; k < 4 && hyp; ++k) {
         P.hsT.src[k] = hs.src[k];
         P.hsT.dst[k] = ws + w.h_wspT[k];
     }
-    P.hsT.src[4] = params + La.c_win;
-    P.hsT.dst[4] = ws + w.h_wspT[4];
+    P.hsT.src[P.n_hsT - 1] = params + La.c_win;
+    P.hsT.dst[P.n_hsT - 1] = ws + w.h_wspT[4];
     P.c = c;
     P.bt = bt;
     if (bufs->host_rows) {
@@ -1438,7 +1655,7 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
     hipLaunchKernelGGL(prologue_kernel, dim3((unsigned)prologue_blocks(P)), dim3(256), 0, s, P);
     // read per call: a test can compare the one-stream and side-stream forms within one process
     const bool one_stream = getenv("MLG_REFIL_ONE_STREAM") != nullptr;
-    mlg::SideStream* side = one_stream ? nullptr : mlg::side_stream(s);
+    mlg::SideStream* side = (one_stream || !hyp) ? nullptr : mlg::side_stream(s);  // VDN: nothing for a side stream
     const hipStream_t sh = side ? side->s : s;  // the hypernet kernels' stream
     if (side) {
         MLG_REQUIRE(mlg::fork_join(side, 0, s, sh), "refil learner: side stream fork");
@@ -1447,9 +1664,11 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
     AgentPtrs on{ws + w.pa_on, ws + w.x1, ws + w.qkv, ws + w.P, ws + w.o, ws + w.x2, ws + w.x3, ws + w.gi_on,
                  ws + w.h_wsp[8]};
     AgentPtrs tg{ws + w.pa_tg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ws + w.gi_tg, ws + w.h_wsp[9]};
-    hipLaunchKernelGGL(s8 ? ent_fwd_kernel<1> : ent_fwd_kernel<0>, dim3((unsigned)((c.I + 1) / 2), 2), dim3(64), 0, s, c,
-                       bt, bufs->groupA, La,
-                       ws + w.ein, on, tg, ws + w.msum);
+    const bool im = c.NC == 3;  // the imagine agent: three online copies; else the plain agent's one
+    hipLaunchKernelGGL(im ? (s8 ? ent_fwd_kernel<1, 3> : ent_fwd_kernel<0, 3>)
+                          : (s8 ? ent_fwd_kernel<1, 1> : ent_fwd_kernel<0, 1>),
+                       dim3((unsigned)((c.I + 1) / 2), 2), dim3(64), 0, s, c, bt, bufs->groupA, La, ws + w.ein, on, tg,
+                       ws + w.msum);
     const int nt_on = (c.Ron + 15) / 16;
     hipLaunchKernelGGL(rec4_kernel, dim3((unsigned)((c.Ron + 3) / 4 + (c.Rtg + 3) / 4)), dim3(256), 0, s, c, La,
                        ws + w.pa_on, ws + w.pa_tg, ws + w.gi_on, ws + w.gi_tg, ws + w.hs_on, ws + w.hs_tg, ws + w.gr,
@@ -1471,9 +1690,10 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
         hp.X[k] = ws + w.X[k];
         hp.Xtg[k] = ws + w.Xtg[k];
     }
-    hipLaunchKernelGGL(s8 ? hyper_fwd_kernel<1> : hyper_fwd_kernel<0>, dim3((unsigned)c.I, 8), dim3(64), 0, sh, c, bt,
-                       bufs->groupA, p.Lh, ws + w.ein, hp,
-                       ws + w.msum);
+    if (hyp)
+        hipLaunchKernelGGL(im ? (s8 ? hyper_fwd_kernel<1, 3> : hyper_fwd_kernel<0, 3>)
+                              : (s8 ? hyper_fwd_kernel<1, 1> : hyper_fwd_kernel<0, 1>),
+                           dim3((unsigned)c.I, 8), dim3(64), 0, sh, c, bt, bufs->groupA, p.Lh, ws + w.ein, hp, ws + w.msum);
     if (side) {
         MLG_REQUIRE(mlg::fork_join(side, 1, sh, s), "refil learner: side stream join");
     }
@@ -1489,7 +1709,11 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
     io.dq = ws + w.dq;
     io.d2 = ws + w.d2;
     io.part = ws + w.part;
-    hipLaunchKernelGGL(s8 ? mix_td_kernel<1> : mix_td_kernel<0>, dim3((unsigned)c.I), dim3(64), 0, s, c, bt, io);
+    if (im) hipLaunchKernelGGL(s8 ? mix_td_kernel<1> : mix_td_kernel<0>, dim3((unsigned)c.I), dim3(64), 0, s, c, bt, io);
+    else if (hyp)
+        hipLaunchKernelGGL((s8 ? mix_td1_kernel<1, 0> : mix_td1_kernel<0, 0>), dim3((unsigned)c.I), dim3(64), 0, s, c, bt, io);
+    else
+        hipLaunchKernelGGL((s8 ? mix_td1_kernel<1, 1> : mix_td1_kernel<0, 1>), dim3((unsigned)c.I), dim3(64), 0, s, c, bt, io);
     if (side) {
         MLG_REQUIRE(mlg::fork_join(side, 2, s, sh), "refil learner: side stream fork");
     }
@@ -1507,8 +1731,10 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
         hb.dqkvm[k] = ws + w.dqkvm[k];
         hb.dfc1m[k] = ws + w.dfc1m[k];
     }
-    hipLaunchKernelGGL(s8 ? hyper_bwd_kernel<1> : hyper_bwd_kernel<0>, dim3((unsigned)c.I, 4), dim3(64), 0, sh, c, bt, hb,
-                       ws + w.msum);
+    if (hyp)
+        hipLaunchKernelGGL(im ? (s8 ? hyper_bwd_kernel<1, 3> : hyper_bwd_kernel<0, 3>)
+                              : (s8 ? hyper_bwd_kernel<1, 1> : hyper_bwd_kernel<0, 1>),
+                           dim3((unsigned)c.I, 4), dim3(64), 0, sh, c, bt, hb, ws + w.msum);
     // weight gradients: the hypernets' jobs (the table's last REFIL_HYPER_JOBS, final after hyper_bwd) run on the side
     // stream beside ent_bwd, the agent's after it; one reduce over the whole table (same chunk sums as one launch)
     int64_t slab_floats, n_red;
@@ -1516,9 +1742,10 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
     RJobs J = make_jobs(p, ws, bufs->grads, &slab_floats, &n_tasks, &n_red);
     int tH, tE;
     int64_t rH, rE;
-    const RJobs JH = mlg::bjob_view(J, J.n - REFIL_HYPER_JOBS, J.n, &tH, &rH),
-               JE = mlg::bjob_view(J, 0, J.n - REFIL_HYPER_JOBS, &tE, &rE);
-    hipLaunchKernelGGL(mlg::wgrad_block_kernel<MJ>, dim3((unsigned)((tH + 3) / 4)), dim3(256), 0, sh, JH, ws + w.slab);
+    const int n_hj = hyp ? REFIL_HYPER_JOBS : 0;
+    const RJobs JH = mlg::bjob_view(J, J.n - n_hj, J.n, &tH, &rH), JE = mlg::bjob_view(J, 0, J.n - n_hj, &tE, &rE);
+    if (hyp)
+        hipLaunchKernelGGL(mlg::wgrad_block_kernel<MJ>, dim3((unsigned)((tH + 3) / 4)), dim3(256), 0, sh, JH, ws + w.slab);
     if (side) MLG_REQUIRE(hipEventRecord(side->ev[3], sh) == hipSuccess, "refil learner: side stream record");
     // ---- agent backward ----
     hipLaunchKernelGGL(rec_bwd4_kernel, dim3((unsigned)((c.Ron + 3) / 4)), dim3(256), 0, s, c, bt, La, ws + w.pa_on,
@@ -1526,8 +1753,9 @@ int run_train(Plan& p, const MlgRefilLearnerCfg* cfg, const MlgRefilLearnerBufs*
                        ws + w.msum);
     EntBwd eb{ws + w.a_wihT, ws + w.a_w2T, ws + w.a_woutT, ws + w.h_wspT[4], ws + w.x1, ws + w.qkv, ws + w.P, ws + w.x3,
               ws + w.dgi, ws + w.dfc2, ws + w.dout, ws + w.dqkv, ws + w.dfc1};
-    hipLaunchKernelGGL(s8 ? ent_bwd_kernel<1> : ent_bwd_kernel<0>, dim3((unsigned)((c.I + 1) / 2)), dim3(64), 0, s, c, bt,
-                       eb, ws + w.msum);
+    hipLaunchKernelGGL(im ? (s8 ? ent_bwd_kernel<1, 3> : ent_bwd_kernel<0, 3>)
+                          : (s8 ? ent_bwd_kernel<1, 1> : ent_bwd_kernel<0, 1>),
+                       dim3((unsigned)((c.I + 1) / 2)), dim3(64), 0, s, c, bt, eb, ws + w.msum);
     // ---- weight gradients, clip, RMSprop ----
     hipLaunchKernelGGL(mlg::wgrad_block_kernel<MJ>, dim3((unsigned)((tE + 3) / 4)), dim3(256), 0, s, JE, ws + w.slab);
     if (side) MLG_REQUIRE(hipStreamWaitEvent(s, side->ev[3], 0) == hipSuccess, "refil learner: side stream join");
@@ -1585,8 +1813,8 @@ extern "C" int mlg_refil_draw_groups(int32_t B, int32_t NE, uint64_t seed, uint3
 
 extern "C" int mlg_refil_train(const MlgRefilLearnerCfg* c, const MlgRefilLearnerBufs* b, void* stream) {
     if (check_cfg(c)) return 1;
-    MLG_REQUIRE(b && b->params && b->grads && b->square_avg && b->target_params && b->workspace && b->stats && b->groupA,
-                "refil_train: null buffer");
+    MLG_REQUIRE(b && b->params && b->grads && b->square_avg && b->target_params && b->workspace && b->stats &&
+                    (b->groupA || !c->imagine), "refil_train: null buffer");
     const MlgEntityBatch& bt = b->batch;
     MLG_REQUIRE(bt.entities && bt.obs_mask && bt.entity_mask && bt.actions && bt.avail && bt.reward && bt.terminated &&
                     bt.actions_onehot && bt.filled, "refil_train: batch has null tensors");

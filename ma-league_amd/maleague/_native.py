@@ -97,7 +97,7 @@ class MlgRefilLearnerCfg(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ["B", "T", "n_agents", "n_entities", "entity_shape", "n_actions",
                                               "entity_last_action", "attn_embed_dim", "attn_n_heads", "rnn_hidden_dim",
                                               "hypernet_embed", "mixing_embed_dim", "double_q",
-                                              "softmax_mixing_weights", "imagine"]] + \
+                                              "softmax_mixing_weights", "imagine", "mixer"]] + \
                [(n, ctypes.c_float) for n in ["gamma", "lmbda", "lr", "optim_alpha", "optim_eps", "grad_norm_clip"]]
 
 

@@ -1,5 +1,10 @@
 """REFILLearner (API of src/marl/learners/refil_learner.py:46-267) on the fused gfx950 pipeline.
 
+Three combinations train, the ones the reference's learner runs on the entity scheme: the imagine agent with
+FlexQMixer (REFIL), and its two baselines on the plain entity agent -- FlexQMixer (attention-QMIX) and VDNMixer
+(attention-VDN). The baselines run one online agent copy, no group draw and no imagined loss; VDN runs no hypernet
+and its flat parameter vector is the agent alone.
+
 train() is one call into mlg_refil_train: the EntityMAC unrolls of the plain, within-group and interact-group
 copies (the imagine agent, entity_rnn_agent.py:88-126) and of the target MAC, FlexQMixer on the plain and the
 imagined chosen Q, double-Q targets through the target mixer, the lambda-mixed TD loss, every gradient,
@@ -14,7 +19,7 @@ import torch
 
 from .. import _native
 from ..components.batch_view import mlg_entity_batch
-from ..modules.mixers import FlexQMixer
+from ..modules.mixers import FlexQMixer, VDNMixer
 from ..utils.checkpoint import save_module, save_optimizer
 from .q_learner import FlatParams, Learner
 
@@ -24,19 +29,32 @@ AGENT_ORDER = ["fc1.weight", "fc1.bias", "attn.in_trans.weight", "attn.out_trans
 HYPER_ORDER = ["fc1.weight", "fc1.bias", "attn.in_trans.weight", "attn.out_trans.weight", "attn.out_trans.bias",
                "fc2.weight", "fc2.bias"]
 MIXER_ORDER = [f"{h}.{p}" for h in ("hyper_w_1", "hyper_w_final", "hyper_b_1", "V") for p in HYPER_ORDER]
+AGENTS = ("imagine_entity_attend_rnn", "entity_attend_rnn")
+MIXERS = ("flex_qmix", "vdn")  # MlgRefilLearnerCfg.mixer = the index
+
+
+def check_combination(agent, mixer):
+    """The (agent, mixer) pairs the reference's REFILLearner runs on the entity scheme; anything else is refused
+    here, before any launch, naming both keys."""
+    what = f"REFILLearner: agent {agent!r} with mixer {mixer!r}"
+    if agent not in AGENTS:
+        raise ValueError(f"{what}: agent must be one of {AGENTS}")
+    if mixer not in MIXERS:
+        raise ValueError(f"{what}: mixer must be one of {MIXERS} (lin_flex_qmix, qmix and no mixer are not built)")
+    if mixer == "vdn" and agent != "entity_attend_rnn":
+        raise ValueError(f"{what}: VDNMixer takes no imagine groups (the reference raises TypeError); "
+                         "use agent 'entity_attend_rnn'")
 
 
 class REFILLearner(Learner):
     def __init__(self, mac, scheme, logger, args, name=None):
         super().__init__(mac, scheme, logger, args, name)
-        if args.mixer != "flex_qmix":
-            raise ValueError(f"REFILLearner: mixer {args.mixer!r} not built (flex_qmix is the REFIL mixer)")
-        if "imagine" not in args.agent:
-            raise NotImplementedError("REFILLearner: the imagine agent is the built path (refil_learner.py:122)")
+        check_combination(args.agent, args.mixer)
+        self.imagine = args.agent == "imagine_entity_attend_rnn"
         if getattr(args, "weight_decay", 0):
             raise NotImplementedError("RMSprop weight_decay != 0 is not built")
         self.last_target_update_episode = 0
-        self.mixer = FlexQMixer(args)
+        self.mixer = FlexQMixer(args) if args.mixer == "flex_qmix" else VDNMixer()
         self.target_mixer = copy.deepcopy(self.mixer)
         self.target_mac = copy.deepcopy(mac)
         self.device = torch.device(getattr(args, "device", "cuda"))
@@ -59,8 +77,9 @@ class REFILLearner(Learner):
         if names != AGENT_ORDER:
             raise RuntimeError(f"agent parameter order {names} != kernel layout {AGENT_ORDER}")
         names = [n for n, _ in self.mixer.named_parameters()]
-        if names != MIXER_ORDER:
-            raise RuntimeError(f"mixer parameter order {names} != kernel layout {MIXER_ORDER}")
+        want = MIXER_ORDER if self.args.mixer == "flex_qmix" else []  # VDNMixer has no parameters
+        if names != want:
+            raise RuntimeError(f"mixer parameter order {names} != kernel layout {want}")
 
     def build_optimizer(self):
         self._check_order()
@@ -89,15 +108,19 @@ class REFILLearner(Learner):
             B=B, T=T, n_agents=a.n_agents, n_entities=a.n_entities, entity_shape=d.entity_shape, n_actions=a.n_actions,
             entity_last_action=d.entity_last_action, attn_embed_dim=a.attn_embed_dim, attn_n_heads=a.attn_n_heads,
             rnn_hidden_dim=a.rnn_hidden_dim, hypernet_embed=a.hypernet_embed, mixing_embed_dim=a.mixing_embed_dim,
-            double_q=int(bool(a.double_q)), softmax_mixing_weights=int(bool(a.softmax_mixing_weights)), imagine=1,
+            double_q=int(bool(a.double_q)), softmax_mixing_weights=int(bool(a.softmax_mixing_weights)),
+            imagine=int(self.imagine), mixer=MIXERS.index(a.mixer),
             gamma=float(a.gamma), lmbda=float(a.lmbda), lr=float(a.lr), optim_alpha=float(a.optim_alpha),
             optim_eps=float(a.optim_eps), grad_norm_clip=float(a.grad_norm_clip))
 
     def train(self, batch, t_env, episode_num: int, groupA=None):
         """refil_learner.py:102-237. groupA [B, NE] (or [B, 1, NE]) uint8: the imagine group draw; drawn on the
-        device when None (the reference's th.rand + th.bernoulli, entity_rnn_agent.py:95-97)."""
+        device when None (the reference's th.rand + th.bernoulli, entity_rnn_agent.py:95-97). The plain agent has
+        no groups: no draw is launched and passing groupA is an error."""
         if self.optimiser is None:
             raise RuntimeError("call build_optimizer() before train()")
+        if groupA is not None and not self.imagine:
+            raise ValueError(f"REFILLearner: agent {self.args.agent!r} draws no imagine groups; groupA must be None")
         lib = _native.load(require_gpu=True)
         B, NE = batch.batch_size, self.args.n_entities
         cfg = self._cfg(B, batch.max_seq_length)
@@ -107,13 +130,16 @@ class REFILLearner(Learner):
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.zeros(int(need * 1.1) + 1024, dtype=torch.float32, device=self.device)
-        if groupA is None:  # drawn on the device: one launch (mlg_refil_draw_groups), counter = train call
+        if not self.imagine:
+            groupA = None
+        elif groupA is None:  # drawn on the device: one launch (mlg_refil_draw_groups), counter = train call
             if self._groups is None or self._groups.shape != (B, NE):
                 self._groups = torch.empty(B, NE, dtype=torch.uint8, device=self.device)
             groupA = self._groups
             _native.call("mlg_refil_draw_groups", B, NE, self._group_seed, self.train_calls & 0xFFFFFFFF,
                          groupA.data_ptr(), _native.stream_ptr(self.device))
-        groupA = groupA.reshape(B, NE).to(device=self.device, dtype=torch.uint8).contiguous()
+        if groupA is not None:
+            groupA = groupA.reshape(B, NE).to(device=self.device, dtype=torch.uint8).contiguous()
         # a sampled view's slot map travels as a kernel argument (no pinned host copy + H2D copy per call)
         host_rows = getattr(batch, "host_rows", None)
         if host_rows is not None and (B > lib.mlg_qlearner_inline_rows() or getattr(batch, "_data", None) is not None):
@@ -123,8 +149,8 @@ class REFILLearner(Learner):
         # due after this step (refil_learner.py:181-183) is written by that launch too (no separate copy)
         counter = self.mac.agent.trained_counter(self.device)
         sync = (episode_num - self.last_target_update_episode) / self.args.target_update_interval >= 1.0
-        bufs = _native.MlgRefilLearnerBufs(mb, groupA.data_ptr(), self._flat.flat.data_ptr(), self._grads.data_ptr(),
-                                           self._sq.data_ptr(), self._tflat.flat.data_ptr(), self._ws.data_ptr(),
+        bufs = _native.MlgRefilLearnerBufs(mb, None if groupA is None else groupA.data_ptr(),
+                                           self._flat.flat.data_ptr(), self._grads.data_ptr(), self._sq.data_ptr(), self._tflat.flat.data_ptr(), self._ws.data_ptr(),
                                            self._stats.data_ptr(), counter.data_ptr(),
                                            self._tflat.flat.data_ptr() if sync else None,
                                            None if host_rows is None else host_rows.ctypes.data)
@@ -147,10 +173,7 @@ class REFILLearner(Learner):
         if t_env - self.log_stats_t >= self.args.learner_log_interval:
             # the reference REFIL learner logs unprefixed keys, im_loss only for imagine agents
             # (refil_learner.py:185-195; unlike QLearner's "{name}loss" keys)
-            imagine = "imagine" in str(getattr(self.args, "agent", ""))
             for k, v in self.last_stats.items():
-                if k == "im_loss" and not imagine:
-                    continue
                 self.logger.log_stat(k, v, t_env)
             self.log_stats_t = t_env
 
@@ -162,6 +185,8 @@ class REFILLearner(Learner):
         st = self._stats.cpu()
         self._last_stats = {"loss": float(st[0]), "im_loss": float(st[1]), "grad_norm": float(st[2]),
                             "td_error_abs": float(st[3]), "q_taken_mean": float(st[4]), "target_mean": float(st[5])}
+        if not self.imagine:  # the reference logs im_loss only for imagine agents (refil_learner.py:187-188)
+            del self._last_stats["im_loss"]
         self._stats_fresh = False
         return self._last_stats
 

@@ -91,6 +91,10 @@ BUILTIN = {
         "critic_train_mode": "seq", "critic_train_reps": 1, "q_nstep": 0, "name": "coma",
     },
 }
+# The attention baselines REFIL is compared against (refil_learner.py:107-110, :152-155): algs/refil with the plain
+# entity agent (attention-QMIX, no imagination), and the same with the VDN mixer (attention-VDN).
+BUILTIN["algs/attn_qmix"] = dict(BUILTIN["algs/refil"], agent="entity_attend_rnn", name="attn_qmix")
+BUILTIN["algs/attn_vdn"] = dict(BUILTIN["algs/attn_qmix"], mixer="vdn", name="attn_vdn")
 
 
 def recursive_dict_update(dest, src):
