@@ -151,6 +151,15 @@ int mlg_rollout_selfplay(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgent
                          const float *away_packed, MlgBatch *home, MlgBatch *away, MlgRunInfo *info,
                          float eps_home, float eps_away, int32_t test_mode, void *stream);
 
+/* Host only, launches nothing. Writes the name of the kernel mlg_rollout (selfplay = 0) or mlg_rollout_selfplay
+ * (selfplay = 1) would launch for this spec and agent dims under the current MLG_ROLLOUT_* environment, and the
+ * dynamic LDS bytes of that launch. Names: "v7-static" / "v7" (compile-time 5v5 or 3v3 shape / runtime shape), "v2",
+ * "v1-lds/tpwK" / "v1-global/tpwK" (weights in LDS / read from global memory, K agent tiles per wave), "sp8",
+ * "sp7-static" / "sp7", "sp2". Both entry points take their decision from the same function. Nonzero
+ * (mlg_last_error) where the entry point itself would refuse the shape. */
+int mlg_rollout_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, int32_t selfplay, char *name,
+                         int32_t name_cap, int64_t *lds_bytes);
+
 /* Zero `count` EpisodeBatch slots starting at slot0 (mod ring_size) in every key -- one launch; the
  * ring-mode pre-fill that replaces constructing a zero EpisodeBatch. slot_bytes[8] = bytes per slot of
  * state, obs, actions, avail, reward, terminated, actions_onehot, filled. */

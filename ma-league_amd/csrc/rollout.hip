@@ -2184,17 +2184,6 @@ int launch_rollout_t(int grid, int threads, hipStream_t s, const MlgEnvSpec& spe
     return 0;
 }
 
-// Weights in LDS when one policy's image fits (self-play holds two policies: weights stay in HBM / L2).
-template <int H, int TPW>
-int launch_rollout(int grid, int threads, hipStream_t s, const MlgEnvSpec& spec, const MlgEnvState& st,
-                   const AgentLayout& L, const Sides& sd, const MlgRunInfo& info, int tm) {
-    RolloutLds lay = make_rollout_lds(L, spec.U, spec.n_agents, true);
-    if (sd.ns == 1 && lay.total * 4 <= LDS_LIMIT_BYTES && !getenv("MLG_ROLLOUT_GLOBAL_WEIGHTS"))
-        return launch_rollout_t<H, TPW, true>(grid, threads, s, spec, st, L, sd, info, tm, lay);
-    lay = make_rollout_lds(L, spec.U, spec.n_agents, false);
-    return launch_rollout_t<H, TPW, false>(grid, threads, s, spec, st, L, sd, info, tm, lay);
-}
-
 // v7 with a compile-time shape when the layout matches one (StaticShape), else the generic v7.
 template <int SN, int SU>
 bool static_shape_matches(const AgentLayout& L, const RolloutLds2& lay) {
@@ -2202,42 +2191,173 @@ bool static_shape_matches(const AgentLayout& L, const RolloutLds2& lay) {
     return memcmp(&L, &S::L, sizeof(AgentLayout)) == 0 && memcmp(&lay, &S::lay, sizeof(RolloutLds2)) == 0;
 }
 
-template <int H, int V>
-int launch_rollout_v2(hipStream_t s, const MlgEnvSpec& spec, const MlgEnvState& st, const AgentLayout& L,
-                      const float* P, const MlgBatch& bt, const MlgRunInfo& info, float eps, int tm,
-                      const RolloutLds2& lay) {
-    const size_t bytes = (size_t)lay.total * 4;
-    auto kern = V == 7 ? rollout_v2_kernel<64, true> : rollout_v2_kernel<H>;
-    if (V == 7 && !getenv("MLG_ROLLOUT_GENERIC")) {
-        if (static_shape_matches<5, 10>(L, lay)) kern = rollout_v2_kernel<64, true, 5, 10>;
-        else if (static_shape_matches<3, 6>(L, lay)) kern = rollout_v2_kernel<64, true, 3, 6>;
-    }
-    const int threads = 512, rew = 16;
-    if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)bytes);
-        if (e != hipSuccess) return mlg::fail("rollout v2: LDS attribute (%zu B): %s", bytes, hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(kern, dim3((bt.B + rew - 1) / rew), dim3(threads), bytes, s, spec, st, L, P, bt, info, eps, tm,
-                       lay);
+// ---- the dispatch decision (host only): which kernel a rollout entry point launches -----------------------------
+// plan_rollout is the one place that decides; mlg_rollout / mlg_rollout_selfplay launch what it returns and
+// mlg_rollout_describe reports it.
+enum class Arm { V1, V2, V7, SP2, SP7, SP8 };
+
+struct RolloutPlan {
+    Arm arm;
+    int sn;         // agents of the compile-time shape instantiation (v7: 5 / 3, sp7 and sp8: 10 / 6); 0: runtime shape
+    int tpw, waves; // v1: agent tiles per wave, waves per workgroup
+    bool wlds;      // v1: the policy's weights in LDS (else read from global memory)
+    RolloutLds lay1;
+    RolloutLds2 lay2;
+    RolloutLdsSP laysp;
+    size_t lds_bytes;  // dynamic LDS of the launch
+    char name[24];
+};
+
+// The generic (v1) kernel: any H in {32, 64, 128}, one or two policy sides. Weights in LDS when one policy's image
+// fits (self-play holds two policies: weights stay in HBM / L2).
+int plan_rollout_v1(const AgentLayout& L, const MlgEnvSpec& spec, bool selfplay, RolloutPlan* p) {
+    const int ns = selfplay ? 2 : 1, nh = spec.n_agents / ns;
+    const int tiles = ns * ((RE * nh + 15) / 16);
+    p->arm = Arm::V1;
+    p->sn = 0;
+    p->waves = tiles < 8 ? tiles : 8;
+    p->tpw = (tiles + p->waves - 1) / p->waves;
+    MLG_REQUIRE(p->tpw <= 4, "rollout: %d agent tiles per wave > 4 (too many agents per env)", p->tpw);
+    MLG_REQUIRE(L.H == 32 || L.H == 64 || L.H == 128, "rollout: rnn_hidden_dim=%d unsupported (32, 64, 128)", L.H);
+    p->lay1 = make_rollout_lds(L, spec.U, spec.n_agents, true);
+    p->wlds = !selfplay && p->lay1.total * 4 <= LDS_LIMIT_BYTES && !getenv("MLG_ROLLOUT_GLOBAL_WEIGHTS");
+    if (!p->wlds) p->lay1 = make_rollout_lds(L, spec.U, spec.n_agents, false);
+    p->lds_bytes = (size_t)p->lay1.total * 4;
+    snprintf(p->name, sizeof p->name, "v1-%s/tpw%d", p->wlds ? "lds" : "global", p->tpw);
     return 0;
 }
 
-// v7 for H = 64 and v2 for H = 32 when the shape allows it (U <= 32, LDS fits), else v1. MLG_ROLLOUT_KERNEL=
-// v1|v2|v7 forces a variant (v1: the reference restatement, v2: fp32 compacted; both kept for the bit-identity tests).
-int pick_rollout(const AgentLayout& L, const MlgEnvSpec& spec, RolloutLds2* lay) {
+// mlg_rollout: v7 for H = 64 and v2 for H = 32 when the shape allows it (U <= 32, LDS fits), else v1.
+// MLG_ROLLOUT_KERNEL=v1|v2|v7 forces a variant (v1: the reference restatement, v2: fp32 compacted; both kept for the
+// bit-identity tests); MLG_ROLLOUT_GENERIC: the runtime-shape v7 also for the 5v5 / 3v3 plans.
+int plan_rollout_single(const AgentLayout& L, const MlgEnvSpec& spec, RolloutPlan* p) {
     const char* k = getenv("MLG_ROLLOUT_KERNEL");
     const int want = (k && k[0] == 'v') ? k[1] - '0' : (L.H == 64 ? 7 : 2);
-    if (want == 1 || (L.H != 64 && L.H != 32) || spec.U > 32) return 1;
-    *lay = make_rollout_lds2(L, spec.U, spec.n_agents, 16);
-    if (lay->total * 4 > LDS_LIMIT_BYTES) return 1;
+    if (want == 1 || (L.H != 64 && L.H != 32) || spec.U > 32) return plan_rollout_v1(L, spec, false, p);
+    p->lay2 = make_rollout_lds2(L, spec.U, spec.n_agents, 16);
+    if (p->lay2.total * 4 > LDS_LIMIT_BYTES) return plan_rollout_v1(L, spec, false, p);
+    p->arm = Arm::V2;
+    p->sn = 0;
     if (want == 7 && L.H == 64) {
-        *lay = make_rollout_lds2(L, spec.U, spec.n_agents, 16, 2, 1);
-        if (lay->total * 4 <= LDS_LIMIT_BYTES) return 7;
-        *lay = make_rollout_lds2(L, spec.U, spec.n_agents, 16);
+        const RolloutLds2 l7 = make_rollout_lds2(L, spec.U, spec.n_agents, 16, 2, 1);
+        if (l7.total * 4 <= LDS_LIMIT_BYTES) {
+            p->arm = Arm::V7;
+            p->lay2 = l7;
+            if (!getenv("MLG_ROLLOUT_GENERIC")) {
+                if (static_shape_matches<5, 10>(L, l7)) p->sn = 5;
+                else if (static_shape_matches<3, 6>(L, l7)) p->sn = 3;
+            }
+        }
     }
-    return 2;
+    p->lds_bytes = (size_t)p->lay2.total * 4;
+    snprintf(p->name, sizeof p->name, "%s", p->arm == Arm::V2 ? "v2" : p->sn ? "v7-static" : "v7");
+    return 0;
 }
+
+// mlg_rollout_selfplay (two policies): sp8 (one round of 16-env workgroups) for the static 5v5 / 3v3 self-play shapes
+// at H = 64, else sp7 (v7 agent phases, 8 envs per workgroup) for H = 64, else sp2 (v2 structure) when the shape
+// allows it, else the generic v1 kernel. MLG_ROLLOUT_KERNEL=v1 | sp2 | sp7 forces one.
+int plan_rollout_selfplay(const AgentLayout& L, const MlgEnvSpec& spec, RolloutPlan* p) {
+    const char* k = getenv("MLG_ROLLOUT_KERNEL");
+    const bool force_v1 = k && k[0] == 'v' && k[1] == '1', force_sp2 = k && !strcmp(k, "sp2");
+    const bool force_sp7 = k && !strcmp(k, "sp7");
+    const bool generic = getenv("MLG_ROLLOUT_GENERIC") != nullptr;
+    if (!force_v1 && !force_sp2 && !force_sp7 && L.H == 64 && !generic) {
+        p->sn = static_shape_matches_sp8<10, 10>(L, spec.n_agents) ? 10
+                : static_shape_matches_sp8<6, 6>(L, spec.n_agents) ? 6 : 0;
+        if (p->sn) {
+            p->arm = Arm::SP8;
+            p->lds_bytes = (size_t)(p->sn == 10 ? StaticShapeSP8<10, 10>::lay.total : StaticShapeSP8<6, 6>::lay.total) * 4;
+            snprintf(p->name, sizeof p->name, "sp8");
+            return 0;
+        }
+    }
+    const RolloutLdsSP l7 = make_rollout_lds_sp(L, spec.U, spec.n_agents, true);
+    if (!force_v1 && !force_sp2 && L.H == 64 && L.Dob <= 32 * SP7_MAXKK && l7.total * 4 <= LDS_LIMIT_BYTES) {
+        p->arm = Arm::SP7;
+        p->laysp = l7;
+        p->sn = 0;  // runtime shapes; the 5v5 / 3v3 self-play plans as constants
+        if (!generic) {
+            if (static_shape_matches_sp<10, 10>(L, l7)) p->sn = 10;
+            else if (static_shape_matches_sp<6, 6>(L, l7)) p->sn = 6;
+        }
+        p->lds_bytes = (size_t)l7.total * 4;
+        snprintf(p->name, sizeof p->name, "%s", p->sn ? "sp7-static" : "sp7");
+        return 0;
+    }
+    const RolloutLdsSP lsp = make_rollout_lds_sp(L, spec.U, spec.n_agents);
+    if (!force_v1 && (L.H == 64 || L.H == 32) && spec.U <= 32 && lsp.total * 4 <= LDS_LIMIT_BYTES) {
+        p->arm = Arm::SP2;
+        p->laysp = lsp;
+        p->sn = 0;
+        p->lds_bytes = (size_t)lsp.total * 4;
+        snprintf(p->name, sizeof p->name, "sp2");
+        return 0;
+    }
+    return plan_rollout_v1(L, spec, true, p);
+}
+
+int plan_rollout(const AgentLayout& L, const MlgEnvSpec& spec, bool selfplay, RolloutPlan* p) {
+    return selfplay ? plan_rollout_selfplay(L, spec, p) : plan_rollout_single(L, spec, p);
+}
+
+// Raises the kernel's dynamic LDS limit when the launch needs more than the 64 KiB default.
+template <typename K>
+int allow_lds(K kern, size_t bytes, const char* who) {
+    if (bytes <= 64 * 1024) return 0;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)bytes);
+    if (e != hipSuccess) return mlg::fail("%s: LDS attribute (%zu B): %s", who, bytes, hipGetErrorString(e));
+    return 0;
+}
+
+template <int H, int TPW, bool WLDS>
+int launch_rollout_t(hipStream_t s, const MlgEnvSpec& spec, const MlgEnvState& st, const AgentLayout& L,
+                     const Sides& sd, const MlgRunInfo& info, int tm, const RolloutPlan& p) {
+    auto kern = rollout_kernel<H, TPW, WLDS>;
+    if (int rc = allow_lds(kern, p.lds_bytes, "rollout")) return rc;
+    hipLaunchKernelGGL(kern, dim3((st.B + RE - 1) / RE), dim3(p.waves * 64), p.lds_bytes, s, spec, st, L, sd, info, tm,
+                       p.lay1);
+    return 0;
+}
+
+template <int H>
+int launch_rollout_h(hipStream_t s, const MlgEnvSpec& spec, const MlgEnvState& st, const AgentLayout& L,
+                     const Sides& sd, const MlgRunInfo& info, int tm, const RolloutPlan& p) {
+#define MLG_RO(TT)                                                                 \
+    return p.wlds ? launch_rollout_t<H, TT, true>(s, spec, st, L, sd, info, tm, p) \
+                  : launch_rollout_t<H, TT, false>(s, spec, st, L, sd, info, tm, p)
+    if (p.tpw == 1) MLG_RO(1);
+    if (p.tpw == 2) MLG_RO(2);
+    if (p.tpw == 3) MLG_RO(3);
+    MLG_RO(4);
+#undef MLG_RO
+}
+
+int launch_rollout_v1(hipStream_t s, const MlgEnvSpec& spec, const MlgEnvState& st, const AgentLayout& L,
+                      const Sides& sd, const MlgRunInfo& info, int tm, const RolloutPlan& p) {
+    int rc = L.H == 64   ? launch_rollout_h<64>(s, spec, st, L, sd, info, tm, p)
+             : L.H == 32 ? launch_rollout_h<32>(s, spec, st, L, sd, info, tm, p)
+                         : launch_rollout_h<128>(s, spec, st, L, sd, info, tm, p);
+    if (rc) return rc;
+    return mlg::check_launch("rollout_kernel");
+}
+
+int launch_rollout_v2(hipStream_t s, const MlgEnvSpec& spec, const MlgEnvState& st, const AgentLayout& L,
+                      const float* P, const MlgBatch& bt, const MlgRunInfo& info, float eps, int tm,
+                      const RolloutPlan& p) {
+    auto kern = L.H == 64 ? rollout_v2_kernel<64> : rollout_v2_kernel<32>;
+    if (p.arm == Arm::V7)
+        kern = p.sn == 5   ? rollout_v2_kernel<64, true, 5, 10>
+               : p.sn == 3 ? rollout_v2_kernel<64, true, 3, 6>
+                           : rollout_v2_kernel<64, true>;
+    const int threads = 512, rew = 16;
+    if (int rc = allow_lds(kern, p.lds_bytes, "rollout v2")) return rc;
+    hipLaunchKernelGGL(kern, dim3((bt.B + rew - 1) / rew), dim3(threads), p.lds_bytes, s, spec, st, L, P, bt, info, eps,
+                       tm, p.lay2);
+    return mlg::check_launch("rollout_v2_kernel");
+}
+
 
 }  // namespace
 
@@ -2354,85 +2474,14 @@ int check_rollout_batch(const MlgBatch* batch, const MlgEnvSpec* spec, const Mlg
     return 0;
 }
 
-// The generic (v1) kernel: any H in {32, 64, 128}, one or two policy sides.
-int dispatch_rollout_v1(hipStream_t s, const MlgEnvSpec& spec, const MlgEnvState& st, const AgentLayout& L,
-                        const Sides& sd, const MlgRunInfo& info, int test_mode) {
-    const int tiles = sd.ns * ((RE * sd.nh + 15) / 16);
-    const int W = tiles < 8 ? tiles : 8;
-    const int tpw = (tiles + W - 1) / W;
-    const int grid = (st.B + RE - 1) / RE;
-    const int threads = W * 64;
-    int rc = 0;
-    MLG_REQUIRE(tpw <= 4, "rollout: %d agent tiles per wave > 4 (too many agents per env)", tpw);
-#define MLG_RO(HH, TT) rc = launch_rollout<HH, TT>(grid, threads, s, spec, st, L, sd, info, test_mode)
-    if (L.H == 64) {
-        if (tpw == 1) MLG_RO(64, 1);
-        else if (tpw == 2) MLG_RO(64, 2);
-        else if (tpw == 3) MLG_RO(64, 3);
-        else MLG_RO(64, 4);
-    } else if (L.H == 32) {
-        if (tpw == 1) MLG_RO(32, 1);
-        else if (tpw == 2) MLG_RO(32, 2);
-        else if (tpw == 3) MLG_RO(32, 3);
-        else MLG_RO(32, 4);
-    } else if (L.H == 128) {
-        if (tpw == 1) MLG_RO(128, 1);
-        else if (tpw == 2) MLG_RO(128, 2);
-        else if (tpw == 3) MLG_RO(128, 3);
-        else MLG_RO(128, 4);
-    } else {
-        return mlg::fail("rollout: rnn_hidden_dim=%d unsupported (32, 64, 128)", L.H);
-    }
-#undef MLG_RO
-    if (rc) return rc;
-    return mlg::check_launch("rollout_kernel");
-}
-
-}  // namespace
-
-extern "C" int mlg_rollout(const MlgEnvSpec* spec, MlgEnvState* st, const MlgAgentDims* dims, const float* packed,
-                           MlgBatch* batch, MlgRunInfo* info, float epsilon, int32_t test_mode, void* stream) {
-    if (check_spec(spec) || check_state(st) || check_agent_dims(dims)) return 1;
-    MLG_REQUIRE(packed && batch && info, "rollout: null pointer");
-    if (check_rollout_batch(batch, spec, st, "rollout")) return 1;
-    MLG_REQUIRE(info->ep_len && info->ret && info->won && info->draw, "rollout: run info has null tensors");
+int check_rollout_dims(const MlgEnvSpec* spec, const MlgAgentDims* dims) {
     MLG_REQUIRE(dims->n_agents == spec->n_agents && dims->n_actions == spec->n_actions && dims->d_obs == 8 * spec->U,
                 "rollout: agent dims do not match env spec (N=%d/%d A=%d/%d d_obs=%d/%d)", dims->n_agents,
                 spec->n_agents, dims->n_actions, spec->n_actions, dims->d_obs, 8 * spec->U);
-    const AgentLayout L = make_agent_layout(*dims);
-    hipStream_t s = (hipStream_t)stream;
-    const float eps = test_mode ? 0.f : epsilon;
-    RolloutLds2 lay2;
-    const int variant = pick_rollout(L, *spec, &lay2);
-    if (variant > 1) {
-        const bool h64 = dims->hidden == 64;
-        int rc = 0;
-#define MLG_V(VV) rc = h64 ? launch_rollout_v2<64, VV>(s, *spec, *st, L, packed, *batch, *info, eps, test_mode, lay2) \
-                           : launch_rollout_v2<32, VV>(s, *spec, *st, L, packed, *batch, *info, eps, test_mode, lay2)
-        if (variant == 7) rc = launch_rollout_v2<64, 7>(s, *spec, *st, L, packed, *batch, *info, eps, test_mode, lay2);
-        else MLG_V(2);
-#undef MLG_V
-        if (rc) return rc;
-        return mlg::check_launch("rollout_v2_kernel");
-    }
-    Sides sd;
-    sd.bt[0] = sd.bt[1] = *batch;
-    sd.P[0] = sd.P[1] = packed;
-    sd.eps[0] = sd.eps[1] = eps;
-    sd.ns = 1;
-    sd.nh = spec->n_agents;
-    return dispatch_rollout_v1(s, *spec, *st, L, sd, *info, test_mode);
+    return 0;
 }
 
-extern "C" int mlg_rollout_selfplay(const MlgEnvSpec* spec, MlgEnvState* st, const MlgAgentDims* dims,
-                                    const float* home_packed, const float* away_packed, MlgBatch* home, MlgBatch* away,
-                                    MlgRunInfo* info, float eps_home, float eps_away, int32_t test_mode, void* stream) {
-    if (check_spec(spec) || check_state(st) || check_agent_dims(dims)) return 1;
-    MLG_REQUIRE(home_packed && away_packed && info, "rollout_selfplay: null pointer");
-    if (check_rollout_batch(home, spec, st, "rollout_selfplay (home)") ||
-        check_rollout_batch(away, spec, st, "rollout_selfplay (away)"))
-        return 1;
-    MLG_REQUIRE(info->ep_len && info->ret && info->won && info->draw, "rollout_selfplay: run info has null tensors");
+int check_selfplay_dims(const MlgEnvSpec* spec, const MlgAgentDims* dims) {
     MLG_REQUIRE(spec->n_policy_teams == 2 && spec->n_agents % 2 == 0,
                 "rollout_selfplay: %d agents in %d policy teams do not fit the symmetric two-team scenario "
                 "(stepper_utils.py:9)", spec->n_agents, spec->n_policy_teams);
@@ -2445,7 +2494,58 @@ extern "C" int mlg_rollout_selfplay(const MlgEnvSpec* spec, MlgEnvState* st, con
                         spec->team[spec->agent_unit[nh + a]] == 1 - spec->policy_team,
                     "rollout_selfplay: agents 0..%d must be the home team, %d..%d the away team", nh - 1, nh,
                     2 * nh - 1);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int mlg_rollout_describe(const MlgEnvSpec* spec, const MlgAgentDims* dims, int32_t selfplay, char* name,
+                                    int32_t name_cap, int64_t* lds_bytes) {
+    if (check_spec(spec) || check_agent_dims(dims)) return 1;
+    MLG_REQUIRE(name && name_cap > 0 && lds_bytes, "rollout_describe: null output");
+    if (selfplay ? check_selfplay_dims(spec, dims) : check_rollout_dims(spec, dims)) return 1;
+    RolloutPlan plan;
+    if (int rc = plan_rollout(make_agent_layout(*dims), *spec, selfplay != 0, &plan)) return rc;
+    MLG_REQUIRE((size_t)name_cap > strlen(plan.name), "rollout_describe: name buffer of %d bytes too small", name_cap);
+    strcpy(name, plan.name);
+    *lds_bytes = (int64_t)plan.lds_bytes;
+    return 0;
+}
+
+extern "C" int mlg_rollout(const MlgEnvSpec* spec, MlgEnvState* st, const MlgAgentDims* dims, const float* packed,
+                           MlgBatch* batch, MlgRunInfo* info, float epsilon, int32_t test_mode, void* stream) {
+    if (check_spec(spec) || check_state(st) || check_agent_dims(dims)) return 1;
+    MLG_REQUIRE(packed && batch && info, "rollout: null pointer");
+    if (check_rollout_batch(batch, spec, st, "rollout")) return 1;
+    MLG_REQUIRE(info->ep_len && info->ret && info->won && info->draw, "rollout: run info has null tensors");
+    if (check_rollout_dims(spec, dims)) return 1;
     const AgentLayout L = make_agent_layout(*dims);
+    hipStream_t s = (hipStream_t)stream;
+    const float eps = test_mode ? 0.f : epsilon;
+    RolloutPlan plan;
+    if (int rc = plan_rollout(L, *spec, false, &plan)) return rc;
+    if (plan.arm != Arm::V1) return launch_rollout_v2(s, *spec, *st, L, packed, *batch, *info, eps, test_mode, plan);
+    Sides sd;
+    sd.bt[0] = sd.bt[1] = *batch;
+    sd.P[0] = sd.P[1] = packed;
+    sd.eps[0] = sd.eps[1] = eps;
+    sd.ns = 1;
+    sd.nh = spec->n_agents;
+    return launch_rollout_v1(s, *spec, *st, L, sd, *info, test_mode, plan);
+}
+
+extern "C" int mlg_rollout_selfplay(const MlgEnvSpec* spec, MlgEnvState* st, const MlgAgentDims* dims,
+                                    const float* home_packed, const float* away_packed, MlgBatch* home, MlgBatch* away,
+                                    MlgRunInfo* info, float eps_home, float eps_away, int32_t test_mode, void* stream) {
+    if (check_spec(spec) || check_state(st) || check_agent_dims(dims)) return 1;
+    MLG_REQUIRE(home_packed && away_packed && info, "rollout_selfplay: null pointer");
+    if (check_rollout_batch(home, spec, st, "rollout_selfplay (home)") ||
+        check_rollout_batch(away, spec, st, "rollout_selfplay (away)"))
+        return 1;
+    MLG_REQUIRE(info->ep_len && info->ret && info->won && info->draw, "rollout_selfplay: run info has null tensors");
+    if (check_selfplay_dims(spec, dims)) return 1;
+    const AgentLayout L = make_agent_layout(*dims);
+    hipStream_t s = (hipStream_t)stream;
     Sides sd;
     sd.bt[0] = *home;
     sd.bt[1] = *away;
@@ -2454,59 +2554,32 @@ extern "C" int mlg_rollout_selfplay(const MlgEnvSpec* spec, MlgEnvState* st, con
     sd.eps[0] = test_mode ? 0.f : eps_home;
     sd.eps[1] = test_mode ? 0.f : eps_away;
     sd.ns = 2;
-    sd.nh = nh;
-    // self-play kernels (two policies): sp8 (one round of 16-env workgroups) for the static 5v5 / 3v3 self-play shapes
-    // at H = 64, else sp7 (v7 agent phases, 8 envs per workgroup) for H = 64, else sp2 (v2 structure) when the shape
-    // allows it, else the generic v1 kernel. MLG_ROLLOUT_KERNEL=v1 | sp2 | sp7 forces one.
-    const char* k = getenv("MLG_ROLLOUT_KERNEL");
-    const bool force_v1 = k && k[0] == 'v' && k[1] == '1', force_sp2 = k && !strcmp(k, "sp2");
-    const bool force_sp7 = k && !strcmp(k, "sp7");
-    if (!force_v1 && !force_sp2 && !force_sp7 && L.H == 64 && !getenv("MLG_ROLLOUT_GENERIC")) {
-        void (*kern8)(MlgEnvSpec, MlgEnvState, const float*, const float*, MlgBatch, MlgBatch, MlgRunInfo, float, float,
-                      int) = nullptr;
-        size_t bytes = 0;
-        if (static_shape_matches_sp8<10, 10>(L, spec->n_agents)) {
-            kern8 = rollout_sp8_kernel<10, 10>;
-            bytes = (size_t)StaticShapeSP8<10, 10>::lay.total * 4;
-        } else if (static_shape_matches_sp8<6, 6>(L, spec->n_agents)) {
-            kern8 = rollout_sp8_kernel<6, 6>;
-            bytes = (size_t)StaticShapeSP8<6, 6>::lay.total * 4;
-        }
-        if (kern8) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern8),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-            if (e != hipSuccess)
-                return mlg::fail("rollout_selfplay: LDS attribute (%zu B): %s", bytes, hipGetErrorString(e));
-            hipLaunchKernelGGL(kern8, dim3((st->B + RS8 - 1) / RS8), dim3(512), bytes, (hipStream_t)stream, *spec, *st,
-                               home_packed, away_packed, *home, *away, *info, sd.eps[0], sd.eps[1], test_mode);
-            return mlg::check_launch("rollout_sp8_kernel");
-        }
+    sd.nh = spec->n_agents / 2;
+    RolloutPlan plan;
+    if (int rc = plan_rollout(L, *spec, true, &plan)) return rc;
+    const size_t bytes = plan.lds_bytes;
+    if (plan.arm == Arm::SP8) {
+        auto kern = plan.sn == 10 ? rollout_sp8_kernel<10, 10> : rollout_sp8_kernel<6, 6>;
+        if (int rc = allow_lds(kern, bytes, "rollout_selfplay")) return rc;
+        hipLaunchKernelGGL(kern, dim3((st->B + RS8 - 1) / RS8), dim3(512), bytes, s, *spec, *st, home_packed,
+                           away_packed, *home, *away, *info, sd.eps[0], sd.eps[1], test_mode);
+        return mlg::check_launch("rollout_sp8_kernel");
     }
-    const RolloutLdsSP l7 = make_rollout_lds_sp(L, spec->U, spec->n_agents, true);
-    if (!force_v1 && !force_sp2 && L.H == 64 && L.Dob <= 32 * SP7_MAXKK && l7.total * 4 <= LDS_LIMIT_BYTES) {
-        const size_t bytes = (size_t)l7.total * 4;
-        auto kern = rollout_sp7_kernel<0, 0>;  // runtime shapes; the 5v5 / 3v3 self-play plans as constants
-        if (!getenv("MLG_ROLLOUT_GENERIC")) {
-            if (static_shape_matches_sp<10, 10>(L, l7)) kern = rollout_sp7_kernel<10, 10>;
-            else if (static_shape_matches_sp<6, 6>(L, l7)) kern = rollout_sp7_kernel<6, 6>;
-        }
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return mlg::fail("rollout_selfplay: LDS attribute (%zu B): %s", bytes, hipGetErrorString(e));
-        hipLaunchKernelGGL(kern, dim3((st->B + RS - 1) / RS), dim3(512), bytes, (hipStream_t)stream, *spec, *st, L,
-                           home_packed, away_packed, *home, *away, *info, sd.eps[0], sd.eps[1], test_mode, l7);
+    if (plan.arm == Arm::SP7) {
+        auto kern = plan.sn == 10 ? rollout_sp7_kernel<10, 10>
+                    : plan.sn == 6 ? rollout_sp7_kernel<6, 6>
+                                   : rollout_sp7_kernel<0, 0>;
+        if (int rc = allow_lds(kern, bytes, "rollout_selfplay")) return rc;
+        hipLaunchKernelGGL(kern, dim3((st->B + RS - 1) / RS), dim3(512), bytes, s, *spec, *st, L, home_packed,
+                           away_packed, *home, *away, *info, sd.eps[0], sd.eps[1], test_mode, plan.laysp);
         return mlg::check_launch("rollout_sp7_kernel");
     }
-    const RolloutLdsSP lsp = make_rollout_lds_sp(L, spec->U, spec->n_agents);
-    if (!force_v1 && (L.H == 64 || L.H == 32) && spec->U <= 32 && lsp.total * 4 <= LDS_LIMIT_BYTES) {
-        const size_t bytes = (size_t)lsp.total * 4;
+    if (plan.arm == Arm::SP2) {
         auto kern = L.H == 64 ? rollout_sp_kernel<64> : rollout_sp_kernel<32>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return mlg::fail("rollout_selfplay: LDS attribute (%zu B): %s", bytes, hipGetErrorString(e));
-        hipLaunchKernelGGL(kern, dim3((st->B + RS - 1) / RS), dim3(512), bytes, (hipStream_t)stream, *spec, *st, L,
-                           home_packed, away_packed, *home, *away, *info, sd.eps[0], sd.eps[1], test_mode, lsp);
+        if (int rc = allow_lds(kern, bytes, "rollout_selfplay")) return rc;
+        hipLaunchKernelGGL(kern, dim3((st->B + RS - 1) / RS), dim3(512), bytes, s, *spec, *st, L, home_packed,
+                           away_packed, *home, *away, *info, sd.eps[0], sd.eps[1], test_mode, plan.laysp);
         return mlg::check_launch("rollout_sp_kernel");
     }
-    return dispatch_rollout_v1((hipStream_t)stream, *spec, *st, L, sd, *info, test_mode);
+    return launch_rollout_v1(s, *spec, *st, L, sd, *info, test_mode, plan);
 }

@@ -144,6 +144,7 @@ SIGNATURES = {
     "mlg_env_observe": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "mlg_rollout": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
     "mlg_rollout_selfplay": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _I, _P]),
+    "mlg_rollout_describe": (ctypes.c_int, [_P, _P, _I, _P, _I, _P]),
     "mlg_agent_forward": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "mlg_mac_forward": (ctypes.c_int, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "mlg_select_actions": (ctypes.c_int, [_P, _P, _I, _I, _I, _P, _P, _I, ctypes.c_float, _P, _P, _P]),
@@ -226,6 +227,19 @@ def call(name: str, *args) -> None:
     rc = getattr(lib, name)(*args)
     if rc != 0:
         raise NativeError(f"{name} failed: {lib.mlg_last_error().decode()}")
+
+
+def rollout_describe(spec: MlgEnvSpec, dims: MlgAgentDims, selfplay: bool = False) -> tuple[str, int]:
+    """(kernel name, dynamic LDS bytes) of the launch mlg_rollout / mlg_rollout_selfplay would make for this spec
+    and agent dims under the current MLG_ROLLOUT_* environment (mlg_rollout_describe: host only, needs no GPU)."""
+    lib = load()
+    name = ctypes.create_string_buffer(32)
+    lds = ctypes.c_int64(0)
+    rc = lib.mlg_rollout_describe(ctypes.byref(spec), ctypes.byref(dims), int(bool(selfplay)), name, len(name),
+                                  ctypes.byref(lds))
+    if rc != 0:
+        raise NativeError(f"mlg_rollout_describe failed: {lib.mlg_last_error().decode()}")
+    return name.value.decode(), int(lds.value)
 
 
 def stream_ptr(device=None) -> int:

@@ -23,6 +23,9 @@ class EntityParallelStepper(ParallelStepper):
     def _to_mlg(self, batch):
         return mlg_entity_batch(batch)
 
+    def describe_rollout(self):
+        raise NotImplementedError("mlg_refil_rollout has its own dispatch: mlg_rollout_describe does not cover it")
+
     def _rollout(self, mb, run_info, epsilon, test_mode):
         agent = self.home_mac.agent
         st = self.envs.to_c()

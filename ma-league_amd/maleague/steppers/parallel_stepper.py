@@ -188,6 +188,17 @@ class ParallelStepper(EnvStepper):
                      _native.ptr(agent.packed()), _native.byref(mb), _native.byref(run_info), float(epsilon),
                      int(bool(test_mode)), _native.stream_ptr(self.device))
 
+    _SELFPLAY = False  # which entry point run() calls: mlg_rollout / mlg_rollout_selfplay
+
+    def describe_rollout(self):
+        """(kernel name, dynamic LDS bytes) of the launch the next run() makes with this env spec and the home MAC's
+        agent under the current MLG_ROLLOUT_* environment (host only; the entry point decides by the same function)."""
+        if self.home_mac is None:
+            raise MultiAgentControllerNotInitialized()
+        if getattr(self.home_mac, "agent_output_type", "q") == "pi_logits":
+            raise NotImplementedError("mlg_rollout_policy has one kernel: there is no dispatch to describe")
+        return _native.rollout_describe(self._cspec, self.home_mac.agent.dims(), self._SELFPLAY)
+
     def initialize(self, scheme, groups, preprocess, home_mac, away_mac=None):
         if away_mac is not None:
             raise NotImplementedError("ParallelStepper drives one policy; self-play (home + away MAC) is "

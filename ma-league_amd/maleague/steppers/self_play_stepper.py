@@ -23,6 +23,7 @@ from .parallel_stepper import LazyEnvInfos, ParallelStepper
 class SelfPlayParallelStepper(ParallelStepper):
     # zero-copy run summaries as ParallelStepper: the league's record_runs kernel reads each run's wins straight from
     # the pinned summary slot (LeagueInstance.play -> last_run_info)
+    _SELFPLAY = True
 
     def __init__(self, args, logger, log_start_t=0):
         super().__init__(args, logger, log_start_t)

@@ -96,6 +96,248 @@ def ref_entity_envs_for(spec, B, seed=0):
             for b in range(B)]
 
 
+_UNIT_CYCLE = ("TR", "AR", "HR", "TM")
+
+
+def shape_plan(name, self_play=False):
+    """match_build_plan for the rollout shape tests: a built-in plan name, or "KvK" (K units per side, unit k of a
+    side is TR AR HR TM cyclically, scripted team first), "5v7" (5 policy agents against 7 scripted units, scripted
+    team first) or "3v5" (3 policy agents listed first, team 0, against 5 scripted units). self_play: both teams
+    policy-controlled (symmetric plans only)."""
+    from maleague.envs.plans import available, builtin_plan, team_from_codes
+    if name in available():
+        return builtin_plan(name, self_play=True) if self_play else name
+    codes = lambda k: " ".join(_UNIT_CYCLE[i % 4] for i in range(k))  # noqa: E731
+    if name == "5v7":
+        assert not self_play
+        return [team_from_codes(codes(7), True), team_from_codes(codes(5), False)]
+    if name == "3v5":
+        assert not self_play
+        return [team_from_codes(codes(3), False), team_from_codes(codes(5), True)]
+    k, k2 = (int(x) for x in name.split("v"))
+    assert k == k2, name
+    return [team_from_codes(codes(k), not self_play), team_from_codes(codes(k), False)]
+
+
+def drqn_dims(spec, hidden, self_play=False):
+    """The MlgAgentDims of a BasicMAC's DRQN agent (obs_last_action and obs_agent_id on) over the env ``spec``: what
+    agent.dims() returns on a built stepper, without building one."""
+    from maleague import _native
+    N = spec.n_agents // 2 if self_play else spec.n_agents
+    return _native.MlgAgentDims(d_obs=8 * spec.U, n_actions=spec.n_actions, n_agents=N, hidden=hidden,
+                                d_in=8 * spec.U + spec.n_actions + N, obs_last_action=1, obs_agent_id=1)
+
+
+Q_TOL = 1e-4  # the project's bar for Q values and hidden states (fp32 kernels vs the oracle)
+
+
+def build_stepper(device, plan="medium_1h_4t", B=48, episode_limit=40, seed=5, **kw):
+    """A ParallelStepper over ``plan`` (a built-in name or a list of two team dicts) with a freshly seeded BasicMAC."""
+    import torch
+    from maleague.components.episode_batch import EpisodeBatch
+    from maleague.controllers import BasicMAC
+    from maleague.custom_logging import MainLogger
+    from maleague.steppers import ParallelStepper
+    args = qmix_args(batch_size_run=B, seed=seed, env_args={"match_build_plan": plan, "grid_size": 20,
+                                                            "stochastic_spawns": True, "episode_limit": episode_limit},
+                     **kw)
+    stepper = ParallelStepper(args, MainLogger())
+    info = stepper.get_env_info()
+    args.n_agents, args.n_actions, args.state_shape = info["n_agents"], info["n_actions"], info["state_shape"]
+    scheme, groups, preprocess = scheme_for(info, torch)
+    proto = EpisodeBatch(scheme, groups, 1, 2, preprocess=preprocess, device=device)
+    torch.manual_seed(seed)
+    mac = BasicMAC(proto.scheme, groups, args)
+    stepper.initialize(scheme, groups, preprocess, mac)
+    return stepper, mac, args
+
+
+def oracle_q(mac, tb, N, T, dtype=None):
+    """The oracle DRQN's Q [B, T, N, A] along a recorded batch (LR.mac_unroll) with ``mac``'s parameters: fp32 by
+    default, or params, inputs and h0 cast to ``dtype`` (torch.float64: strictly more precise than the kernels)."""
+    import torch
+    import learner_ref as LR
+    params = {k: v.detach().cpu() for k, v in mac.agent.state_dict().items()}
+    h0 = None
+    if dtype is not None:
+        params = {k: v.to(dtype) for k, v in params.items()}
+        tb = {k: tb[k].to(dtype) for k in ("obs", "actions_onehot")}
+        h0 = torch.zeros(tb["obs"].shape[0] * N, params["gru.weight_hh"].shape[1], dtype=dtype)
+    with torch.no_grad():
+        q, _ = LR.mac_unroll(params, tb, N, T=T, h0=h0)
+    return q.numpy()
+
+
+def check_run(stepper, mac, args, batch, infos, episode, test_mode, eps, envs=None, dtype=None, nb=None):
+    """Teacher-forced env replay + oracle agent check of a run; ``envs``: the env indices to check (all by
+    default; a subset for the 4096-env headline shape). ``dtype``: the oracle unroll's precision (oracle_q).
+    ``nb``: the recorded batch as host arrays when it is not ``batch``'s own copy. Returns the counts (greedy picks
+    checked, near ties among them, epsilon draws)."""
+    import envref
+    import torch
+    spec = stepper.spec
+    B, N, A, T1 = stepper.batch_size, spec.n_agents, spec.n_actions, stepper.episode_limit + 1
+    sub = list(range(B)) if envs is None else [int(e) for e in envs]
+    nb = np_batch(batch) if nb is None else nb
+    ep_len = stepper.last_run["ep_len"].numpy()
+    rets = stepper.last_run["returns"].numpy()
+    assert (ep_len >= 1).all() and (ep_len <= stepper.episode_limit).all()
+    assert stepper.t == ep_len.max()
+    # --- env side, teacher forced: replay the recorded actions through the C oracle ---
+    refs = ref_envs_for(spec, B, seed=args.seed)
+    for b in sub:
+        r = refs[b]
+        r.episode = episode
+        r.reset()
+        L = int(ep_len[b])
+        np.testing.assert_array_equal(nb["obs"][b, 0], r.obs())
+        np.testing.assert_array_equal(nb["state"][b, 0], r.state())
+        np.testing.assert_array_equal(nb["avail_actions"][b, 0], r.avail())
+        ret = 0.0
+        for t in range(L):
+            rew, done, info = r.step(nb["actions"][b, t, :, 0])
+            ret += rew[0]
+            assert nb["reward"][b, t, 0] == np.float32(rew[0])
+            assert nb["terminated"][b, t, 0] == int(done) and done == (t == L - 1)
+            np.testing.assert_array_equal(nb["obs"][b, t + 1], r.obs())
+            np.testing.assert_array_equal(nb["state"][b, t + 1], r.state())
+            np.testing.assert_array_equal(nb["avail_actions"][b, t + 1], r.avail())
+        assert rets[b] == np.float32(ret)
+        np.testing.assert_array_equal(nb["filled"][b, :, 0], (np.arange(T1) <= L).astype(np.int64))
+        # actions recorded for t = 0..L (the final one after termination), zero beyond
+        assert (nb["actions"][b, L + 1:] == 0).all() and (nb["actions_onehot"][b, L + 1:] == 0).all()
+        oh = np.zeros((L + 1, N, A), np.float32)
+        oh[np.arange(L + 1)[:, None], np.arange(N)[None, :], nb["actions"][b, :L + 1, :, 0]] = 1
+        np.testing.assert_array_equal(nb["actions_onehot"][b, :L + 1], oh)
+        assert (nb["reward"][b, L:] == 0).all() and (nb["terminated"][b, L:] == 0).all()
+    assert len(infos) == B
+    # --- agent side: oracle Q on the recorded batch; greedy / epsilon picks bit-exact ---
+    tb = {k: torch.from_numpy(v[sub]) for k, v in nb.items()}
+    Tm = int(ep_len[sub].max()) + 1
+    q = dict(zip(sub, oracle_q(mac, tb, N, Tm, dtype)))
+    n_checked = n_random = n_tie = 0
+    for b in sub:
+        for t in range(int(ep_len[b]) + 1):
+            for n in range(N):
+                a = int(nb["actions"][b, t, n, 0])
+                av = nb["avail_actions"][b, t, n]
+                if not test_mode and eps > 0:
+                    key = envref.env_key(args.seed, b)
+                    r1 = envref.rng(key, envref.ctr(episode, t, 2, n))
+                    if envref.u01(r1) < np.float32(eps):
+                        r2 = envref.rng(key, envref.ctr(episode, t, 3, n))
+                        assert a == envref.random_available(av.tolist(), r2)
+                        n_random += 1
+                        continue
+                m = np.where(av == 0, -np.inf, q[b][t, n])
+                g = int(np.argmax(m))
+                srt = np.sort(m)
+                if srt[-1] - srt[-2] > Q_TOL:
+                    assert a == g, (b, t, n, a, g)
+                else:  # near-tie within fp32 tolerance: chosen must be (numerically) a max
+                    assert m[a] >= srt[-1] - Q_TOL
+                    n_tie += 1
+                n_checked += 1
+    assert n_checked > 0
+    if not test_mode and eps > 0.2:
+        assert n_random > 0
+    return {"greedy": n_checked, "near_ties": n_tie, "epsilon_draws": n_random}
+
+
+def sp_args(B, episode_limit, seed, plan="medium_1h_4t", **kw):
+    from maleague.envs.plans import builtin_plan
+    mbp = builtin_plan(plan, self_play=True) if isinstance(plan, str) else plan
+    return qmix_args(batch_size_run=B, seed=seed,
+                     env_args={"match_build_plan": mbp, "grid_size": 20,
+                               "stochastic_spawns": True, "episode_limit": episode_limit}, **kw)
+
+
+def build_selfplay(device, plan="medium_1h_4t", B=48, episode_limit=40, seed=5, **kw):
+    """A SelfPlayParallelStepper over ``plan`` (both teams policy-controlled) with two freshly seeded BasicMACs."""
+    import torch
+    from maleague.components.episode_batch import EpisodeBatch
+    from maleague.controllers import BasicMAC
+    from maleague.custom_logging import MainLogger
+    from maleague.steppers import SelfPlayParallelStepper
+    args = sp_args(B, episode_limit, seed, plan, **kw)
+    stepper = SelfPlayParallelStepper(args, MainLogger())
+    info = stepper.get_env_info()
+    assert info["n_agents"] % 2 == 0
+    args.n_agents, args.n_actions, args.state_shape = info["n_agents"] // 2, info["n_actions"], info["state_shape"]
+    sinfo = dict(info, n_agents=args.n_agents)
+    scheme, groups, preprocess = scheme_for(sinfo, torch)
+    proto = EpisodeBatch(scheme, groups, 1, 2, preprocess=preprocess, device=device)
+    torch.manual_seed(seed)
+    home = BasicMAC(proto.scheme, groups, args)
+    away = BasicMAC(proto.scheme, groups, args)
+    stepper.initialize(scheme, groups, preprocess, home, away)
+    return stepper, home, away, args
+
+
+def check_sides(stepper, macs, args, batches, infos, episode, test_mode, eps, envs=None, dtype=None):
+    """Teacher-forced env replay of both sides + oracle agent check. ``envs``: the env indices to check (all by
+    default; a spread subset at the 4096-env config-3 shape). ``dtype``: the oracle unroll's precision (oracle_q).
+    Returns the counts (greedy picks checked, near ties, epsilon draws)."""
+    import envref
+    import stepper_ref
+    import torch
+    spec = stepper.spec
+    B, N, A, T1 = stepper.batch_size, spec.n_agents // 2, spec.n_actions, stepper.episode_limit + 1
+    sub = np.arange(B) if envs is None else np.asarray(envs, dtype=np.int64)
+    nbs = [np_batch(b) for b in batches]
+    ep_len = stepper.last_run["ep_len"].numpy()
+    assert (ep_len >= 1).all() and (ep_len <= stepper.episode_limit).all()
+    # --- env side + bookkeeping, teacher forced through the oracle self-play stepper ---
+    all_refs = ref_envs_for(spec, B, seed=args.seed)
+    refs = [all_refs[int(b)] for b in sub]
+    for r in refs:
+        r.episode = episode
+    pol = [lambda t, run, b, s=s: nbs[s]["actions"][sub[run], t, :, 0] for s in range(2)]
+    out = stepper_ref.run_self_play(stepper_ref.RefVecEnv(refs), pol[0], pol[1], len(sub), T1, N, A, 8 * spec.U,
+                                    6 * spec.U, test_mode=test_mode)
+    for s, key in enumerate(("home", "away")):
+        for k, v in out[key].items():
+            np.testing.assert_array_equal(nbs[s][k][sub], v, err_msg=f"{key}[{k}]")
+    np.testing.assert_array_equal(stepper.last_run["returns"].numpy()[sub], np.float32(out["returns"][0]))
+    np.testing.assert_array_equal(stepper.last_run["away_returns"].numpy()[sub], np.float32(out["returns"][1]))
+    if envs is None:
+        assert stepper.t == out["t"]
+        assert [infos[i] for i in range(B)] == out["env_infos"]
+        if not test_mode:
+            assert int(ep_len.sum()) == out["env_steps"]
+    else:
+        assert stepper.t == ep_len.max() and len(infos) == B
+    # --- agent side per side: oracle Q on the recorded batch; greedy / epsilon picks bit-exact ---
+    n_random = n_greedy = n_tie = 0
+    for s, (mac, nb) in enumerate(zip(macs, nbs)):
+        tb = {k: torch.from_numpy(v[sub]) for k, v in nb.items()}
+        q = dict(zip(sub.tolist(), oracle_q(mac, tb, N, int(ep_len[sub].max()) + 1, dtype)))
+        for b in sub.tolist():
+            for t in range(int(ep_len[b]) + 1):
+                for n in range(N):
+                    a = int(nb["actions"][b, t, n, 0])
+                    av = nb["avail_actions"][b, t, n]
+                    if not test_mode and eps[s] > 0:
+                        key = envref.env_key(args.seed, b)
+                        r1 = envref.rng(key, envref.ctr(episode, t, 2, s * N + n))
+                        if envref.u01(r1) < np.float32(eps[s]):
+                            r2 = envref.rng(key, envref.ctr(episode, t, 3, s * N + n))
+                            assert a == envref.random_available(av.tolist(), r2)
+                            n_random += 1
+                            continue
+                    m = np.where(av == 0, -np.inf, q[b][t, n])
+                    srt = np.sort(m)
+                    n_greedy += 1
+                    if srt[-1] - srt[-2] > Q_TOL:
+                        assert a == int(np.argmax(m)), (s, b, t, n)
+                    else:
+                        assert m[a] >= srt[-1] - Q_TOL
+                        n_tie += 1
+    if not test_mode and max(eps) > 0.2:
+        assert n_random > 0
+    return {"greedy": n_greedy, "near_ties": n_tie, "epsilon_draws": n_random}
+
+
 def assert_near_tie_divergence(ref_sides, got_sides, q_sides, B, tol=1e-5):
     """two kernels that agree in fp32 up to summation order must produce the same episodes except where a
     near-tie flips an argmax. For every episode that differs (over every side of a self-play pair), the first differing

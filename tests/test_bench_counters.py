@@ -31,23 +31,19 @@ V7_SOURCES = ("ma-league_amd/csrc/rollout.hip", "ma-league_amd/csrc/mlg_device.h
 
 def test_v7_latency_floor_stamp_is_current():
     """the one-env step cycles behind roofline.latency_floor_ms must come from the v7 sources in the
-    tree: the recorded stamp commit may not be older than the last commit that changed them (skipped where the tree
-    has no git history, e.g. the GPU box's snapshot)."""
-    import subprocess
+    tree. The stamp records the sha256 of every v7 source file it was measured on (one_env_step_sources) next to the
+    commit it was measured on top of, and the files in the tree must hash to the same: any edit of them, committed or
+    not, with or without git history, fails until the step is re-measured. (The earlier form compared commit
+    ancestry, which a change that edits a v7 source and re-measures in the same commit cannot satisfy: the stamp
+    would have to name the hash of the commit that contains it.)"""
+    import hashlib
     c = _counters("rollout_v2_kernel<64, true, 5, 10>")
-    stamp = c.get("one_env_step_commit")
-    assert stamp, "the v7 one-env step cycles name the commit of the sources they were measured on"
-
-    def git(*a):
-        return subprocess.run(["git", "-C", ROOT, *a], capture_output=True, text=True)
-
-    if git("rev-parse", "--git-dir").returncode != 0:
-        import pytest
-        pytest.skip("no git history in this tree")
-    last = git("log", "-1", "--format=%H", "--", *V7_SOURCES).stdout.strip()
-    assert last, "v7 sources not in the history"
-    r = git("merge-base", "--is-ancestor", last, stamp)
-    assert r.returncode == 0, (f"v7 sources changed at {last[:7]} after the one-env step stamp ({stamp}): re-measure "
-                               "with scripts/gpu_stamps_trace.sh STAMPS=1 and update profiles/counters.json")
-    dirty = git("status", "--porcelain", "--", *V7_SOURCES).stdout.strip()
-    assert not dirty, f"uncommitted v7 source changes: re-measure the one-env step after committing ({dirty})"
+    assert c.get("one_env_step_commit"), "the v7 one-env step cycles name the commit they were measured on top of"
+    stamped = c.get("one_env_step_sources")
+    assert stamped and set(stamped) == set(V7_SOURCES), "the v7 one-env step cycles list the sources they belong to"
+    for path in V7_SOURCES:
+        with open(os.path.join(ROOT, path), "rb") as f:
+            now = hashlib.sha256(f.read()).hexdigest()
+        assert now == stamped[path], (f"{path} changed after the one-env step stamp: re-measure with the stamps build "
+                                      "(make -C ma-league_amd stamps; MLG_ROLLOUT_KERNEL=v7 MLG_LIB=<stamps library> "
+                                      "python scripts/stamps_rollout.py) and update profiles/counters.json")

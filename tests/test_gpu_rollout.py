@@ -10,11 +10,12 @@ import torch
 
 import envref
 import learner_ref as LR
-from helpers import assert_near_tie_divergence, np_batch, qmix_args, ref_envs_for, scheme_for
+from helpers import Q_TOL, assert_near_tie_divergence, np_batch, qmix_args, ref_envs_for, scheme_for
+from helpers import build_stepper as _build_stepper, check_run as _check_run  # shared with test_gpu_rollout_shapes
+from helpers import shape_plan
 
 pytestmark = pytest.mark.gpu
 
-Q_TOL = 1e-4
 # the measured number of v7 episodes (of 100) that diverge from v2 at a near-tie argmax flip,
 # per plan (static and runtime shapes), pinned with a small margin (was a blanket B // 10)
 V7_MAX_DIVERGING = {"medium_1h_4t": 2, "medium": 2, "small": 2}  # measured 0 / 0 / 0 (both shapes, r05)
@@ -28,11 +29,13 @@ def _mk_env(device, plan, B, episode_limit=60, seed=3, stochastic=True):
 
 
 @pytest.mark.parametrize("plan,stochastic", [("small", True), ("medium_1h_4t", True), ("medium_1h_2t_2a_melee", True),
-                                             ("medium_1h_4a", False), ("large", True)])
+                                             ("medium_1h_4a", False), ("large", True),
+                                             # asymmetric: 5 agents vs 7 scripted, and the policy team listed first
+                                             ("5v7", True), ("3v5", True)])
 def test_env_kernels_bit_exact(device, plan, stochastic):
     from maleague import _native
     B, T = 24, 50
-    spec, st = _mk_env(device, plan, B, episode_limit=T, seed=7, stochastic=stochastic)
+    spec, st = _mk_env(device, shape_plan(plan), B, episode_limit=T, seed=7, stochastic=stochastic)
     cspec = spec.to_c()
     refs = ref_envs_for(spec, B, seed=7)
     U, N, A = spec.U, spec.n_agents, spec.n_actions
@@ -141,101 +144,6 @@ def test_select_actions_epsilon_stream(device):
     np.testing.assert_array_equal(acts.cpu().numpy(), exp)
     np.testing.assert_array_equal(greedy.cpu().numpy(), exp_g)
     assert 0 < (exp_g == 0).sum() < B * N
-
-
-def _build_stepper(device, plan="medium_1h_4t", B=48, episode_limit=40, seed=5, **kw):
-    from maleague.components.episode_batch import EpisodeBatch
-    from maleague.controllers import BasicMAC
-    from maleague.custom_logging import MainLogger
-    from maleague.steppers import ParallelStepper
-    args = qmix_args(batch_size_run=B, seed=seed, env_args={"match_build_plan": plan, "grid_size": 20,
-                                                            "stochastic_spawns": True, "episode_limit": episode_limit},
-                     **kw)
-    stepper = ParallelStepper(args, MainLogger())
-    info = stepper.get_env_info()
-    args.n_agents, args.n_actions, args.state_shape = info["n_agents"], info["n_actions"], info["state_shape"]
-    scheme, groups, preprocess = scheme_for(info, torch)
-    proto = EpisodeBatch(scheme, groups, 1, 2, preprocess=preprocess, device=device)
-    torch.manual_seed(seed)
-    mac = BasicMAC(proto.scheme, groups, args)
-    stepper.initialize(scheme, groups, preprocess, mac)
-    return stepper, mac, args
-
-
-def _check_run(stepper, mac, args, batch, infos, episode, test_mode, eps, envs=None):
-    """Teacher-forced env replay + oracle agent check of a run; ``envs``: the env indices to check (all by
-    default; a subset for the 4096-env headline shape)."""
-    spec = stepper.spec
-    B, N, A, T1 = stepper.batch_size, spec.n_agents, spec.n_actions, stepper.episode_limit + 1
-    sub = list(range(B)) if envs is None else [int(e) for e in envs]
-    nb = np_batch(batch)
-    ep_len = stepper.last_run["ep_len"].numpy()
-    rets = stepper.last_run["returns"].numpy()
-    assert (ep_len >= 1).all() and (ep_len <= stepper.episode_limit).all()
-    assert stepper.t == ep_len.max()
-    # --- env side, teacher forced: replay the recorded actions through the C oracle ---
-    refs = ref_envs_for(spec, B, seed=args.seed)
-    for b in sub:
-        r = refs[b]
-        r.episode = episode
-        r.reset()
-        L = int(ep_len[b])
-        np.testing.assert_array_equal(nb["obs"][b, 0], r.obs())
-        np.testing.assert_array_equal(nb["state"][b, 0], r.state())
-        np.testing.assert_array_equal(nb["avail_actions"][b, 0], r.avail())
-        ret = 0.0
-        for t in range(L):
-            rew, done, info = r.step(nb["actions"][b, t, :, 0])
-            ret += rew[0]
-            assert nb["reward"][b, t, 0] == np.float32(rew[0])
-            assert nb["terminated"][b, t, 0] == int(done) and done == (t == L - 1)
-            np.testing.assert_array_equal(nb["obs"][b, t + 1], r.obs())
-            np.testing.assert_array_equal(nb["state"][b, t + 1], r.state())
-            np.testing.assert_array_equal(nb["avail_actions"][b, t + 1], r.avail())
-        assert rets[b] == np.float32(ret)
-        np.testing.assert_array_equal(nb["filled"][b, :, 0], (np.arange(T1) <= L).astype(np.int64))
-        # actions recorded for t = 0..L (the final one after termination), zero beyond
-        assert (nb["actions"][b, L + 1:] == 0).all() and (nb["actions_onehot"][b, L + 1:] == 0).all()
-        oh = np.zeros((L + 1, N, A), np.float32)
-        oh[np.arange(L + 1)[:, None], np.arange(N)[None, :], nb["actions"][b, :L + 1, :, 0]] = 1
-        np.testing.assert_array_equal(nb["actions_onehot"][b, :L + 1], oh)
-        assert (nb["reward"][b, L:] == 0).all() and (nb["terminated"][b, L:] == 0).all()
-    # env_infos in order of termination
-    order = sorted(range(B), key=lambda i: (int(ep_len[i]), i))
-    assert len(infos) == B
-    # --- agent side: oracle Q on the recorded batch; greedy / epsilon picks bit-exact ---
-    params = {k: v.detach().cpu() for k, v in mac.agent.state_dict().items()}
-    tb = {k: torch.from_numpy(v[sub]) for k, v in nb.items()}
-    Tm = int(ep_len[sub].max()) + 1
-    with torch.no_grad():
-        q, _ = LR.mac_unroll(params, tb, N, T=Tm)
-    q = dict(zip(sub, q.numpy()))
-    n_checked = n_random = 0
-    for b in sub:
-        for t in range(int(ep_len[b]) + 1):
-            for n in range(N):
-                a = int(nb["actions"][b, t, n, 0])
-                av = nb["avail_actions"][b, t, n]
-                if not test_mode and eps > 0:
-                    key = envref.env_key(args.seed, b)
-                    r1 = envref.rng(key, envref.ctr(episode, t, 2, n))
-                    if envref.u01(r1) < np.float32(eps):
-                        r2 = envref.rng(key, envref.ctr(episode, t, 3, n))
-                        assert a == envref.random_available(av.tolist(), r2)
-                        n_random += 1
-                        continue
-                m = np.where(av == 0, -np.inf, q[b][t, n])
-                g = int(np.argmax(m))
-                srt = np.sort(m)
-                if srt[-1] - srt[-2] > Q_TOL:
-                    assert a == g, (b, t, n, a, g)
-                else:  # near-tie within fp32 tolerance: chosen must be (numerically) a max
-                    assert m[a] >= srt[-1] - Q_TOL
-                n_checked += 1
-    assert n_checked > 0
-    if not test_mode and eps > 0.2:
-        assert n_random > 0
-    return order
 
 
 @pytest.mark.parametrize("plan", ["medium_1h_4t", "small", "medium_1h_2t_2a"])

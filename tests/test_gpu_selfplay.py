@@ -14,106 +14,14 @@ import torch
 import envref
 import learner_ref as LR
 import stepper_ref
-from helpers import assert_near_tie_divergence, np_batch, qmix_args, ref_envs_for, scheme_for
+from helpers import Q_TOL, assert_near_tie_divergence, np_batch, qmix_args, ref_envs_for, scheme_for
+from helpers import build_selfplay as _build, check_sides as _check_sides, sp_args as _sp_args  # shared helpers
 
 pytestmark = pytest.mark.gpu
 
-Q_TOL = 1e-4
 # the measured number of sp7 episodes (of 100) that diverge from sp2 at a near-tie argmax flip,
 # per plan, pinned with a small margin (was a blanket B // 10)
 SP7_MAX_DIVERGING = {"medium_1h_4t": 2, "small": 2, "medium": 2}  # measured 0 / 0 / 0 (r05)
-
-
-def _sp_args(B, episode_limit, seed, plan="medium_1h_4t", **kw):
-    from maleague.envs.plans import builtin_plan
-    mbp = builtin_plan(plan, self_play=True) if isinstance(plan, str) else plan
-    return qmix_args(batch_size_run=B, seed=seed,
-                     env_args={"match_build_plan": mbp, "grid_size": 20,
-                               "stochastic_spawns": True, "episode_limit": episode_limit}, **kw)
-
-
-def _build(device, plan="medium_1h_4t", B=48, episode_limit=40, seed=5):
-    from maleague.components.episode_batch import EpisodeBatch
-    from maleague.controllers import BasicMAC
-    from maleague.custom_logging import MainLogger
-    from maleague.steppers import SelfPlayParallelStepper
-    args = _sp_args(B, episode_limit, seed, plan)
-    stepper = SelfPlayParallelStepper(args, MainLogger())
-    info = stepper.get_env_info()
-    assert info["n_agents"] % 2 == 0
-    args.n_agents, args.n_actions, args.state_shape = info["n_agents"] // 2, info["n_actions"], info["state_shape"]
-    sinfo = dict(info, n_agents=args.n_agents)
-    scheme, groups, preprocess = scheme_for(sinfo, torch)
-    proto = EpisodeBatch(scheme, groups, 1, 2, preprocess=preprocess, device=device)
-    torch.manual_seed(seed)
-    home = BasicMAC(proto.scheme, groups, args)
-    away = BasicMAC(proto.scheme, groups, args)
-    stepper.initialize(scheme, groups, preprocess, home, away)
-    return stepper, home, away, args
-
-
-def _check_sides(stepper, macs, args, batches, infos, episode, test_mode, eps, envs=None):
-    """Teacher-forced env replay of both sides + oracle agent check. ``envs``: the env indices to check (all by
-    default; a spread subset at the 4096-env config-3 shape). Returns the counts (greedy picks checked, near ties,
-    epsilon draws)."""
-    spec = stepper.spec
-    B, N, A, T1 = stepper.batch_size, spec.n_agents // 2, spec.n_actions, stepper.episode_limit + 1
-    sub = np.arange(B) if envs is None else np.asarray(envs, dtype=np.int64)
-    nbs = [np_batch(b) for b in batches]
-    ep_len = stepper.last_run["ep_len"].numpy()
-    assert (ep_len >= 1).all() and (ep_len <= stepper.episode_limit).all()
-    # --- env side + bookkeeping, teacher forced through the oracle self-play stepper ---
-    all_refs = ref_envs_for(spec, B, seed=args.seed)
-    refs = [all_refs[int(b)] for b in sub]
-    for r in refs:
-        r.episode = episode
-    pol = [lambda t, run, b, s=s: nbs[s]["actions"][sub[run], t, :, 0] for s in range(2)]
-    out = stepper_ref.run_self_play(stepper_ref.RefVecEnv(refs), pol[0], pol[1], len(sub), T1, N, A, 8 * spec.U,
-                                    6 * spec.U, test_mode=test_mode)
-    for s, key in enumerate(("home", "away")):
-        for k, v in out[key].items():
-            np.testing.assert_array_equal(nbs[s][k][sub], v, err_msg=f"{key}[{k}]")
-    np.testing.assert_array_equal(stepper.last_run["returns"].numpy()[sub], np.float32(out["returns"][0]))
-    np.testing.assert_array_equal(stepper.last_run["away_returns"].numpy()[sub], np.float32(out["returns"][1]))
-    if envs is None:
-        assert stepper.t == out["t"]
-        assert [infos[i] for i in range(B)] == out["env_infos"]
-        if not test_mode:
-            assert int(ep_len.sum()) == out["env_steps"]
-    else:
-        assert stepper.t == ep_len.max() and len(infos) == B
-    # --- agent side per side: oracle Q on the recorded batch; greedy / epsilon picks bit-exact ---
-    n_random = n_greedy = n_tie = 0
-    for s, (mac, nb) in enumerate(zip(macs, nbs)):
-        params = {k: v.detach().cpu() for k, v in mac.agent.state_dict().items()}
-        tb = {k: torch.from_numpy(v[sub]) for k, v in nb.items()}
-        with torch.no_grad():
-            q, _ = LR.mac_unroll(params, tb, N, T=int(ep_len[sub].max()) + 1)
-        q = dict(zip(sub.tolist(), q.numpy()))
-        for b in sub.tolist():
-            for t in range(int(ep_len[b]) + 1):
-                for n in range(N):
-                    a = int(nb["actions"][b, t, n, 0])
-                    av = nb["avail_actions"][b, t, n]
-                    if not test_mode and eps[s] > 0:
-                        key = envref.env_key(args.seed, b)
-                        r1 = envref.rng(key, envref.ctr(episode, t, 2, s * N + n))
-                        if envref.u01(r1) < np.float32(eps[s]):
-                            r2 = envref.rng(key, envref.ctr(episode, t, 3, s * N + n))
-                            assert a == envref.random_available(av.tolist(), r2)
-                            n_random += 1
-                            continue
-                    m = np.where(av == 0, -np.inf, q[b][t, n])
-                    srt = np.sort(m)
-                    n_greedy += 1
-                    if srt[-1] - srt[-2] > Q_TOL:
-                        assert a == int(np.argmax(m)), (s, b, t, n)
-                    else:
-                        assert m[a] >= srt[-1] - Q_TOL
-                        n_tie += 1
-    if not test_mode and max(eps) > 0.2:
-        assert n_random > 0
-    return {"greedy": n_greedy, "near_ties": n_tie, "epsilon_draws": n_random}
 
 
 @pytest.mark.parametrize("plan", ["medium_1h_4t", "small", "medium_1h_2t_2a_melee"])
