@@ -320,6 +320,15 @@ int mlg_refil_agent_forward(const MlgRefilDims *d, const float *packed, const fl
 int mlg_refil_rollout(const MlgEntityEnvSpec *spec, MlgEnvState *st, const MlgRefilDims *d, const float *packed,
                       MlgEntityBatch *batch, MlgRunInfo *info, float epsilon, int32_t test_mode, void *stream);
 
+/* Host only, launches nothing (the contract of mlg_rollout_describe). Writes the name of the kernel mlg_refil_rollout
+ * would launch for this spec and agent dims under the current MLG_REFIL_ROLLOUT / MLG_REFIL_GENERIC environment, and
+ * the dynamic LDS bytes of that launch. Names: "ro4-static" / "ro4" (four envs per wave: the compile-time refil_8
+ * shape / runtime shape), "ro2/kc1", "ro2/kc2", "ro2/kc3" (two envs per wave, entity input width 16 / 32 / 48).
+ * mlg_refil_rollout takes its decision from the same function. Nonzero (mlg_last_error) where it would refuse the
+ * shape. */
+int mlg_refil_rollout_describe(const MlgEntityEnvSpec *spec, const MlgRefilDims *d, char *name, int32_t name_cap,
+                               int64_t *lds_bytes);
+
 /* EntityAttentionLayer.forward (src/marl/modules/layers/attention.py:24-79; in = embed = out = 64, 4 heads) over bs
  * items: x [bs][ne][64], pre_mask [bs][nq][ne], post_mask [bs][nq] (uint8, 1 = masked) -> y [bs][nq][64]. With
  * gy != nullptr also the backward of sum(y * gy): dx [bs][ne][64] written, dw_in [192][64], dw_out [64][64],

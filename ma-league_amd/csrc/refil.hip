@@ -924,14 +924,25 @@ extern "C" int mlg_refil_agent_forward(const MlgRefilDims* d, const float* packe
     return mlg::check_launch("refil_agent_forward");
 }
 
-extern "C" int mlg_refil_rollout(const MlgEntityEnvSpec* spec, MlgEnvState* st, const MlgRefilDims* d,
-                                 const float* packed, MlgEntityBatch* batch, MlgRunInfo* info, float epsilon,
-                                 int32_t test_mode, void* stream) {
+namespace {
+
+// The launch mlg_refil_rollout makes for a spec and agent dims: decided here for the entry point and for
+// mlg_refil_rollout_describe, so the query cannot drift from the launch.
+struct RefilRolloutPlan {
+    const char* name;  // "ro4-static" / "ro4" (four envs per wave: refil_8 static shape / runtime shape), "ro2/kcK"
+    bool four;         // refil_rollout4_kernel<2, SU> (else refil_rollout_kernel<kc>)
+    bool st16;         // the static 16-unit instantiation
+    int kc;            // entity input width in 16-wide chunks (two-env kernel)
+    size_t lds_bytes;
+};
+
+int plan_refil_rollout(const MlgEntityEnvSpec* spec, const MlgRefilDims* d, RefilRolloutPlan* plan) {
     if (check_dims(d)) return 1;
-    MLG_REQUIRE(spec && st && packed && batch && info, "refil_rollout: null argument");
+    MLG_REQUIRE(spec != nullptr, "refil_rollout: null argument");
     const MlgEnvSpec& sp = spec->base;
     const int S = sp.U / 2;
-    MLG_REQUIRE(sp.U % 2 == 0 && sp.U <= NE && S <= NAS, "refil_rollout: U=%d unsupported (even, <= 16)", sp.U);
+    MLG_REQUIRE(sp.U >= 2 && sp.U % 2 == 0 && sp.U <= NE && S <= NAS, "refil_rollout: U=%d unsupported (even, <= 16)",
+                sp.U);
     MLG_REQUIRE(sp.n_agents == S && d->n_agents == S && d->n_entities == sp.U && d->entity_shape == 8 &&
                     d->n_actions == MLG_ACT_BASE + sp.U && d->entity_last_action,
                 "refil_rollout: dims (n_agents=%d n_entities=%d entity_shape=%d n_actions=%d) do not match the env "
@@ -940,6 +951,47 @@ extern "C" int mlg_refil_rollout(const MlgEntityEnvSpec* spec, MlgEnvState* st, 
                 "refil_rollout: min_agents=%d max_agents=%d (slots %d)", spec->min_agents, spec->max_agents, S);
     MLG_REQUIRE(sp.policy_team == 0 && sp.scripted[0] == 0 && sp.scripted[1] == 1,
                 "refil_rollout: the entity env has policy team 0 and scripted team 1");
+    const RAgent L = agent_layout(d);
+    // default: four envs per wave (refil_ro4.inc) for the entity width of the env variant (K1 = 32);
+    // MLG_REFIL_ROLLOUT=v1 selects the two-env kernel (A/B, parity tests run both)
+    const char* var = getenv("MLG_REFIL_ROLLOUT");
+    const bool v1 = (var && strcmp(var, "v1") == 0) || L.K1 != 32;
+    if (!v1) {
+        // the refil_8 shape (16 units: the checks above fix the rest of the dims) as the static instantiation
+        // (MLG_REFIL_GENERIC=1: the generic one, A/B)
+        const bool generic = getenv("MLG_REFIL_GENERIC") != nullptr;
+        const bool st16 = sp.U == 16 && !generic;
+        *plan = RefilRolloutPlan{st16 ? "ro4-static" : "ro4", true, st16, 2, sizeof(R4Shared)};
+        return 0;
+    }
+    const int kc = L.K1 <= 16 ? 1 : (L.K1 <= 32 ? 2 : 3);
+    static const char* const names[3] = {"ro2/kc1", "ro2/kc2", "ro2/kc3"};
+    *plan = RefilRolloutPlan{names[kc - 1], false, false, kc, sizeof(RoShared)};
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int mlg_refil_rollout_describe(const MlgEntityEnvSpec* spec, const MlgRefilDims* d, char* name,
+                                          int32_t name_cap, int64_t* lds_bytes) {
+    MLG_REQUIRE(name && name_cap > 0 && lds_bytes, "refil_rollout_describe: null output");
+    RefilRolloutPlan plan;
+    if (int rc = plan_refil_rollout(spec, d, &plan)) return rc;
+    MLG_REQUIRE((size_t)name_cap > strlen(plan.name), "refil_rollout_describe: name buffer of %d bytes too small",
+                name_cap);
+    strcpy(name, plan.name);
+    *lds_bytes = (int64_t)plan.lds_bytes;
+    return 0;
+}
+
+extern "C" int mlg_refil_rollout(const MlgEntityEnvSpec* spec, MlgEnvState* st, const MlgRefilDims* d,
+                                 const float* packed, MlgEntityBatch* batch, MlgRunInfo* info, float epsilon,
+                                 int32_t test_mode, void* stream) {
+    MLG_REQUIRE(spec && st && packed && batch && info, "refil_rollout: null argument");
+    RefilRolloutPlan plan;
+    if (int rc = plan_refil_rollout(spec, d, &plan)) return rc;
+    const MlgEnvSpec& sp = spec->base;
+    const int S = sp.U / 2;
     const MlgEntityBatch& bt = *batch;
     MLG_REQUIRE(bt.entities && bt.obs_mask && bt.entity_mask && bt.actions && bt.avail && bt.reward && bt.terminated &&
                     bt.actions_onehot && bt.filled, "refil_rollout: batch has null tensors");
@@ -951,16 +1003,9 @@ extern "C" int mlg_refil_rollout(const MlgEntityEnvSpec* spec, MlgEnvState* st, 
     while (p < sp.grid) p <<= 1;
     RoArgs a{sp.U, S, d->n_actions, d->entity_shape, S, spec->min_agents, spec->max_agents, bt.B, 1.0f / (float)p};
     const RAgent L = agent_layout(d);
-    // default: four envs per wave (refil_ro4.inc) for the entity width of the env variant (K1 = 32);
-    // MLG_REFIL_ROLLOUT=v1 selects the two-env kernel (A/B, parity tests run both)
-    const char* var = getenv("MLG_REFIL_ROLLOUT");
-    const bool v1 = (var && strcmp(var, "v1") == 0) || L.K1 != 32;
-    if (!v1) {
-        const size_t lds4 = sizeof(R4Shared);
-        // the refil_8 shape (16 units: the checks above fix the rest of the dims) as the static instantiation
-        // (MLG_REFIL_GENERIC=1: the generic one, A/B)
-        const bool generic = getenv("MLG_REFIL_GENERIC") != nullptr;
-        const bool st16 = sp.U == 16 && !generic;
+    if (plan.four) {
+        const size_t lds4 = plan.lds_bytes;
+        const bool st16 = plan.st16;
         auto kern4 = st16 ? refil_rollout4_kernel<2, 16> : refil_rollout4_kernel<2, 0>;
         static bool attr4[2] = {false, false};
         if (!attr4[st16]) {
@@ -975,10 +1020,11 @@ extern "C" int mlg_refil_rollout(const MlgEntityEnvSpec* spec, MlgEnvState* st, 
                            test_mode);
         return mlg::check_launch("refil_rollout4");
     }
-    auto kern = L.K1 <= 16 ? refil_rollout_kernel<1> : (L.K1 <= 32 ? refil_rollout_kernel<2> : refil_rollout_kernel<3>);
-    const size_t lds = sizeof(RoShared);
+    auto kern = plan.kc == 1 ? refil_rollout_kernel<1>
+                             : (plan.kc == 2 ? refil_rollout_kernel<2> : refil_rollout_kernel<3>);
+    const size_t lds = plan.lds_bytes;
     static bool attr_set[3] = {false, false, false};
-    const int ki = L.K1 <= 16 ? 0 : (L.K1 <= 32 ? 1 : 2);
+    const int ki = plan.kc - 1;
     if (!attr_set[ki]) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)lds);

@@ -162,6 +162,7 @@ SIGNATURES = {
     "mlg_refil_pack_agent": (ctypes.c_int, [_P, _P, _P, _P]),
     "mlg_refil_agent_forward": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "mlg_refil_rollout": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
+    "mlg_refil_rollout_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
     "mlg_refil_attention": (ctypes.c_int, [_P] * 6 + [_I] * 4 + [_P] * 7),
     "mlg_refil_packed_mixer_size": (ctypes.c_int64, [_P]),
     "mlg_refil_pack_mixer": (ctypes.c_int, [_P, _P, _P, _P]),
@@ -239,6 +240,18 @@ def rollout_describe(spec: MlgEnvSpec, dims: MlgAgentDims, selfplay: bool = Fals
                                   ctypes.byref(lds))
     if rc != 0:
         raise NativeError(f"mlg_rollout_describe failed: {lib.mlg_last_error().decode()}")
+    return name.value.decode(), int(lds.value)
+
+
+def refil_rollout_describe(spec: MlgEntityEnvSpec, dims: MlgRefilDims) -> tuple[str, int]:
+    """(kernel name, dynamic LDS bytes) of the launch mlg_refil_rollout would make for this entity spec and agent dims
+    under the current MLG_REFIL_ROLLOUT / MLG_REFIL_GENERIC environment (mlg_refil_rollout_describe: host only)."""
+    lib = load()
+    name = ctypes.create_string_buffer(32)
+    lds = ctypes.c_int64(0)
+    rc = lib.mlg_refil_rollout_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name), ctypes.byref(lds))
+    if rc != 0:
+        raise NativeError(f"mlg_refil_rollout_describe failed: {lib.mlg_last_error().decode()}")
     return name.value.decode(), int(lds.value)
 
 

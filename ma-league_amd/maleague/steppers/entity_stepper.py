@@ -10,6 +10,7 @@ from __future__ import annotations
 from .. import _native
 from ..components.batch_view import mlg_entity_batch
 from ..envs.entity_env import EntityEnvSpec
+from ..exceptions import MultiAgentControllerNotInitialized
 from .parallel_stepper import EpisodeStepper, ParallelStepper
 
 
@@ -24,7 +25,11 @@ class EntityParallelStepper(ParallelStepper):
         return mlg_entity_batch(batch)
 
     def describe_rollout(self):
-        raise NotImplementedError("mlg_refil_rollout has its own dispatch: mlg_rollout_describe does not cover it")
+        """(kernel name, dynamic LDS bytes) of the launch run() would make under the current MLG_REFIL_* environment
+        (mlg_refil_rollout_describe: host only)."""
+        if self.home_mac is None:
+            raise MultiAgentControllerNotInitialized()
+        return _native.refil_rollout_describe(self._cspec, self.home_mac.agent.dims())
 
     def _rollout(self, mb, run_info, epsilon, test_mode):
         agent = self.home_mac.agent

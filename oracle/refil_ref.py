@@ -144,7 +144,7 @@ def mac_forward(p, batch, args, groupA=None):
     """The whole-episode EntityMAC forward; with groupA, the imagined within / interact copies as well."""
     ent, om, em = build_entity_inputs(batch, args.n_agents, args.n_actions)
     bs = ent.shape[0]
-    h0 = torch.zeros(bs, args.n_agents, args.rnn_hidden_dim)
+    h0 = torch.zeros(bs, args.n_agents, args.rnn_hidden_dim, dtype=p["fc1.weight"].dtype)  # float64 unroll: cast p
     if groupA is None:
         return entity_agent(p, ent, om, em, h0, args)[0], None
     within, interact, Wn, In = imagine_masks(groupA, em, om)

@@ -370,3 +370,149 @@ def assert_near_tie_divergence(ref_sides, got_sides, q_sides, B, tol=1e-5):
                 flips += 1
         assert flips > 0, f"episode {b} diverges at t={t_first} without an action flip"
     return n_diff
+
+
+# ---- REFIL (entity env) rollout: one launch of mlg_refil_rollout and its teacher-forced check ---------------------
+
+def refil_agent(device, params=None, seed=0, **kw):
+    """An ImagineEntityAttentionRNNAgent on ``device`` (refil_args(**kw)): torch-seeded, or with ``params`` loaded
+    (state_dict keys -> arrays)."""
+    import torch
+    from maleague.modules.agents import REGISTRY
+    a = refil_args(**kw)
+    torch.manual_seed(seed)
+    ag = REGISTRY["imagine_entity_attend_rnn"](a.entity_shape + a.n_actions, a).to(device)
+    if params is not None:
+        sd = ag.state_dict()
+        assert set(params) <= set(sd), set(params) - set(sd)
+        sd.update({k: torch.from_numpy(np.array(v)) for k, v in params.items()})
+        ag.load_state_dict(sd)
+    return ag, a
+
+
+def refil_rollout(device, B=12, T=40, seed=5, eps=0.0, test_mode=True, ring=None, agent_seed=1, st=None, kmin=3, kmax=8,
+                  batch=None, extent=None, plan="refil_8", agent_params=None, grid=20):
+    """One mlg_refil_rollout launch over ``plan`` (a built-in name or a list of two team dicts) from the env state
+    ``st`` (fresh by default; a run advances its episode counters). The agent: torch-seeded with ``agent_seed``, or
+    ``agent_params`` -- a callable (d0, n_actions) -> state_dict arrays, or such a dict. ring: full-write mode over a
+    garbage-filled batch; extent: the slot extents tensor of full-write mode."""
+    import torch
+    from maleague import _native
+    from maleague.components.batch_view import mlg_entity_batch
+    from maleague.components.episode_batch import EpisodeBatch
+    from maleague.envs.entity_env import EntityEnvSpec
+    from maleague.envs.teams_env import VecEnvState
+    spec = EntityEnvSpec.from_env_args({"match_build_plan": plan, "episode_limit": T, "seed": seed, "grid_size": grid,
+                                        "min_agents": kmin, "max_agents": kmax})
+    info = spec.env_info()
+    if callable(agent_params):
+        agent_params = agent_params(info["entity_shape"] + info["n_actions"], info["n_actions"])
+    ag, a = refil_agent(device, agent_params, seed=agent_seed, n_agents=info["n_agents"],
+                        n_entities=info["n_entities"], n_actions=info["n_actions"])
+    scheme, groups, pre = entity_scheme_for(info, torch)
+    if st is None:
+        st = VecEnvState(spec, B, device)
+    if batch is None:
+        batch = EpisodeBatch(scheme, groups, B, T + 1, preprocess=pre, device=device)
+        if ring is not None:
+            for v in batch.data.transition_data.values():
+                v.fill_(7)
+    mb, keep = mlg_entity_batch(batch)
+    if ring is not None:
+        mb.full_write = 1
+    if extent is not None:
+        mb.slot_extent = extent.data_ptr()
+    run = torch.zeros(6 * B, dtype=torch.int32, device=device)
+    ri = _native.MlgRunInfo(run[0:B].data_ptr(), run[4 * B:5 * B].data_ptr(), run[B:3 * B].data_ptr(),
+                            run[3 * B:4 * B].data_ptr(), None, None)
+    _native.call("mlg_refil_rollout", _native.byref(spec.to_c()), _native.byref(st.to_c()), _native.byref(ag.dims()),
+                 _native.ptr(ag.packed()), _native.byref(mb), _native.byref(ri), float(eps), int(test_mode),
+                 _native.stream_ptr())
+    torch.cuda.synchronize()
+    r = run.cpu().numpy()
+    summary = {"len": r[0:B], "won": r[B:3 * B].reshape(B, 2), "draw": r[3 * B:4 * B],
+               "ret": r[4 * B:5 * B].view(np.float32)}
+    if extent is not None:
+        refil_rollout.last_batch = batch
+    return spec, ag, a, np_batch(batch), summary, st
+
+
+def refil_oracle_q(ag, a, nb, envs=None, dtype=None):
+    """The oracle EntityMAC's Q [len(envs), T1, NA, A] along a recorded batch (refil_ref.mac_forward) with the agent's
+    parameters: fp32 by default, or parameters and inputs cast to ``dtype`` (torch.float64: strictly more precise than
+    the kernels)."""
+    import torch
+    import refil_ref as RR
+    p = {k: v.detach().cpu() for k, v in ag.state_dict().items()}
+    sel = slice(None) if envs is None else envs
+    keys = ("entities", "obs_mask", "entity_mask", "actions_onehot")  # what EntityMAC._build_inputs reads
+    tb = {k: torch.from_numpy(np.array(nb[k][sel])) for k in keys}    # copies: the host arrays may be read-only
+    if dtype is not None:
+        p = {k: v.to(dtype) if v.is_floating_point() else v for k, v in p.items()}
+        tb = {k: v.to(dtype) if k in ("entities", "actions_onehot") else v for k, v in tb.items()}
+    with torch.no_grad():
+        return RR.mac_forward(p, tb, a)[0].numpy()
+
+
+def refil_teacher_check(spec, ag, a, nb, summ, B, T, seed, eps, test_mode, envs=None, dtype=None, episode=0):
+    """Replay the recorded actions of ``envs`` (default: all) through the oracle entity env at episode index
+    ``episode``: entities, masks, avail, reward, terminated, filled, one-hot rows, lengths, won / draw bit-exact
+    (returns within 1e-3); every epsilon draw the oracle's draw from the counter RNG; every other pick an argmax of the oracle's
+    masked Q (``dtype``: refil_oracle_q), a different pick passing only where the top-two gap is within Q_TOL and the
+    pick within Q_TOL of the maximum. Returns the counts: greedy picks, decisions (greedy picks with at least two
+    available actions), near ties among them, epsilon draws."""
+    import envref
+    envs = list(range(B)) if envs is None else [int(e) for e in envs]
+    refs = ref_entity_envs_for(spec, B, seed=seed)
+    NA, A = spec.n_agents, spec.n_actions
+    qref = dict(zip(envs, refil_oracle_q(ag, a, nb, envs, dtype)))
+    n_rand = n_greedy = n_dec = n_tie = 0
+    for b in envs:
+        r = refs[b]
+        r.episode = episode
+        r.reset()
+        L = int(summ["len"][b])
+        assert 1 <= L <= T
+        ret = np.float32(0)
+        for t in range(L + 1):
+            ent, om, em = r.entities()
+            np.testing.assert_array_equal(nb["entities"][b, t], ent, err_msg=f"entities b={b} t={t}")
+            np.testing.assert_array_equal(nb["obs_mask"][b, t], om, err_msg=f"obs_mask b={b} t={t}")
+            np.testing.assert_array_equal(nb["entity_mask"][b, t], em)
+            av = r.avail()
+            np.testing.assert_array_equal(nb["avail_actions"][b, t], av)
+            assert nb["filled"][b, t, 0] == 1
+            acts = nb["actions"][b, t, :, 0]
+            for n in range(NA):
+                key = envref.env_key(seed, b)
+                u = envref.u01(envref.rng(key, envref.ctr(r.cur_episode, t, 2, n)))
+                coin = not test_mode and eps > 0 and u < np.float32(eps)  # the kernel compares in fp32
+                if coin:
+                    want = envref.random_available(av[n], envref.rng(key, envref.ctr(r.cur_episode, t, 3, n)))
+                    assert acts[n] == want
+                    n_rand += 1
+                else:
+                    qm = np.where(av[n] != 0, qref[b][t, n], -np.inf)
+                    srt = np.sort(qm)
+                    assert av[n, acts[n]] != 0 and qm[acts[n]] >= qm.max() - Q_TOL, (b, t, n)
+                    if srt[-1] - srt[-2] > Q_TOL:
+                        assert acts[n] == int(np.argmax(qm)), (b, t, n, int(acts[n]), int(np.argmax(qm)))
+                    else:
+                        n_tie += 1
+                    n_dec += int(np.isfinite(srt[-2]))
+                    n_greedy += 1
+            oh = np.zeros((NA, A), np.float32)
+            oh[np.arange(NA), acts] = 1
+            np.testing.assert_array_equal(nb["actions_onehot"][b, t], oh)
+            if t < L:
+                rew, done, info = r.step(acts)
+                assert nb["reward"][b, t, 0] == np.float32(rew[0])
+                assert nb["terminated"][b, t, 0] == int(done)
+                assert done == (t == L - 1)
+                ret += np.float32(rew[0])
+        assert summ["won"][b, 0] == int(info["battle_won"][0]) and summ["won"][b, 1] == int(info["battle_won"][1])
+        assert summ["draw"][b] == int(info["draw"])
+        assert abs(summ["ret"][b] - ret) <= 1e-3
+        assert nb["filled"][b, L + 1:].sum() == 0 and nb["reward"][b, L:].sum() == 0
+    assert n_greedy > 0 and (test_mode or n_rand > 0)
+    return {"greedy": n_greedy, "decisions": n_dec, "near_ties": n_tie, "epsilon_draws": n_rand}

@@ -8,23 +8,11 @@ import numpy as np
 import pytest
 import torch
 
-import envref
-import refil_ref as RR
-from helpers import entity_scheme_for, np_batch, ref_entity_envs_for, refil_args
+from helpers import Q_TOL, refil_args
+from helpers import refil_agent as _agent, refil_rollout as _rollout  # noqa: F401  (other suites import _rollout)
+from helpers import refil_teacher_check as _teacher_check
 
 pytestmark = pytest.mark.gpu
-
-Q_TOL = 1e-4
-
-
-def _agent(device, params=None, seed=0, **kw):
-    from maleague.modules.agents import REGISTRY
-    a = refil_args(**kw)
-    torch.manual_seed(seed)
-    ag = REGISTRY["imagine_entity_attend_rnn"](a.entity_shape + a.n_actions, a).to(device)
-    if params is not None:
-        ag.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in params.items()})
-    return ag, a
 
 
 def _params(d, prefix):
@@ -44,45 +32,6 @@ def test_agent_forward_matches_golden(device, golden):
     np.testing.assert_allclose(qi.cpu().numpy(), d["imagine.q"], atol=Q_TOL, rtol=0)
     np.testing.assert_array_equal(Wm.cpu().numpy(), d["imagine.Wmask"])
     np.testing.assert_array_equal(Im.cpu().numpy(), d["imagine.Imask"])
-
-
-def _rollout(device, B=12, T=40, seed=5, eps=0.0, test_mode=True, ring=None, agent_seed=1, st=None, kmin=3, kmax=8,
-             batch=None, extent=None):
-    from maleague import _native
-    from maleague.components.episode_batch import EpisodeBatch
-    from maleague.components.batch_view import mlg_entity_batch
-    from maleague.envs.entity_env import EntityEnvSpec
-    from maleague.envs.teams_env import VecEnvState
-    spec = EntityEnvSpec.from_env_args({"match_build_plan": "refil_8", "episode_limit": T, "seed": seed,
-                                        "min_agents": kmin, "max_agents": kmax})
-    ag, a = _agent(device, seed=agent_seed)
-    info = spec.env_info()
-    scheme, groups, pre = entity_scheme_for(info, torch)
-    if st is None:
-        st = VecEnvState(spec, B, device)
-    if batch is None:
-        batch = EpisodeBatch(scheme, groups, B, T + 1, preprocess=pre, device=device)
-        if ring is not None:
-            for v in batch.data.transition_data.values():
-                v.fill_(7)
-    mb, keep = mlg_entity_batch(batch)
-    if ring is not None:
-        mb.full_write = 1
-    if extent is not None:
-        mb.slot_extent = extent.data_ptr()
-    run = torch.zeros(6 * B, dtype=torch.int32, device=device)
-    ri = _native.MlgRunInfo(run[0:B].data_ptr(), run[4 * B:5 * B].data_ptr(), run[B:3 * B].data_ptr(),
-                            run[3 * B:4 * B].data_ptr(), None, None)
-    _native.call("mlg_refil_rollout", _native.byref(spec.to_c()), _native.byref(st.to_c()), _native.byref(ag.dims()),
-                 _native.ptr(ag.packed()), _native.byref(mb), _native.byref(ri), float(eps), int(test_mode),
-                 _native.stream_ptr())
-    torch.cuda.synchronize()
-    r = run.cpu().numpy()
-    summary = {"len": r[0:B], "won": r[B:3 * B].reshape(B, 2), "draw": r[3 * B:4 * B],
-               "ret": r[4 * B:5 * B].view(np.float32)}
-    if extent is not None:
-        _rollout.last_batch = batch
-    return spec, ag, a, np_batch(batch), summary, st
 
 
 @pytest.fixture(params=["v4", "v4g", "v1"])
@@ -118,59 +67,6 @@ def test_rollout_teacher_forced_vs_oracle(device, rollout_variant, eps, test_mod
     _teacher_check(spec, ag, a, nb, summ, B, T, seed, eps, test_mode)
 
 
-def _teacher_check(spec, ag, a, nb, summ, B, T, seed, eps, test_mode, envs=None):
-    """Replay the recorded actions of ``envs`` (default: all) through the oracle entity env; every greedy pick an
-    oracle argmax within Q_TOL, every epsilon draw bit-exact, bookkeeping and summary exact."""
-    envs = list(range(B)) if envs is None else [int(e) for e in envs]
-    refs = ref_entity_envs_for(spec, B, seed=seed)
-    NA, A = spec.n_agents, spec.n_actions
-    p = {k: v.detach().cpu() for k, v in ag.state_dict().items()}
-    qref, _ = RR.mac_forward(p, {k: torch.from_numpy(v[envs]) for k, v in nb.items()}, a)
-    qref = dict(zip(envs, qref.numpy()))
-    n_rand = n_greedy = 0
-    for b in envs:
-        r = refs[b]
-        r.reset()
-        L = int(summ["len"][b])
-        assert 1 <= L <= T
-        ret = np.float32(0)
-        for t in range(L + 1):
-            ent, om, em = r.entities()
-            np.testing.assert_array_equal(nb["entities"][b, t], ent, err_msg=f"entities b={b} t={t}")
-            np.testing.assert_array_equal(nb["obs_mask"][b, t], om, err_msg=f"obs_mask b={b} t={t}")
-            np.testing.assert_array_equal(nb["entity_mask"][b, t], em)
-            av = r.avail()
-            np.testing.assert_array_equal(nb["avail_actions"][b, t], av)
-            assert nb["filled"][b, t, 0] == 1
-            acts = nb["actions"][b, t, :, 0]
-            for n in range(NA):
-                key = envref.env_key(seed, b)
-                coin = not test_mode and eps > 0 and envref.u01(envref.rng(key, envref.ctr(r.cur_episode, t, 2, n))) < eps
-                if coin:
-                    want = envref.random_available(av[n], envref.rng(key, envref.ctr(r.cur_episode, t, 3, n)))
-                    assert acts[n] == want
-                    n_rand += 1
-                else:
-                    qm = np.where(av[n] != 0, qref[b][t, n], -np.inf)
-                    assert av[n, acts[n]] != 0 and qm[acts[n]] >= qm.max() - Q_TOL, (b, t, n)
-                    n_greedy += 1
-            oh = np.zeros((NA, A), np.float32)
-            oh[np.arange(NA), acts] = 1
-            np.testing.assert_array_equal(nb["actions_onehot"][b, t], oh)
-            if t < L:
-                rew, done, info = r.step(acts)
-                assert nb["reward"][b, t, 0] == np.float32(rew[0])
-                assert nb["terminated"][b, t, 0] == int(done)
-                assert done == (t == L - 1)
-                ret += np.float32(rew[0])
-        assert summ["won"][b, 0] == int(info["battle_won"][0]) and summ["won"][b, 1] == int(info["battle_won"][1])
-        assert summ["draw"][b] == int(info["draw"])
-        assert abs(summ["ret"][b] - ret) <= 1e-3
-        assert nb["filled"][b, L + 1:].sum() == 0 and nb["reward"][b, L:].sum() == 0
-    assert n_greedy > 0 and (test_mode or n_rand > 0)
-    return n_greedy, n_rand
-
-
 def test_rollout_config5_full_shape(device):
     """BASELINE config 5 at its launch shape (4096 envs, episode limit 100, 3-8 agents per env, train mode at the
     steady-state epsilon 0.05; 256 workgroups of the four-env kernel in one round): size-independent invariants,
@@ -197,8 +93,8 @@ def test_rollout_config5_full_shape(device):
     for k in summ:
         np.testing.assert_array_equal(summ[k], summ2[k], err_msg=k)
     sub = np.linspace(0, B - 1, 64).astype(int)
-    n_greedy, n_rand = _teacher_check(spec, ag, a, nb, summ, B, T, seed, eps, False, envs=sub)
-    assert n_greedy > 1000 and n_rand > 0
+    n = _teacher_check(spec, ag, a, nb, summ, B, T, seed, eps, False, envs=sub)
+    assert n["greedy"] > 1000 and n["epsilon_draws"] > 0
 
 
 def test_rollout_ring_full_write_equals_zeroed(device, rollout_variant):
