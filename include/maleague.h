@@ -270,6 +270,16 @@ int64_t mlg_qlearner_workspace_floats(const MlgLearnerCfg *c);
 /* Largest batch (episodes) whose slot map may travel as MlgLearnerBufs.host_rows (a kernel argument). */
 int mlg_qlearner_inline_rows(void);
 int mlg_qlearner_train(const MlgLearnerCfg *c, const MlgLearnerBufs *b, void *stream);
+/* Host only, launches nothing (the contract of mlg_rollout_describe). Writes the names of the kernels
+ * mlg_qlearner_train would launch for this cfg under the current MLG_MIX_GENERIC environment, as
+ * "<agent part> + <mixer part>", e.g. "h64/bwd-fused/q1 + qmix-split". mlg_qlearner_train takes its decisions from
+ * the same host function. Agent part: h32 | h64 | h128 (the per-H agent kernels), bwd-fused (H = 64: fc2's and the
+ * mixer's weight gradients ride in the reverse-recurrence launch, bwd4_wgrad_kernel) or bwd-split, q1..q6 (16-action
+ * tiles of agent_q_kernel). Mixer part: iql, vdn-fast / vdn and qmix-split / qmix-generic (default widths E = 32,
+ * HE = 64: the prefetching forms up to N = 8, A = 16, S = 64 / the generic mix_td_kernel<64, 32>), qmix1-e{E} (one
+ * hypernet layer), qmix-he{HE}-e{E} (the other widths). Nonzero (mlg_last_error) where mlg_qlearner_train would
+ * refuse the cfg. */
+int mlg_qlearner_describe(const MlgLearnerCfg *c, char *name, int32_t name_cap);
 
 
 /* ---- REFIL (config 5): entity scheme, EntityAttentionRNNAgent, FlexQMixer, REFILLearner ----------------- */

@@ -34,6 +34,8 @@
 //                  hyper_w_1.{weight, bias}, hyper_w_final.{weight, bias}, hyper_b_1.{weight, bias},
 //                  V.{0.weight, 0.bias, 2.weight, 2.bias}.
 #include <algorithm>
+#include <cstdio>
+#include <cstring>
 
 #include "agent_device.h"
 #include "batch_mask_device.h"
@@ -2052,9 +2054,81 @@ WJobs make_jobs(Plan& p, float* ws, float* grads, int64_t* slab_floats, int* n_t
     return J;
 }
 
+// ---- dispatch: every shape-dependent choice of a call, decided once on the host. run_train launches what this
+// says and mlg_qlearner_describe prints it, so the query cannot drift from the launches.
+enum MixKernel {
+    MIX_IQL,         // iql_td_kernel
+    MIX_VDN_FAST,    // mix_td_kernel<64, 32, true>, mixer 1
+    MIX_VDN,         // mix_td_kernel<64, 32>, mixer 1
+    MIX_QMIX_SPLIT,  // rec4_mixpre_kernel<H> + mix_td2_kernel<64, 32>
+    MIX_QMIX_FAST1,  // mix_td_kernel<64, 32, true>, mixer 2: needs threads % 128 != 0, which no H gives
+    MIX_QMIX_DFLT,   // mix_td_kernel<64, 32>, mixer 2
+    MIX_QMIX1,       // mix_td1_kernel<E>
+    MIX_QMIX_WIDTHS  // mix_td_kernel<HE, E>, the other widths
+};
+struct Dispatch {
+    bool dflt_mix, fast_mix, split_mix, fused;
+    int threads;  // workgroup size of the per-H agent kernels
+    int q_tiles;  // 16-action tiles: agent_q_kernel runs 64 q_tiles threads
+    int per;      // mixer tiles per workgroup of rec4_mixpre_kernel (split_mix)
+    MixKernel mix;
+    static constexpr bool fused_for(int H) { return H == 64; }  // 4 waves, as the wgrad workgroups
+};
+
+// MLG_MIX_GENERIC is read per call, so a test can set it. Nonzero (mlg_last_error) where no mixer kernel exists.
+int make_dispatch(const Plan& p, Dispatch* out) {
+    const LCfg& c = p.c;
+    Dispatch d;
+    // split mixer (default for the FAST shapes): the hypernetwork forward rides in the recurrence launch
+    // (rec4_mixpre_kernel), mix_td2_kernel does the rest. VDN runs the one-kernel mix_td; MLG_MIX_GENERIC=1
+    // forces its generic form (the path of the other shapes)
+    d.dflt_mix = c.mixer == 1 || (c.mixer == 2 && p.layers == 2 && c.E == 32 && c.HE == 64);
+    d.fast_mix = d.dflt_mix && p.mp.Sp <= 64 && c.N <= MIXPF_N && c.A <= MIXPF_A && !getenv("MLG_MIX_GENERIC");
+    d.threads = (c.H / 16) * 64;
+    d.split_mix = c.mixer == 2 && d.fast_mix && d.threads % 128 == 0;
+    d.per = d.threads / 128;
+    d.q_tiles = c.Ap / 16;
+    d.fused = Dispatch::fused_for(c.H);
+    if (c.mixer == 0) {
+        d.mix = MIX_IQL;
+    } else if (d.split_mix) {
+        d.mix = MIX_QMIX_SPLIT;
+    } else if (d.fast_mix) {
+        d.mix = c.mixer == 1 ? MIX_VDN_FAST : MIX_QMIX_FAST1;
+    } else if (c.mixer == 2 && p.layers == 1) {  // widths checked by check_cfg
+        d.mix = MIX_QMIX1;
+    } else if (d.dflt_mix) {
+        d.mix = c.mixer == 1 ? MIX_VDN : MIX_QMIX_DFLT;
+    } else {  // the other widths: the generic one-kernel form only
+        const bool he_ok = c.HE == 32 || c.HE == 64 || c.HE == 128, e_ok = c.E == 16 || c.E == 32 || c.E == 64;
+        if (!he_ok || !e_ok) return mlg::fail("learner: no mixer kernel for hypernet_embed=%d mixing_embed_dim=%d", c.HE, c.E);
+        d.mix = MIX_QMIX_WIDTHS;
+    }
+    *out = d;
+    return 0;
+}
+
+// "<agent part> + <mixer part>" of a dispatch (mlg_qlearner_describe; the names are listed in maleague.h)
+void dispatch_name(const LCfg& c, const Dispatch& d, char* name, size_t cap) {
+    char mix[32];
+    switch (d.mix) {
+        case MIX_IQL: snprintf(mix, sizeof mix, "iql"); break;
+        case MIX_VDN_FAST: snprintf(mix, sizeof mix, "vdn-fast"); break;
+        case MIX_VDN: snprintf(mix, sizeof mix, "vdn"); break;
+        case MIX_QMIX_SPLIT: snprintf(mix, sizeof mix, "qmix-split"); break;
+        case MIX_QMIX_FAST1: snprintf(mix, sizeof mix, "qmix-fast1"); break;
+        case MIX_QMIX_DFLT: snprintf(mix, sizeof mix, "qmix-generic"); break;
+        case MIX_QMIX1: snprintf(mix, sizeof mix, "qmix1-e%d", c.E); break;
+        case MIX_QMIX_WIDTHS: snprintf(mix, sizeof mix, "qmix-he%d-e%d", c.HE, c.E); break;
+    }
+    snprintf(name, cap, "h%d/%s/q%d + %s", c.H, d.fused ? "bwd-fused" : "bwd-split", d.q_tiles, mix);
+}
+
 template <int H>
 int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hipStream_t s) {
     const LCfg& c = p.c;
+    Dispatch dsp;
+    if (make_dispatch(p, &dsp)) return 1;
     float* ws = bufs->workspace;
     MlgBatch bt = bufs->batch;
     int32_t* rows_ws = reinterpret_cast<int32_t*>(ws + p.w.rows);
@@ -2087,13 +2161,8 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     pj.E = c.E;
     pj.HE = c.HE;
     pj.mixer = c.mixer;
-    // split mixer (default for the FAST shapes): the hypernetwork forward rides in the recurrence launch
-    // (rec4_mixpre_kernel), mix_td2_kernel does the rest. VDN runs the one-kernel mix_td; MLG_MIX_GENERIC=1
-    // forces its generic form (the path of the other shapes; read per call, so a test can set it)
-    const bool dflt_mix = c.mixer == 1 || (c.mixer == 2 && p.layers == 2 && c.E == 32 && c.HE == 64);
-    const bool fast_mix = dflt_mix && p.mp.Sp <= 64 && c.N <= MIXPF_N && c.A <= MIXPF_A && !getenv("MLG_MIX_GENERIC");
-    const int threads = (c.H / 16) * 64;
-    const bool split_mix = c.mixer == 2 && fast_mix && threads % 128 == 0;
+    const int threads = dsp.threads;
+    const bool split_mix = dsp.split_mix;
     pj.d2 = ws + p.w.d2;  // d2 is sparse: zero it (and dq) every call
     pj.dq = ws + p.w.dq;
     pj.n_d2 = (int64_t)c.T * c.R * c.A;
@@ -2151,7 +2220,7 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     hipLaunchKernelGGL((agent_in_kernel<H>), dim3(ntiles, c.T, 2), dim3(threads), 0, s, c, bt, p.L, ws + p.w.p_on,
                        ws + p.w.p_tg, ws + p.w.in, ws + p.w.x, ws + p.w.gi_on, ws + p.w.gi_tg, sk);
     if (split_mix) {
-        const int nrec = 2 * ((c.R + 3) / 4), per = threads / 128;
+        const int nrec = 2 * ((c.R + 3) / 4), per = dsp.per;
         hipLaunchKernelGGL((rec4_mixpre_kernel<H>), dim3(nrec + (p.w.n_mix_tiles + per - 1) / per), dim3(threads), 0, s,
                            c, p.L, ws + p.w.p_on, ws + p.w.p_tg, ws + p.w.gi_on, ws + p.w.gi_tg, ws + p.w.hs,
                            ws + p.w.hs_tg, ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, sk, bt, Mon,
@@ -2160,40 +2229,44 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
         hipLaunchKernelGGL((agent_rec4_kernel<H>), dim3(2 * ((c.R + 3) / 4)), dim3(threads), 0, s, c, p.L,
                            ws + p.w.p_on, ws + p.w.p_tg, ws + p.w.gi_on, ws + p.w.gi_tg, ws + p.w.hs, ws + p.w.hs_tg,
                            ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, sk);
-    hipLaunchKernelGGL((agent_q_kernel<H>), dim3(ntiles, c.T, 2), dim3(64 * (c.Ap / 16)), 0, s, c, p.L, ws + p.w.p_on,
+    hipLaunchKernelGGL((agent_q_kernel<H>), dim3(ntiles, c.T, 2), dim3(64 * dsp.q_tiles), 0, s, c, p.L, ws + p.w.p_on,
                        ws + p.w.p_tg, ws + p.w.hs, ws + p.w.hs_tg, ws + p.w.mac, ws + p.w.tmac, sk);
     MixOut mo{ws + p.w.srow, ws + p.w.l1act, ws + p.w.d1, ws + p.w.da2, ws + p.w.df2, ws + p.w.dv2,
               ws + p.w.dq, ws + p.w.d2, ws + p.w.part};
 #define MLG_MIX_LAUNCH(K)                                                                                       \
     hipLaunchKernelGGL((K), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, Mtg, p.mp, ws + p.w.mac, ws + p.w.tmac, \
                        ws + p.w.msum, mo, sk)
-    if (c.mixer == 0) {
-        hipLaunchKernelGGL(iql_td_kernel, dim3(p.w.n_mix_tiles), dim3(64), 0, s, c, bt, ws + p.w.mac, ws + p.w.tmac,
-                           ws + p.w.msum, mo, sk);
-    } else if (split_mix) {
-        hipLaunchKernelGGL((mix_td2_kernel<64, 32>), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, ws + p.w.mac,
-                           ws + p.w.tmac, ws + p.w.msum, hy, mo, sk);
-    } else if (fast_mix) {
-        MLG_MIX_LAUNCH((mix_td_kernel<64, 32, true>));
-    } else if (c.mixer == 2 && p.layers == 1) {  // widths checked by check_cfg
-        if (c.E == 16) MLG_MIX_LAUNCH(mix_td1_kernel<16>);
-        else if (c.E == 32) MLG_MIX_LAUNCH(mix_td1_kernel<32>);
-        else MLG_MIX_LAUNCH(mix_td1_kernel<64>);
-    } else if (dflt_mix) {
-        MLG_MIX_LAUNCH((mix_td_kernel<64, 32>));
-    } else {  // the other widths: the generic one-kernel form only
-        const int key = c.HE * 1000 + c.E;
-        switch (key) {
-            case 32016: MLG_MIX_LAUNCH((mix_td_kernel<32, 16>)); break;
-            case 32032: MLG_MIX_LAUNCH((mix_td_kernel<32, 32>)); break;
-            case 32064: MLG_MIX_LAUNCH((mix_td_kernel<32, 64>)); break;
-            case 64016: MLG_MIX_LAUNCH((mix_td_kernel<64, 16>)); break;
-            case 64064: MLG_MIX_LAUNCH((mix_td_kernel<64, 64>)); break;
-            case 128016: MLG_MIX_LAUNCH((mix_td_kernel<128, 16>)); break;
-            case 128032: MLG_MIX_LAUNCH((mix_td_kernel<128, 32>)); break;
-            case 128064: MLG_MIX_LAUNCH((mix_td_kernel<128, 64>)); break;
-            default: return mlg::fail("learner: no mixer kernel for hypernet_embed=%d mixing_embed_dim=%d", c.HE, c.E);
-        }
+    switch (dsp.mix) {
+        case MIX_IQL:
+            hipLaunchKernelGGL(iql_td_kernel, dim3(p.w.n_mix_tiles), dim3(64), 0, s, c, bt, ws + p.w.mac, ws + p.w.tmac,
+                               ws + p.w.msum, mo, sk);
+            break;
+        case MIX_QMIX_SPLIT:
+            hipLaunchKernelGGL((mix_td2_kernel<64, 32>), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, ws + p.w.mac,
+                               ws + p.w.tmac, ws + p.w.msum, hy, mo, sk);
+            break;
+        case MIX_VDN_FAST:
+        case MIX_QMIX_FAST1: MLG_MIX_LAUNCH((mix_td_kernel<64, 32, true>)); break;
+        case MIX_QMIX1:
+            if (c.E == 16) MLG_MIX_LAUNCH(mix_td1_kernel<16>);
+            else if (c.E == 32) MLG_MIX_LAUNCH(mix_td1_kernel<32>);
+            else MLG_MIX_LAUNCH(mix_td1_kernel<64>);
+            break;
+        case MIX_VDN:
+        case MIX_QMIX_DFLT: MLG_MIX_LAUNCH((mix_td_kernel<64, 32>)); break;
+        case MIX_QMIX_WIDTHS:
+            switch (c.HE * 1000 + c.E) {
+                case 32016: MLG_MIX_LAUNCH((mix_td_kernel<32, 16>)); break;
+                case 32032: MLG_MIX_LAUNCH((mix_td_kernel<32, 32>)); break;
+                case 32064: MLG_MIX_LAUNCH((mix_td_kernel<32, 64>)); break;
+                case 64016: MLG_MIX_LAUNCH((mix_td_kernel<64, 16>)); break;
+                case 64064: MLG_MIX_LAUNCH((mix_td_kernel<64, 64>)); break;
+                case 128016: MLG_MIX_LAUNCH((mix_td_kernel<128, 16>)); break;
+                case 128032: MLG_MIX_LAUNCH((mix_td_kernel<128, 32>)); break;
+                case 128064: MLG_MIX_LAUNCH((mix_td_kernel<128, 64>)); break;
+                default: return mlg::fail("learner: no mixer kernel for hypernet_embed=%d mixing_embed_dim=%d", c.HE, c.E);
+            }
+            break;
     }
 #undef MLG_MIX_LAUNCH
     // weight gradients: fc2 and the mixer's jobs (final after the mixer kernel, table view JA) run as extra
@@ -2205,7 +2278,7 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     int ta, tb;
     int64_t ra, rb;
     const WJobs JA = mlg::bjob_view(J, 3, J.n, &ta, &ra), JB = mlg::bjob_view(J, 0, 3, &tb, &rb);
-    constexpr bool fused = H == 64;  // 4 waves, as the wgrad workgroups
+    constexpr bool fused = Dispatch::fused_for(H);  // == dsp.fused
     if constexpr (fused) {
         const int nbwd = (c.R + 3) / 4;
         hipLaunchKernelGGL((bwd4_wgrad_kernel<H>), dim3((unsigned)(nbwd + (ta + 3) / 4)), dim3(256), 0, s, c, bt, p.L,
@@ -2265,6 +2338,19 @@ extern "C" int64_t mlg_qlearner_workspace_floats(const MlgLearnerCfg* c) {
     int tasks;
     make_jobs(p, nullptr, nullptr, &slab, &tasks, &n_red);
     return p.w.total + slab;
+}
+
+extern "C" int mlg_qlearner_describe(const MlgLearnerCfg* c, char* name, int32_t name_cap) {
+    if (check_cfg(c)) return 1;
+    MLG_REQUIRE(name && name_cap > 0, "qlearner_describe: null output");
+    Plan p = make_plan(c, c->T);
+    Dispatch d;
+    if (make_dispatch(p, &d)) return 1;
+    char full[64];
+    dispatch_name(p.c, d, full, sizeof full);
+    MLG_REQUIRE((size_t)name_cap > strlen(full), "qlearner_describe: name buffer of %d bytes too small", name_cap);
+    strcpy(name, full);
+    return 0;
 }
 
 extern "C" int mlg_qlearner_train(const MlgLearnerCfg* c, const MlgLearnerBufs* b, void* stream) {

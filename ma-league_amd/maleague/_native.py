@@ -157,6 +157,7 @@ SIGNATURES = {
     "mlg_qlearner_workspace_floats": (ctypes.c_int64, [_P]),
     "mlg_qlearner_inline_rows": (ctypes.c_int, []),
     "mlg_qlearner_train": (ctypes.c_int, [_P, _P, _P]),
+    "mlg_qlearner_describe": (ctypes.c_int, [_P, _P, _I]),
     "mlg_zero_slots_bytes": (ctypes.c_int, [_P, _P, _I, _I, _I, _P]),
     "mlg_refil_packed_agent_size": (ctypes.c_int64, [_P]),
     "mlg_refil_pack_agent": (ctypes.c_int, [_P, _P, _P, _P]),
@@ -253,6 +254,17 @@ def refil_rollout_describe(spec: MlgEntityEnvSpec, dims: MlgRefilDims) -> tuple[
     if rc != 0:
         raise NativeError(f"mlg_refil_rollout_describe failed: {lib.mlg_last_error().decode()}")
     return name.value.decode(), int(lds.value)
+
+
+def qlearner_describe(cfg: MlgLearnerCfg) -> str:
+    """"<agent part> + <mixer part>": the kernels mlg_qlearner_train would launch for this cfg under the current
+    MLG_MIX_GENERIC environment (mlg_qlearner_describe: host only, needs no GPU; the names are in maleague.h)."""
+    lib = load()
+    name = ctypes.create_string_buffer(64)
+    rc = lib.mlg_qlearner_describe(ctypes.byref(cfg), name, len(name))
+    if rc != 0:
+        raise NativeError(f"mlg_qlearner_describe failed: {lib.mlg_last_error().decode()}")
+    return name.value.decode()
 
 
 def stream_ptr(device=None) -> int:

@@ -109,13 +109,16 @@ class QLearnerRef:
     """QLearner.train + update_targets (marl/learners/q_learner.py:34-131), RMSprop (learner.py:25-31),
     clip_grad_norm_ (q_learner.py:104)."""
 
-    def __init__(self, agent_params: dict, mixer_params: dict | None, args):
+    def __init__(self, agent_params: dict, mixer_params: dict | None, args, dtype=torch.float32):
+        """dtype: torch.float32 (the reference's arithmetic), or torch.float64 for a yardstick strictly more precise
+        than any fp32 implementation (the fp32 parameters, batch and optimizer state are then carried in float64)."""
         self.args = args
-        self.p = {k: torch.tensor(np.asarray(v), dtype=torch.float32).requires_grad_(True) for k, v in agent_params.items()}
+        self.dtype = dtype
+        self.p = {k: torch.tensor(np.asarray(v), dtype=dtype).requires_grad_(True) for k, v in agent_params.items()}
         self.mixer = args.mixer
         self.mp = None
         if mixer_params is not None and args.mixer == "qmix":
-            self.mp = {k: torch.tensor(np.asarray(v), dtype=torch.float32).requires_grad_(True)
+            self.mp = {k: torch.tensor(np.asarray(v), dtype=dtype).requires_grad_(True)
                        for k, v in mixer_params.items()}
         self.tp = {k: v.detach().clone() for k, v in self.p.items()}
         self.tmp = None if self.mp is None else {k: v.detach().clone() for k, v in self.mp.items()}
@@ -124,6 +127,7 @@ class QLearnerRef:
         self.opt = torch.optim.RMSprop(params, lr=args.lr, alpha=args.optim_alpha, eps=args.optim_eps)
         self.last_target_update_episode = 0
         self.trained_steps = 0
+        self.last_grads = None  # the latest call's gradients before the clip, in self.params order
 
     def _mix(self, mp, qs, states):
         if self.mixer == "qmix":
@@ -134,6 +138,17 @@ class QLearnerRef:
         return qs
 
     def train(self, batch: dict, t_env: int, episode_num: int) -> dict:
+        if self.dtype == torch.float32:
+            return self._train(batch, t_env, episode_num)
+        prev = torch.get_default_dtype()
+        torch.set_default_dtype(self.dtype)  # the constants built along the way (h0, agent ids, zeros)
+        try:
+            batch = {k: (v.to(self.dtype) if v.is_floating_point() else v) for k, v in batch.items()}
+            return self._train(batch, t_env, episode_num)
+        finally:
+            torch.set_default_dtype(prev)
+
+    def _train(self, batch: dict, t_env: int, episode_num: int) -> dict:
         a = self.args
         N = a.n_agents
         rewards = batch["reward"][:, :-1]
@@ -167,6 +182,7 @@ class QLearnerRef:
         loss = (mtd ** 2).sum() / mask.sum()
         self.opt.zero_grad()
         loss.backward()
+        self.last_grads = [p.grad.detach().clone() for p in self.params]
         grad_norm = torch.nn.utils.clip_grad_norm_(self.params, a.grad_norm_clip)
         self.opt.step()
         if (episode_num - self.last_target_update_episode) / a.target_update_interval >= 1.0:

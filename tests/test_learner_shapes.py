@@ -114,3 +114,20 @@ def test_oracle_reproduces_shape_goldens(golden, name, kw):
     assert os.path.getsize(os.path.join(os.path.dirname(__file__), "golden", name)) <= 1 << 20
     assert not any(k.startswith("p1.") for k in d.files), "non-full form"
     assert LR.batch_from_npz(d)["obs"].shape == (4, 7, 5, 80)
+
+
+def test_oracle_reproduces_the_9v9_h128_golden(golden):
+    """The reference's QLearner off the default agent shape (N = 9, A = 23, S = 108, d_obs = 144, H = 128; two files,
+    tests/golden/make_learner_shapes_golden.py): the oracle, which the per-arm GPU tests are measured against,
+    reproduces it within test_oracle_golden.py's bounds."""
+    import learner_arm_shapes as LA
+    import learner_ref as LR
+    from test_oracle_golden import _check_learner
+    d = LA.SplitGolden(golden)
+    _check_learner("9v9-h128", qmix_args(device="cpu", **LA.GOLDEN_9V9_KW), True, lambda name: d, False)
+    for name in LA.GOLDEN_9V9:
+        assert os.path.getsize(os.path.join(os.path.dirname(__file__), "golden", name)) <= 1 << 20
+    assert not any(k.startswith("p1.") for k in d.files), "non-full form"
+    assert LR.batch_from_npz(d)["obs"].shape == (4, 7, 9, 144)
+    assert LR.batch_from_npz(d)["state"].shape == (4, 7, 108) and d["p0.agent.gru.weight_hh"].shape == (384, 128)
+    assert LA.plan_dims("9v9") == (9, 23, 108, 144)
