@@ -340,13 +340,11 @@ int mlg_refil_rollout_describe(const MlgEntityEnvSpec *spec, const MlgRefilDims 
                                int64_t *lds_bytes);
 
 /* EntityAttentionLayer.forward (src/marl/modules/layers/attention.py:24-79; in = embed = out = 64, 4 heads) over bs
- * items: x [bs][ne][64], pre_mask [bs][nq][ne], post_mask [bs][nq] (uint8, 1 = masked) -> y [bs][nq][64]. With
- * gy != nullptr also the backward of sum(y * gy): dx [bs][ne][64] written, dw_in [192][64], dw_out [64][64],
- * db_out [64] accumulated (atomic adds; caller zeroes). */
+ * items: x [bs][ne][64], pre_mask [bs][nq][ne], post_mask [bs][nq] (uint8, 1 = masked) -> y [bs][nq][64]. Forward
+ * only: its backward is mlg_refil_attention_backward below. */
 int mlg_refil_attention(const float *w_in, const float *w_out, const float *b_out, const float *x,
                         const uint8_t *pre_mask, const uint8_t *post_mask, int32_t bs, int32_t ne, int32_t nq,
-                        int32_t n_heads, float *y, const float *gy, float *dx, float *dw_in, float *dw_out,
-                        float *db_out, void *stream);
+                        int32_t n_heads, float *y, void *stream);
 
 /* FlexQMixer (flex_qmix.py:55-117): packed = 4 AttentionHyperNet blocks from the flat named_parameters() vector
  * (hyper_w_1, hyper_w_final, hyper_b_1, V); forward over R rows: agent_qs [R][NA] (plain) or [R][2 NA] with the

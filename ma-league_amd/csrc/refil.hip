@@ -17,6 +17,7 @@
 
 #include "mlg_host.h"
 #include "refil_device.h"
+#include "refil_host.h"
 
 using namespace refil;
 
@@ -62,6 +63,20 @@ struct RStamps {
     __device__ void flush() {}
 };
 #endif
+
+int check_refil_dims(const MlgRefilDims* d) {
+    MLG_REQUIRE(d != nullptr, "null refil dims");
+    MLG_REQUIRE(d->n_agents >= 1 && d->n_agents <= NAS, "refil: n_agents=%d unsupported (1..8)", d->n_agents);
+    MLG_REQUIRE(d->n_entities >= d->n_agents && d->n_entities <= NE, "refil: n_entities=%d unsupported (n_agents..16)",
+                d->n_entities);
+    MLG_REQUIRE(d->attn_embed_dim == EMB && d->rnn_hidden_dim == EMB && d->attn_n_heads == NH,
+                "refil: attn_embed_dim=%d rnn_hidden_dim=%d attn_n_heads=%d unsupported (64, 64, 4)", d->attn_embed_dim,
+                d->rnn_hidden_dim, d->attn_n_heads);
+    const int D0 = refil_d0(d);
+    MLG_REQUIRE(d->entity_shape >= 1 && D0 <= KMAX, "refil: entity input width %d unsupported (<= %d)", D0, KMAX);
+    MLG_REQUIRE(d->n_actions >= 1 && d->n_actions <= 32, "refil: n_actions=%d unsupported (<= 32)", d->n_actions);
+    return 0;
+}
 
 namespace {
 
@@ -170,39 +185,14 @@ int launch_copy(const CopyJobs& J, const float* src, float* dst, hipStream_t s) 
     return mlg::check_launch("refil pack");
 }
 
-int check_dims(const MlgRefilDims* d) {
-    MLG_REQUIRE(d != nullptr, "null refil dims");
-    MLG_REQUIRE(d->n_agents >= 1 && d->n_agents <= NAS, "refil: n_agents=%d unsupported (1..8)", d->n_agents);
-    MLG_REQUIRE(d->n_entities >= d->n_agents && d->n_entities <= NE, "refil: n_entities=%d unsupported (n_agents..16)",
-                d->n_entities);
-    MLG_REQUIRE(d->attn_embed_dim == EMB && d->rnn_hidden_dim == EMB && d->attn_n_heads == NH,
-                "refil: attn_embed_dim=%d rnn_hidden_dim=%d attn_n_heads=%d unsupported (64, 64, 4)", d->attn_embed_dim,
-                d->rnn_hidden_dim, d->attn_n_heads);
-    const int D0 = d->entity_shape + (d->entity_last_action ? d->n_actions : 0);
-    MLG_REQUIRE(d->entity_shape >= 1 && D0 <= KMAX, "refil: entity input width %d unsupported (<= %d)", D0, KMAX);
-    MLG_REQUIRE(d->n_actions >= 1 && d->n_actions <= 32, "refil: n_actions=%d unsupported (<= 32)", d->n_actions);
-    return 0;
-}
-
 __host__ inline RAgent agent_layout(const MlgRefilDims* d) {
-    return make_ragent(d->entity_shape + (d->entity_last_action ? d->n_actions : 0), d->n_actions);
+    return make_ragent(refil_d0(d), d->n_actions);
 }
 
 // ---- the agent tile (two items x 8 agent rows) ----------------------------------------------------------
-// Entity block of one item: ein (LDS [16][LDI]) -> x1 = relu(fc1) -> qkv = in_trans(x1) -> attention with the
-// item's pre-mask rows -> o rows [obase, obase + nq). The caller syncs before reusing ein/x1/qkv.
-__device__ inline void entity_block(const float* __restrict__ P, const RAgent& L, const float* ein, float* x1, float* qkv,
-                                    const uint32_t* mrow, int nq, int ne, float* o, int lane) {
-    dense_lds<true>(P + L.w1, L.K1, P + L.b1, EMB / 16, ein, LDI, L.K1 / 16, x1, LDX, lane);
-    wave_sync();
-    dense_lds<false>(P + L.win, EMB, nullptr, 3 * EMB / 16, x1, LDX, EMB / 16, qkv, LDQ, lane);
-    wave_sync();
-    attn_fwd(qkv, mrow, nq, ne, o, LDX, nullptr, lane);
-    wave_sync();
-}
-
-// Rollout form: the entity inputs arrive as the fc1 B operand in registers (xin, lane = entity row), fc1's output
-// stays in registers as in_trans' B operand; only q (agent rows, [NAS][LDX]) and k | v ([NE][LDKV]) go to LDS.
+// Rollout form of entity_block (refil_device.h): the entity inputs arrive as the fc1 B operand in registers (xin,
+// lane = entity row), fc1's output stays in registers as in_trans' B operand; only q (agent rows, [NAS][LDX]) and
+// k | v ([NE][LDKV]) go to LDS.
 constexpr int LDKV = 2 * EMB + 4;
 template <int KC1>
 __device__ inline void entity_block_reg(const float* __restrict__ P, const RAgent& L, const floatx4 (&xin)[KC1],
@@ -822,41 +812,24 @@ __global__ void __launch_bounds__(64) refil_agent_step_kernel(RAgent L, const fl
     __shared__ uint32_t emb[2];
     const int lane = threadIdx.x;
     const int i0 = blockIdx.x * 2;
-    for (int i = lane; i < 16 * LDX; i += 64) o[i] = 0.f;
-    if (lane < 32) {
+    zero_tile(o, lane);
+    if (lane < 32) {  // an item past R (the spare half of an odd R): everything masked
         const int e = lane >> 4, q = lane & 15;
-        const int it = i0 + e;
-        uint32_t bits = 0xFFFFFFFFu;
-        if (it < R && q < NEa) {
-            bits = 0;
-            for (int j = 0; j < NEa; ++j) bits |= (uint32_t)(om[((int64_t)it * NEa + q) * NEa + j] != 0) << j;
-        }
-        mrow[e][q] = bits;
-        if (q == 0) {
-            uint32_t m = 0xFFFFFFFFu;
-            if (it < R) {
-                m = 0;
-                for (int j = 0; j < NEa; ++j) m |= (uint32_t)(em[(int64_t)it * NEa + j] != 0) << j;
-                m |= ~((1u << NEa) - 1u);
-            }
-            emb[e] = m;
-        }
+        const int64_t it = i0 + e;
+        mrow[e][q] = (it < R && q < NEa) ? mask_row_bits(om + (it * NEa + q) * NEa, NEa) : 0xFFFFFFFFu;
+        if (q == 0) emb[e] = it < R ? mask_row_bits(em + it * NEa, NEa) : 0xFFFFFFFFu;
     }
     wave_sync();
     for (int e = 0; e < 2; ++e) {
-        const int it = i0 + e;
-        for (int i = lane; i < NE * L.K1; i += 64) {
-            const int j = i / L.K1, c = i % L.K1;
-            ein[j * LDI + c] = (it < R && j < NEa && c < D0) ? ent[((int64_t)it * NEa + j) * D0 + c] : 0.f;
-        }
+        const int64_t it = i0 + e;
+        load_entity_rows(it < R ? ent + it * NEa * D0 : nullptr, NEa, D0, L.K1, ein, lane, 64);
         wave_sync();
-        entity_block(P, L, ein, x1, qkv, mrow[e], NA, NEa, o + e * NAS * LDX, lane);
+        entity_block(P, L, ein, x1, qkv, mrow[e], NA, NEa, o + e * NAS * LDX, nullptr, lane);
     }
     const int col = lane & 15, g = lane >> 4;
     const int e = col >> 3, n = col & 7, it = i0 + e;
     const bool valid = it < R && n < NA;
-    uint32_t dead = 0;
-    for (int ee = 0; ee < 2; ++ee) dead |= ((emb[ee] | ~((1u << NA) - 1u)) & 0xFFu) << (8 * ee);
+    const uint32_t dead = dead_rows(emb[0], NA, NAS) | dead_rows(emb[1], NA, NAS) << 8;
     floatx4 h[4];
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
@@ -882,8 +855,6 @@ __global__ void __launch_bounds__(64) refil_agent_step_kernel(RAgent L, const fl
 
 }  // namespace
 
-int check_refil_dims(const MlgRefilDims* d) { return check_dims(d); }  // for refil_grad.hip
-
 extern "C" int mlg_refil_debug_set_stamps(void* ptr) {
 #ifdef MLG_STAMPS
     unsigned long long* p = (unsigned long long*)ptr;
@@ -896,12 +867,12 @@ extern "C" int mlg_refil_debug_set_stamps(void* ptr) {
 }
 
 extern "C" int64_t mlg_refil_packed_agent_size(const MlgRefilDims* d) {
-    if (check_dims(d)) return -1;
+    if (check_refil_dims(d)) return -1;
     return agent_layout(d).total;
 }
 
 extern "C" int mlg_refil_pack_agent(const MlgRefilDims* d, const float* flat, float* packed, void* stream) {
-    if (check_dims(d)) return 1;
+    if (check_refil_dims(d)) return 1;
     MLG_REQUIRE(flat && packed, "refil_pack_agent: null pointer");
     const RAgent L = agent_layout(d);
     if (launch_copy(agent_pack_jobs(L), flat, packed, (hipStream_t)stream)) return 1;
@@ -914,7 +885,7 @@ extern "C" int mlg_refil_pack_agent(const MlgRefilDims* d, const float* flat, fl
 extern "C" int mlg_refil_agent_forward(const MlgRefilDims* d, const float* packed, const float* entities,
                                        const uint8_t* obs_mask, const uint8_t* entity_mask, const float* h_in, float* q,
                                        float* h_out, int32_t R, void* stream) {
-    if (check_dims(d)) return 1;
+    if (check_refil_dims(d)) return 1;
     MLG_REQUIRE(packed && entities && obs_mask && entity_mask && h_in && q && h_out, "refil_agent_forward: null pointer");
     MLG_REQUIRE(R >= 0, "refil_agent_forward: R=%d", R);
     if (R == 0) return 0;
@@ -937,7 +908,7 @@ struct RefilRolloutPlan {
 };
 
 int plan_refil_rollout(const MlgEntityEnvSpec* spec, const MlgRefilDims* d, RefilRolloutPlan* plan) {
-    if (check_dims(d)) return 1;
+    if (check_refil_dims(d)) return 1;
     MLG_REQUIRE(spec != nullptr, "refil_rollout: null argument");
     const MlgEnvSpec& sp = spec->base;
     const int S = sp.U / 2;

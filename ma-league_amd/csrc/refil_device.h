@@ -190,6 +190,17 @@ __device__ __forceinline__ floatx4 relu4(floatx4 v) {
     return v;
 }
 
+template <int MT>
+__device__ __forceinline__ void zero_acc(floatx4 (&acc)[MT]) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+}
+
+// zero the 16 rows of an attention output tile o (LDS [16][LDX]): the rows no query writes stay zero
+__device__ __forceinline__ void zero_tile(float* o, int lane) {
+    for (int i = lane; i < 16 * LDX; i += 64) o[i] = 0.f;
+}
+
 // Y[16][64 * G] rows of LDS = act(bias + W X) for 4*G output tiles (G groups of 4 tiles)
 template <bool RELU>
 __device__ __forceinline__ void dense_lds(const float* __restrict__ W, int ldw, const float* bias, int mtiles,
@@ -493,6 +504,139 @@ __device__ __forceinline__ float mw(float x, int softmax) {
 __device__ __forceinline__ float mw_bwd(float dy, float y, float x, int softmax) {
     if (!softmax) return dy * sgnf(x);
     return y * (dy - sum32(y * dy));
+}
+
+// ---- masks -----------------------------------------------------------------------------------------------
+// a mask row of n <= NE bytes as bits (bit j = byte j != 0), bits >= n set: the NE loads are unrolled and issued
+// back to back (a loop over the runtime n waited for each byte in turn; these sit on every per-item kernel's
+// critical path)
+__device__ __forceinline__ uint32_t mask_row_bits(const uint8_t* row, int n) {
+    uint32_t m = ~((1u << n) - 1u) & 0xFFFFu;
+    uint8_t v[NE];
+#pragma unroll
+    for (int j = 0; j < NE; ++j) v[j] = row[j < n ? j : 0];
+#pragma unroll
+    for (int j = 0; j < NE; ++j) m |= (uint32_t)(j < n && v[j] != 0) << j;
+    return m;
+}
+// dead agent rows among the low `width` tile rows, from the entity-mask bits: the entity-masked agents and the
+// padding rows >= n_agents
+__device__ __forceinline__ uint32_t dead_rows(uint32_t em, int n_agents, int width) {
+    const uint32_t agents = (1u << n_agents) - 1u;
+    return ((em & agents) | ~agents) & ((1u << width) - 1u);
+}
+
+// ---- one item of each layer: the forward its op and its backward both run --------------------------------
+// Each takes the item's LDS buffers as arguments and ends on a wave_sync (single wave per item).
+//
+// EntityAttentionLayer up to the attention output (attention.py:24-66): x rows [ne][64] -> sx, pre-mask rows
+// [nq][ne] -> mrow, qkv = in_trans(x), o = attention (rows no query writes are zero); the weights P are kept when
+// Pw is non-null. Padding slots >= ne / >= nq hold zeros; a query row whose every key is masked gives o = P = 0.
+__device__ inline void attn_item_fwd(const float* __restrict__ w_in, const float* __restrict__ x,
+                                     const uint8_t* __restrict__ pre, int ne, int nq, float* sx, float* qkv, float* o,
+                                     uint32_t* mrow, float* Pw, int lane) {
+    for (int i = lane; i < NE * EMB; i += 64) {
+        const int j = i / EMB, c = i % EMB;
+        sx[j * LDX + c] = j < ne ? x[(int64_t)j * EMB + c] : 0.f;
+    }
+    zero_tile(o, lane);
+    if (lane < 16) mrow[lane] = lane < nq ? mask_row_bits(pre + (int64_t)lane * ne, ne) : 0xFFFFFFFFu;
+    wave_sync();
+    dense_lds<false>(w_in, EMB, nullptr, 3 * EMB / 16, sx, LDX, EMB / 16, qkv, LDQ, lane);
+    wave_sync();
+    attn_fwd(qkv, mrow, nq, ne, o, LDX, Pw, lane);
+    wave_sync();
+}
+
+// entity rows [ne][D0] of one item (null: no such item) -> ein (LDS [NE][LDI]), zeros past ne rows / D0 columns
+__device__ __forceinline__ void load_entity_rows(const float* __restrict__ ent, int ne, int D0, int K1, float* ein,
+                                                 int tid, int nthreads) {
+    for (int i = tid; i < NE * K1; i += nthreads) {
+        const int j = i / K1, c = i % K1;
+        ein[j * LDI + c] = (ent && j < ne && c < D0) ? ent[(int64_t)j * D0 + c] : 0.f;
+    }
+}
+
+// Entity block of an agent or hypernet (L = RAgent or RHyper): ein -> x1 = relu(fc1) -> qkv = in_trans(x1) ...
+template <class Layer>
+__device__ inline void entity_qkv(const float* __restrict__ P, const Layer& L, const float* ein, float* x1, float* qkv,
+                                  int lane) {
+    dense_lds<true>(P + L.w1, L.K1, P + L.b1, EMB / 16, ein, LDI, L.K1 / 16, x1, LDX, lane);
+    wave_sync();
+    dense_lds<false>(P + L.win, EMB, nullptr, 3 * EMB / 16, x1, LDX, EMB / 16, qkv, LDQ, lane);
+    wave_sync();
+}
+// ... -> attention with the item's pre-mask rows -> o rows [0, nq) (weights kept when Pw is non-null). The caller
+// syncs before reusing ein / x1 / qkv.
+__device__ inline void entity_block(const float* __restrict__ P, const RAgent& L, const float* ein, float* x1, float* qkv,
+                                    const uint32_t* mrow, int nq, int ne, float* o, float* Pw, int lane) {
+    entity_qkv(P, L, ein, x1, qkv, lane);
+    attn_fwd(qkv, mrow, nq, ne, o, LDX, Pw, lane);
+    wave_sync();
+}
+
+// AttentionHyperNet over one mixer row (flex_qmix.py:28-53): ein -> fc1 -> in_trans -> attention -> out_trans ->
+// post mask -> fc2 -> post mask. One attention pass under the default mask (entity mask; every key for a dead agent),
+// or, with the row's imagine masks wm / im [NE][NE] (hyper_w_1 only), two over one qkv: W into o rows 0-7, I into
+// rows 8-15. m: LDS [2][16] mask rows; Pw: null or LDS [2][NH * 16 * NE]. Lane (col, g) holds tile row col = (pass
+// col >> 3, agent col & 7) of x2 (out_trans, post-masked) and X (fc2, post-masked). Returns the dead agent rows.
+__device__ inline uint32_t hyper_rows_fwd(const float* __restrict__ P, const RHyper& L, int NA, int NEa,
+                                          const uint8_t* __restrict__ em, const uint8_t* __restrict__ wm,
+                                          const uint8_t* __restrict__ im, const float* ein, float* x1, float* qkv,
+                                          float* o, uint32_t (*m)[16], float* Pw, int lane, floatx4 (&x2)[4],
+                                          floatx4 (&X)[2]) {
+    const uint32_t emb = mask_row_bits(em, NEa), dead = dead_rows(emb, NA, NAS);
+    const int V = wm ? 2 : 1;
+    zero_tile(o, lane);
+    if (lane < 16) {
+        if (wm) {
+            m[0][lane] = lane < NEa ? mask_row_bits(wm + lane * NEa, NEa) : 0xFFFFu;
+            m[1][lane] = lane < NEa ? mask_row_bits(im + lane * NEa, NEa) : 0xFFFFu;
+        } else {
+            m[0][lane] = ((dead >> lane) & 1u) ? 0xFFFFu : emb;
+        }
+    }
+    wave_sync();
+    entity_qkv(P, L, ein, x1, qkv, lane);
+    for (int v = 0; v < V; ++v)
+        attn_fwd(qkv, m[v], NA, NEa, o + v * NAS * LDX, LDX, Pw ? Pw + v * NH * 16 * NE : nullptr, lane);
+    wave_sync();
+    const bool rdead = (dead >> (lane & 7)) & 1u;
+    bias_init<4>(x2, P + L.bout, 0, lane);
+    mm_lds<4>(x2, P + L.wout, EMB, 0, o, LDX, EMB / 16, lane);
+    if (rdead) zero_acc<4>(x2);
+    bias_init<2>(X, P + L.b2, 0, lane);
+    mm_reg<2, 4>(X, P + L.w2, EMB, 0, x2, lane);
+    if (rdead) zero_acc<2>(X);
+    return dead;
+}
+
+// FlexQMixer mixing of one row (flex_qmix.py:91-117), lane e of a 32-lane half. X: the row's five hypernet outputs
+// [5][NAS][EM] (w1 plain or W, w1 I, w_final, b1, V; LDS or HBM); qs: its nrow = NA or 2 NA agent qs.
+//   pre_e = b1_e + sum_q qs_q mw(x_q)_e,  q_tot = sum_e elu(pre_e) mw(wfp)_e + v;  b1, wfp = agent means, v = mean of V
+struct MixRow {
+    float wfp, wf, pre, hid, q_tot;
+};
+__device__ __forceinline__ MixRow mix_row(const float* X, const float* qs, int NA, int nrow, int softmax, int e) {
+    MixRow r;
+    float b1 = 0.f, vs = 0.f;
+    r.wfp = 0.f;
+    for (int q = 0; q < NA; ++q) {
+        b1 += X[(3 * NAS + q) * EM + e];
+        r.wfp += X[(2 * NAS + q) * EM + e];
+        vs += X[(4 * NAS + q) * EM + e];
+    }
+    b1 /= (float)NA;
+    r.wfp /= (float)NA;
+    r.wf = mw(r.wfp, softmax);
+    r.pre = b1;
+    for (int q = 0; q < nrow; ++q) {
+        const float xw = q < NA ? X[q * EM + e] : X[(NAS + q - NA) * EM + e];
+        r.pre += qs[q] * mw(xw, softmax);
+    }
+    r.hid = elu_f(r.pre);
+    r.q_tot = sum32(r.hid * r.wf) + sum32(vs) / ((float)NA * (float)EM);
+    return r;
 }
 
 // ---- GRUCell on one 16-row tile, x and h in registers (D layout), PyTorch gate order r, z, n ------------

@@ -11,12 +11,10 @@
 // float atomics).
 #include "mlg_host.h"
 #include "refil_device.h"
+#include "refil_host.h"
 #include "wgrad_device.h"
 
 using namespace refil;
-
-int check_refil_dims(const MlgRefilDims* d);        // refil.hip
-int check_refil_mixer_dims(const MlgRefilDims* d);  // refil_layers.hip
 
 namespace {
 
@@ -50,10 +48,38 @@ __device__ __forceinline__ void mmT_reg(floatx4 (&acc)[MT], const float* __restr
             acc[i] = mfma_chunk(ld_col4(W, kc * 16 + 4 * g, ldw, (mt0 + i) * 16 + col), x[kc], acc[i]);
 }
 
-template <int MT>
-__device__ __forceinline__ void zero_acc(floatx4 (&acc)[MT]) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+// The workspace plan every backward shares: the row pass' buffers first (take, in the op's own order), then the wgrad
+// slab of its jobs J (finish). n_params = floats of dparams.
+struct GradPlan {
+    int64_t slab, nrm, total, n_params;
+    int n_tasks;
+    int64_t n_red;
+    GJobs J;
+    int64_t take(int64_t n) {
+        const int64_t at = slab;
+        slab += mlg_align4(n);
+        return at;
+    }
+    void finish() {
+        int64_t slab_part;
+        const int64_t n = mlg::layout_bjobs(J, &n_tasks, &n_red, &slab_part);
+        nrm = slab + slab_part;
+        total = slab + n;
+    }
+};
+
+// The shape of the three entry points once the dims are checked and the plan is made: an empty batch only zeroes
+// dparams; otherwise `rows` checks the remaining pointers and launches the row pass, then the wgrad jobs run.
+template <class Rows>
+int run_backward(const char* what, const GradPlan& pl, int n, float* dparams, float* ws, hipStream_t s, Rows rows) {
+    if (n == 0) {
+        if (hipMemsetAsync(dparams, 0, (size_t)pl.n_params * sizeof(float), s) != hipSuccess)
+            return mlg::fail("%s: zeroing dparams failed", what);
+        return 0;
+    }
+    MLG_REQUIRE(ws && aligned16(ws), "%s: workspace must be non-null and 16-byte aligned", what);
+    if (rows() || mlg::check_launch(what)) return 1;
+    return run_jobs(pl.J, pl.n_tasks, pl.n_red, ws + pl.slab, ws + pl.nrm, s, what);
 }
 
 // ---- EntityAttentionLayer ------------------------------------------------------------------------------------------
@@ -64,9 +90,9 @@ struct AttnGradWs {
     float *dqkv;  // [bs ne][192] delta at in_trans' output
 };
 
-// One wave per item, laid out like attention_kernel (refil_layers.hip): x -> qkv -> attention (weights P kept in LDS)
-// -> o, then dout = gy [row alive]; dO = W_out^T dout; attn_bwd; dx = W_in^T dqkv. Padding slots >= ne / >= nq hold
-// zeros throughout; a query row whose every key is masked has P = 0 and passes nothing (attention.py:59).
+// One wave per item: the forward of attention_kernel (attn_item_fwd, weights P kept in LDS), then dout = gy [row alive];
+// dO = W_out^T dout; attn_bwd; dx = W_in^T dqkv. A query row whose every key is masked has P = 0 and passes nothing
+// (attention.py:59).
 __global__ void __launch_bounds__(64) attention_backward_kernel(const float* __restrict__ w_in,
                                                                 const float* __restrict__ w_out,
                                                                 const float* __restrict__ x,
@@ -82,42 +108,20 @@ __global__ void __launch_bounds__(64) attention_backward_kernel(const float* __r
     __shared__ float s_P[NH * 16 * NE];
     __shared__ float s_ds[NH * 16 * NE];
     __shared__ uint32_t s_m[16];
-    __shared__ uint32_t s_dead;
-    const int lane = threadIdx.x, it = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t it = blockIdx.x;
     const int col = lane & 15, g = lane >> 4;
-    for (int i = lane; i < NE * EMB; i += 64) {
-        const int j = i / EMB, c = i % EMB;
-        s_x[j * LDX + c] = j < ne ? x[((int64_t)it * ne + j) * EMB + c] : 0.f;
-    }
-    for (int i = lane; i < 16 * LDX; i += 64) s_o[i] = 0.f;
-    if (lane < 16) {
-        uint32_t m = 0xFFFFFFFFu;
-        if (lane < nq) {
-            m = ~((1u << ne) - 1u);
-            for (int j = 0; j < ne; ++j) m |= (uint32_t)(pre[((int64_t)it * nq + lane) * ne + j] != 0) << j;
-        }
-        s_m[lane] = m;
-    }
-    if (lane == 0) {
-        uint32_t d = ~((1u << nq) - 1u) & 0xFFFFu;
-        for (int q = 0; q < nq; ++q) d |= (uint32_t)(post[(int64_t)it * nq + q] != 0) << q;
-        s_dead = d;
-    }
-    wave_sync();
-    dense_lds<false>(w_in, EMB, nullptr, 3 * EMB / 16, s_x, LDX, EMB / 16, s_qkv, LDQ, lane);
-    wave_sync();
-    attn_fwd(s_qkv, s_m, nq, ne, s_o, LDX, s_P, lane);
-    wave_sync();
+    attn_item_fwd(w_in, x + it * ne * EMB, pre + it * nq * ne, ne, nq, s_x, s_qkv, s_o, s_m, s_P, lane);
     // dout rows (all 16, zeros past nq and for post-masked rows) into s_dqkv as scratch; o and dout rows to the workspace
-    const uint32_t dead = s_dead;
+    const uint32_t dead = mask_row_bits(post + it * nq, nq);
     for (int i = lane; i < 16 * EMB; i += 64) {
         const int q = i / EMB, c = i % EMB;
         const bool live = q < nq && !((dead >> q) & 1u);
-        const float d = live ? gy[((int64_t)it * nq + q) * EMB + c] : 0.f;
+        const float d = live ? gy[(it * nq + q) * EMB + c] : 0.f;
         s_dqkv[q * LDQ + c] = d;
         if (q < nq) {
-            w.dout[((int64_t)it * nq + q) * EMB + c] = d;
-            w.o[((int64_t)it * nq + q) * EMB + c] = s_o[q * LDX + c];
+            w.dout[(it * nq + q) * EMB + c] = d;
+            w.o[(it * nq + q) * EMB + c] = s_o[q * LDX + c];
         }
     }
     wave_sync();
@@ -131,35 +135,25 @@ __global__ void __launch_bounds__(64) attention_backward_kernel(const float* __r
     wave_sync();
     for (int i = lane; i < ne * 3 * EMB; i += 64) {
         const int j = i / (3 * EMB), f = i % (3 * EMB);
-        w.dqkv[((int64_t)it * ne + j) * 3 * EMB + f] = s_dqkv[j * LDQ + f];
+        w.dqkv[(it * ne + j) * 3 * EMB + f] = s_dqkv[j * LDQ + f];
     }
     zero_acc<4>(acc);
     mmT_lds<4>(acc, w_in, EMB, 0, s_dqkv, LDQ, 3 * EMB / 16, lane);  // dx = W_in^T dqkv
     if (col < ne) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) st4(dx + ((int64_t)it * ne + col) * EMB + i * 16 + 4 * g, acc[i]);
+        for (int i = 0; i < 4; ++i) st4(dx + (it * ne + col) * EMB + i * 16 + 4 * g, acc[i]);
     }
 }
 
-struct AttnGradPlan {
-    int64_t o, dout, dqkv, slab, nrm, total, n_params;
-    int n_tasks;
-    int64_t n_red;
-    GJobs J;
+struct AttnGradPlan : GradPlan {
+    int64_t o, dout, dqkv;
 };
 
 AttnGradPlan attn_grad_plan(int bs, int ne, int nq, float* ws, const float* x, float* dparams) {
     AttnGradPlan p{};
-    int64_t o = 0;
-    auto take = [&](int64_t n) {
-        const int64_t at = o;
-        o += mlg_align4(n);
-        return at;
-    };
-    p.o = take((int64_t)bs * nq * EMB);
-    p.dout = take((int64_t)bs * nq * EMB);
-    p.dqkv = take((int64_t)bs * ne * 3 * EMB);
-    p.slab = o;
+    p.o = p.take((int64_t)bs * nq * EMB);
+    p.dout = p.take((int64_t)bs * nq * EMB);
+    p.dqkv = p.take((int64_t)bs * ne * 3 * EMB);
     // dparams in named_parameters() order: in_trans.weight [192][64], out_trans.weight [64][64], out_trans.bias [64]
     const int64_t win = 0, wout = win + 3 * EMB * EMB, bout = wout + EMB * EMB;
     p.n_params = bout + EMB;
@@ -169,10 +163,7 @@ AttnGradPlan attn_grad_plan(int bs, int ne, int nq, float* ws, const float* x, f
     J.n = 0;
     J.j[J.n++] = mlg::bjob(at(p.dqkv), 3 * EMB, x, EMB, gp(win), nullptr, 3 * EMB, EMB, bs * ne);
     J.j[J.n++] = mlg::bjob(at(p.dout), EMB, at(p.o), EMB, gp(wout), gp(bout), EMB, EMB, bs * nq);
-    int64_t slab_part;
-    const int64_t slab = mlg::layout_bjobs(J, &p.n_tasks, &p.n_red, &slab_part);
-    p.nrm = p.slab + slab_part;
-    p.total = p.slab + slab;
+    p.finish();
     return p;
 }
 
@@ -225,45 +216,25 @@ __global__ void __launch_bounds__(64) refil_agent_backward_kernel(RAgent L, cons
     __shared__ float s_P[NH * 16 * NE];
     __shared__ float s_ds[NH * 16 * NE];
     __shared__ uint32_t s_m[16];
-    __shared__ uint32_t s_dead;
-    const int lane = threadIdx.x, it = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t it = blockIdx.x;
     const int col = lane & 15, g = lane >> 4;
-    const int D0 = L.D0, A = L.A;
+    const int A = L.A;
     const floatx4 zero = {0.f, 0.f, 0.f, 0.f};
-    for (int i = lane; i < NE * L.K1; i += 64) {
-        const int j = i / L.K1, c = i % L.K1;
-        s_ein[j * LDI + c] = (j < NEa && c < D0) ? ent[((int64_t)it * NEa + j) * D0 + c] : 0.f;
-    }
-    for (int i = lane; i < 16 * LDX; i += 64) s_o[i] = 0.f;
-    if (lane < 16) {
-        uint32_t bits = 0xFFFFFFFFu;
-        if (lane < NEa) {
-            bits = 0;
-            for (int j = 0; j < NEa; ++j) bits |= (uint32_t)(om[((int64_t)it * NEa + lane) * NEa + j] != 0) << j;
-        }
-        s_m[lane] = bits;
-    }
-    if (lane == 0) {
-        uint32_t m = 0;
-        for (int j = 0; j < NA; ++j) m |= (uint32_t)(em[(int64_t)it * NEa + j] != 0) << j;
-        s_dead = (m | ~((1u << NA) - 1u)) & 0xFFFFu;  // masked agents and the tile rows past NA
-    }
+    // ---- forward: entity block (attention weights kept) ----
+    load_entity_rows(ent + it * NEa * L.D0, NEa, L.D0, L.K1, s_ein, lane, 64);
+    zero_tile(s_o, lane);
+    if (lane < 16) s_m[lane] = lane < NEa ? mask_row_bits(om + (it * NEa + lane) * NEa, NEa) : 0xFFFFFFFFu;
     wave_sync();
-    // ---- forward: entity block ----
-    dense_lds<true>(P + L.w1, L.K1, P + L.b1, EMB / 16, s_ein, LDI, L.K1 / 16, s_x1, LDX, lane);
-    wave_sync();
-    dense_lds<false>(P + L.win, EMB, nullptr, 3 * EMB / 16, s_x1, LDX, EMB / 16, s_qkv, LDQ, lane);
-    wave_sync();
-    attn_fwd(s_qkv, s_m, NA, NEa, s_o, LDX, s_P, lane);
-    wave_sync();
+    entity_block(P, L, s_ein, s_x1, s_qkv, s_m, NA, NEa, s_o, s_P, lane);
     for (int i = lane; i < NEa * EMB; i += 64) {
         const int j = i / EMB, c = i % EMB;
-        w.x1[((int64_t)it * NEa + j) * EMB + c] = s_x1[j * LDX + c];
+        w.x1[(it * NEa + j) * EMB + c] = s_x1[j * LDX + c];
     }
     // ---- forward: agent rows (tile row col = agent col) ----
     const bool valid = col < NA;
-    const bool rdead = (s_dead >> col) & 1u;
-    const int64_t row = (int64_t)it * NA + col;
+    const bool rdead = (dead_rows(mask_row_bits(em + it * NEa, NEa), NA, 16) >> col) & 1u;  // also the rows past NA
+    const int64_t row = it * NA + col;
     const int64_t rh = row * EMB, r3 = row * 3 * EMB;
     floatx4 x2[4], x3[4], h[4];
     bias_init<4>(x2, P + L.bout, 0, lane);
@@ -371,7 +342,7 @@ __global__ void __launch_bounds__(64) refil_agent_backward_kernel(RAgent L, cons
     wave_sync();
     for (int i = lane; i < NEa * 3 * EMB; i += 64) {
         const int j = i / (3 * EMB), f = i % (3 * EMB);
-        w.dqkv[((int64_t)it * NEa + j) * 3 * EMB + f] = s_dqkv[j * LDQ + f];
+        w.dqkv[(it * NEa + j) * 3 * EMB + f] = s_dqkv[j * LDQ + f];
     }
     // ---- dx1 = (W_in^T dqkv) [x1 > 0] (tile row col = entity col) ----
     floatx4 acc[4];
@@ -384,43 +355,33 @@ __global__ void __launch_bounds__(64) refil_agent_backward_kernel(RAgent L, cons
             floatx4 d;
 #pragma unroll
             for (int r = 0; r < 4; ++r) d[r] = xv[r] > 0.f ? acc[c][r] : 0.f;
-            st4(w.dx1 + ((int64_t)it * NEa + col) * EMB + c * 16 + 4 * g, d);
+            st4(w.dx1 + (it * NEa + col) * EMB + c * 16 + 4 * g, d);
         }
     }
 }
 
-struct RAgentGradPlan {
-    int64_t x1, dx1, dqkv, o, dout, x2, dx3, x3, dgi, dgh, hp, gq, slab, nrm, total, n_params;
-    int n_tasks;
-    int64_t n_red;
-    GJobs J;
+struct RAgentGradPlan : GradPlan {
+    int64_t x1, dx1, dqkv, o, dout, x2, dx3, x3, dgi, dgh, hp, gq;
 };
 
 RAgentGradPlan ragent_grad_plan(const MlgRefilDims& d, int R, float* ws, const float* entities, const float* h_in,
                                 float* dparams) {
     RAgentGradPlan p{};
     const int NA = d.n_agents, NEa = d.n_entities, A = d.n_actions;
-    const RAgent L = make_ragent(d.entity_shape + (d.entity_last_action ? d.n_actions : 0), A);
+    const RAgent L = make_ragent(refil_d0(&d), A);
     const int64_t re = (int64_t)R * NEa, ra = (int64_t)R * NA;
-    int64_t o = 0;
-    auto take = [&](int64_t n) {
-        const int64_t at = o;
-        o += mlg_align4(n);
-        return at;
-    };
-    p.x1 = take(re * EMB);
-    p.dx1 = take(re * EMB);
-    p.dqkv = take(re * 3 * EMB);
-    p.o = take(ra * EMB);
-    p.dout = take(ra * EMB);
-    p.x2 = take(ra * EMB);
-    p.dx3 = take(ra * EMB);
-    p.x3 = take(ra * EMB);
-    p.dgi = take(ra * 3 * EMB);
-    p.dgh = take(ra * 3 * EMB);
-    p.hp = take(ra * EMB);
-    p.gq = take(ra * A);
-    p.slab = o;
+    p.x1 = p.take(re * EMB);
+    p.dx1 = p.take(re * EMB);
+    p.dqkv = p.take(re * 3 * EMB);
+    p.o = p.take(ra * EMB);
+    p.dout = p.take(ra * EMB);
+    p.x2 = p.take(ra * EMB);
+    p.dx3 = p.take(ra * EMB);
+    p.x3 = p.take(ra * EMB);
+    p.dgi = p.take(ra * 3 * EMB);
+    p.dgh = p.take(ra * 3 * EMB);
+    p.hp = p.take(ra * EMB);
+    p.gq = p.take(ra * A);
     p.n_params = L.c_total;
     auto at = [&](int64_t off) { return ws ? ws + off : (float*)nullptr; };
     auto gp = [&](int64_t off) { return dparams ? dparams + off : (float*)nullptr; };
@@ -434,16 +395,13 @@ RAgentGradPlan ragent_grad_plan(const MlgRefilDims& d, int R, float* ws, const f
     J.j[J.n++] = mlg::bjob(at(p.dgi), 3 * EMB, at(p.x3), EMB, gp(L.c_wih), gp(L.c_bih), 3 * EMB, EMB, (int)ra);
     J.j[J.n++] = mlg::bjob(at(p.dgh), 3 * EMB, h_in, EMB, gp(L.c_whh), gp(L.c_bhh), 3 * EMB, EMB, (int)ra);
     J.j[J.n++] = mlg::bjob(at(p.gq), A, at(p.hp), EMB, gp(L.c_w3), gp(L.c_b3), A, EMB, (int)ra);
-    int64_t slab_part;
-    const int64_t slab = mlg::layout_bjobs(J, &p.n_tasks, &p.n_red, &slab_part);
-    p.nrm = p.slab + slab_part;
-    p.total = p.slab + slab;
+    p.finish();
     return p;
 }
 
 // ---- FlexQMixer --------------------------------------------------------------------------------------------------
-// Three row passes: (A) one wave per (row, hypernet) recomputes the hypernet's output X as mixer_fwd_kernel does and
-// writes it to the workspace ([R][5 slots][8 agent rows][32]: w1 (plain or W), w1 I, w_final, b1, V); (B) one 32-lane
+// Three row passes: (A) one wave per (row, hypernet) recomputes the hypernet's output X (hyper_rows_fwd, the forward of
+// mixer_fwd_kernel) and writes it to the workspace ([R][5 slots][8 agent rows][32]: w1 (plain or W), w1 I, w_final, b1, V); (B) one 32-lane
 // half per row redoes the mixing (flex_qmix.py:91-117) and writes dX per slot and d_agent_qs; (C) one wave per (row,
 // hypernet) recomputes the hypernet again with the attention weights kept and walks back through it:
 //   dx3 = dX [agent alive];  dout = (W2^T dx3) [agent alive];  dO = W_out^T dout;  attn_bwd;  dx1 = (W_in^T dqkv) [x1 > 0]
@@ -480,76 +438,39 @@ __global__ void __launch_bounds__(64) mixer_hyper_kernel(RHyper L, MixGradArgs a
     __shared__ float s_x1[NE * LDX];
     __shared__ float s_qkv[NE * LDQ];
     __shared__ float s_o[16 * LDX];
-    __shared__ float s_P[2][NH * 16 * NE];
+    __shared__ float s_P[BWD ? 2 * NH * 16 * NE : 4];
     __shared__ float s_do[BWD ? 16 * LDX : 4];
     __shared__ float s_dqkv[BWD ? NE * LDQ : 4];
     __shared__ float s_ds[BWD ? NH * 16 * NE : 4];
-    __shared__ uint32_t s_m[3][16];
-    __shared__ uint32_t s_dead;
-    const int lane = threadIdx.x, r = blockIdx.x, k = blockIdx.y;
+    __shared__ uint32_t s_m[2][16];
+    const int lane = threadIdx.x, k = blockIdx.y;
+    const int64_t r = blockIdx.x;
     const int col = lane & 15, g = lane >> 4;
     const int NA = a.NA;
     const int V = (k == 0 && a.imagine) ? 2 : 1;
     const floatx4 zero = {0.f, 0.f, 0.f, 0.f};
-    for (int i = lane; i < NE * L.K1; i += 64) {
-        const int j = i / L.K1, c = i % L.K1;
-        s_ein[j * LDI + c] = (j < a.NE && c < a.D0) ? a.ent[((int64_t)r * a.NE + j) * a.D0 + c] : 0.f;
-    }
-    for (int i = lane; i < 16 * LDX; i += 64) s_o[i] = 0.f;
-    if (lane < 16) {  // the masks of mixer_fwd_kernel
-        const int q = lane;
-        uint32_t em = ~((1u << a.NE) - 1u) & 0xFFFFu;
-        for (int j = 0; j < a.NE; ++j) em |= (uint32_t)(a.em[(int64_t)r * a.NE + j] != 0) << j;
-        const uint32_t dead = ((em & ((1u << NA) - 1u)) | ~((1u << NA) - 1u)) & 0xFFu;
-        s_m[0][q] = (q < NAS && ((dead >> q) & 1u)) ? 0xFFFFu : em;
-        if (a.imagine) {
-            uint32_t wb = ~((1u << a.NE) - 1u) & 0xFFFFu, ib = wb;
-            if (q < a.NE) {
-                for (int j = 0; j < a.NE; ++j) {
-                    wb |= (uint32_t)(a.wm[((int64_t)r * a.NE + q) * a.NE + j] != 0) << j;
-                    ib |= (uint32_t)(a.im[((int64_t)r * a.NE + q) * a.NE + j] != 0) << j;
-                }
-            } else {
-                wb = ib = 0xFFFFu;
-            }
-            s_m[1][q] = wb;
-            s_m[2][q] = ib;
-        }
-        if (q == 0) s_dead = dead;
-    }
-    wave_sync();
     const float* P = a.packed + (int64_t)k * L.total;
-    dense_lds<true>(P + L.w1, L.K1, P + L.b1, EMB / 16, s_ein, LDI, L.K1 / 16, s_x1, LDX, lane);
-    wave_sync();
-    dense_lds<false>(P + L.win, EMB, nullptr, 3 * EMB / 16, s_x1, LDX, EMB / 16, s_qkv, LDQ, lane);
-    wave_sync();
-    for (int v = 0; v < V; ++v)
-        attn_fwd(s_qkv, s_m[V == 2 ? v + 1 : 0], NA, a.NE, s_o + v * NAS * LDX, LDX, s_P[v], lane);
-    wave_sync();
+    const int64_t mrow = r * a.NE * a.NE;
+    load_entity_rows(a.ent + r * a.NE * a.D0, a.NE, a.D0, L.K1, s_ein, lane, 64);
+    floatx4 x2[4], X[2];
+    const uint32_t dead =
+        hyper_rows_fwd(P, L, NA, a.NE, a.em + r * a.NE, V == 2 ? a.wm + mrow : nullptr, V == 2 ? a.im + mrow : nullptr,
+                       s_ein, s_x1, s_qkv, s_o, s_m, BWD ? s_P : nullptr, lane, x2, X);
     const int v = col >> 3, n = col & 7;
-    const bool rdead = (s_dead >> n) & 1u;  // masked agents and the slots past NA
-    floatx4 x2[4];
-    bias_init<4>(x2, P + L.bout, 0, lane);
-    mm_lds<4>(x2, P + L.wout, EMB, 0, s_o, LDX, EMB / 16, lane);
-    if (rdead) zero_acc<4>(x2);
     const int slot = k == 0 ? v : k + 1;
-    const int64_t xo = (((int64_t)r * 5 + slot) * NAS + n) * EM;
+    const int64_t xo = ((r * 5 + slot) * NAS + n) * EM;
     if constexpr (!BWD) {
-        floatx4 X[2];
-        bias_init<2>(X, P + L.b2, 0, lane);
-        mm_reg<2, 4>(X, P + L.w2, EMB, 0, x2, lane);
-        if (rdead) zero_acc<2>(X);
         if (v < V) {
 #pragma unroll
             for (int c = 0; c < 2; ++c) st4(a.X + xo + c * 16 + 4 * g, X[c]);
         }
     } else {
         const MixHyperWs w = a.hw[k];
-        const bool valid = v < V && n < NA, active = valid && !rdead;
-        const int64_t ra = ((int64_t)r * V + v) * NA + n;
+        const bool valid = v < V && n < NA, active = valid && !((dead >> n) & 1u);  // dead: masked agents, slots past NA
+        const int64_t ra = (r * V + v) * NA + n;
         for (int i = lane; i < a.NE * EMB; i += 64) {
             const int j = i / EMB, c = i % EMB;
-            w.x1[((int64_t)r * a.NE + j) * EMB + c] = s_x1[j * LDX + c];
+            w.x1[(r * a.NE + j) * EMB + c] = s_x1[j * LDX + c];
         }
         floatx4 dx3[2], dout[4], dO[4];
 #pragma unroll
@@ -572,15 +493,15 @@ __global__ void __launch_bounds__(64) mixer_hyper_kernel(RHyper L, MixGradArgs a
             st_row(s_do, LDX, c, dO[c], lane);
         }
         wave_sync();
-        attn_bwd<false>(s_qkv, s_P[0], NA, s_do, LDX, s_ds, s_dqkv, lane);
+        attn_bwd<false>(s_qkv, s_P, NA, s_do, LDX, s_ds, s_dqkv, lane);
         if (V == 2) {
             wave_sync();
-            attn_bwd<true>(s_qkv, s_P[1], NA, s_do + NAS * LDX, LDX, s_ds, s_dqkv, lane);
+            attn_bwd<true>(s_qkv, s_P + NH * 16 * NE, NA, s_do + NAS * LDX, LDX, s_ds, s_dqkv, lane);
         }
         wave_sync();
         for (int i = lane; i < a.NE * 3 * EMB; i += 64) {
             const int j = i / (3 * EMB), f = i % (3 * EMB);
-            w.dqkv[((int64_t)r * a.NE + j) * 3 * EMB + f] = s_dqkv[j * LDQ + f];
+            w.dqkv[(r * a.NE + j) * 3 * EMB + f] = s_dqkv[j * LDQ + f];
         }
         floatx4 acc[4];
         zero_acc<4>(acc);
@@ -592,14 +513,13 @@ __global__ void __launch_bounds__(64) mixer_hyper_kernel(RHyper L, MixGradArgs a
                 floatx4 d;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) d[q] = xv[q] > 0.f ? acc[c][q] : 0.f;
-                st4(w.dx1 + ((int64_t)r * a.NE + col) * EMB + c * 16 + 4 * g, d);
+                st4(w.dx1 + (r * a.NE + col) * EMB + c * 16 + 4 * g, d);
             }
         }
     }
 }
 
-// (B) the mixing and its backward, lane e of a 32-lane half per row (two rows per wave):
-//   pre_e = b1_e + sum_q qs_q mw(x_q)_e,  q_tot = sum_e elu(pre_e) mw(wfp)_e + v;  b1, wfp = agent means, v = mean of V
+// (B) the mixing (mix_row) and its backward, lane e of a 32-lane half per row (two rows per wave):
 //   d v -> g / (NA EM) per element;  d wfp = mw_bwd(g elu(pre));  d pre = g wf elu'(pre);  d b1 rows = d pre / NA
 //   d qs_q = sum_e mw(x_q)_e d pre_e;  d x_q = mw_bwd(qs_q d pre)
 // The entity-masked agent rows of X are zeros behind a masked_fill: pass (C) drops their dX.
@@ -613,22 +533,9 @@ __global__ void __launch_bounds__(64) mixer_mix_backward_kernel(MixGradArgs a) {
     float* dX = a.dX + (int64_t)r * 5 * NAS * EM;
     const float* qs = a.qs + (int64_t)r * nrow;
     const float gr = a.g[r];
-    float b1 = 0.f, wfp = 0.f;
-    for (int q = 0; q < NA; ++q) {
-        b1 += X[(3 * NAS + q) * EM + e];
-        wfp += X[(2 * NAS + q) * EM + e];
-    }
-    b1 /= (float)NA;
-    wfp /= (float)NA;
-    const float wf = mw(wfp, a.softmax);
-    float pre = b1;
-    for (int q = 0; q < nrow; ++q) {
-        const float xw = q < NA ? X[q * EM + e] : X[(NAS + q - NA) * EM + e];
-        pre += qs[q] * mw(xw, a.softmax);
-    }
-    const float hid = elu_f(pre);
-    const float dpre = gr * wf * elu_d(pre);
-    const float dwfp = mw_bwd(gr * hid, wf, wfp, a.softmax);
+    const MixRow m = mix_row(X, qs, NA, nrow, a.softmax, e);
+    const float dpre = gr * m.wf * elu_d(m.pre);
+    const float dwfp = mw_bwd(gr * m.hid, m.wf, m.wfp, a.softmax);
     const float dv = gr / ((float)NA * (float)EM);
     for (int q = 0; q < NA; ++q) {
         if (live) {
@@ -650,39 +557,29 @@ __global__ void __launch_bounds__(64) mixer_mix_backward_kernel(MixGradArgs a) {
     }
 }
 
-struct MixGradPlan {
-    int64_t X, dX, slab, nrm, total, n_params;
+struct MixGradPlan : GradPlan {
+    int64_t X, dX;
     int64_t hw[4][7];
-    int n_tasks;
-    int64_t n_red;
-    GJobs J;
 };
 
 MixGradPlan mixer_grad_plan(const MlgRefilDims& d, int R, bool imagine, float* ws, const float* entities,
                             float* dparams) {
     MixGradPlan p{};
     const int NA = d.n_agents, NEa = d.n_entities;
-    const RHyper L = make_rhyper(d.entity_shape + (d.entity_last_action ? d.n_actions : 0));
+    const RHyper L = make_rhyper(refil_d0(&d));
     const int64_t re = (int64_t)R * NEa;
-    int64_t o = 0;
-    auto take = [&](int64_t n) {
-        const int64_t at = o;
-        o += mlg_align4(n);
-        return at;
-    };
-    p.X = take((int64_t)R * 5 * NAS * EM);
-    p.dX = take((int64_t)R * 5 * NAS * EM);
+    p.X = p.take((int64_t)R * 5 * NAS * EM);
+    p.dX = p.take((int64_t)R * 5 * NAS * EM);
     for (int k = 0; k < 4; ++k) {
         const int64_t ra = (int64_t)R * NA * ((k == 0 && imagine) ? 2 : 1);
-        p.hw[k][0] = take(re * EMB);
-        p.hw[k][1] = take(re * EMB);
-        p.hw[k][2] = take(re * 3 * EMB);
-        p.hw[k][3] = take(ra * EMB);
-        p.hw[k][4] = take(ra * EMB);
-        p.hw[k][5] = take(ra * EMB);
-        p.hw[k][6] = take(ra * EM);
+        p.hw[k][0] = p.take(re * EMB);
+        p.hw[k][1] = p.take(re * EMB);
+        p.hw[k][2] = p.take(re * 3 * EMB);
+        p.hw[k][3] = p.take(ra * EMB);
+        p.hw[k][4] = p.take(ra * EMB);
+        p.hw[k][5] = p.take(ra * EMB);
+        p.hw[k][6] = p.take(ra * EM);
     }
-    p.slab = o;
     p.n_params = 4 * L.c_total;
     auto at = [&](int64_t off) { return ws ? ws + off : (float*)nullptr; };
     GJobs& J = p.J;
@@ -697,10 +594,7 @@ MixGradPlan mixer_grad_plan(const MlgRefilDims& d, int R, bool imagine, float* w
         J.j[J.n++] = mlg::bjob(at(h[4]), EMB, at(h[3]), EMB, gp(L.c_wout), gp(L.c_bout), EMB, EMB, ra);
         J.j[J.n++] = mlg::bjob(at(h[6]), EM, at(h[5]), EMB, gp(L.c_w2), gp(L.c_b2), EM, EMB, ra);
     }
-    int64_t slab_part;
-    const int64_t slab = mlg::layout_bjobs(J, &p.n_tasks, &p.n_red, &slab_part);
-    p.nrm = p.slab + slab_part;
-    p.total = p.slab + slab;
+    p.finish();
     return p;
 }
 
@@ -726,45 +620,25 @@ extern "C" int mlg_refil_mixer_backward(const MlgRefilDims* d, const float* pack
     MLG_REQUIRE((w_mask == nullptr) == (i_mask == nullptr), "refil_mixer_backward: imagine needs both w_mask and i_mask");
     hipStream_t s = (hipStream_t)stream;
     const bool imagine = w_mask != nullptr;
-    MixGradPlan pl = mixer_grad_plan(*d, R, imagine, workspace, entities, dparams);
-    if (R == 0) {
-        if (hipMemsetAsync(dparams, 0, (size_t)pl.n_params * sizeof(float), s) != hipSuccess)
-            return mlg::fail("refil_mixer_backward: zeroing dparams failed");
+    const MixGradPlan pl = mixer_grad_plan(*d, R, imagine, workspace, entities, dparams);
+    return run_backward("refil_mixer_backward", pl, R, dparams, workspace, s, [&]() -> int {
+        MLG_REQUIRE(agent_qs && entities && entity_mask && g_qtot && d_agent_qs,
+                    "refil_mixer_backward: null pointer (agent_qs, entities, entity_mask, g_qtot, d_agent_qs)");
+        MLG_REQUIRE(aligned16(packed), "refil_mixer_backward: packed must be 16-byte aligned");
+        const RHyper L = make_rhyper(refil_d0(d));
+        MixGradArgs a{d->n_agents, d->n_entities, L.D0, R, softmax_mixing_weights, imagine, packed, agent_qs, entities,
+                      entity_mask, w_mask, i_mask, g_qtot, workspace + pl.X, workspace + pl.dX, d_agent_qs, {}};
+        for (int k = 0; k < 4; ++k) {
+            const int64_t* h = pl.hw[k];
+            a.hw[k] = MixHyperWs{workspace + h[0], workspace + h[1], workspace + h[2], workspace + h[3],
+                                 workspace + h[4], workspace + h[5], workspace + h[6]};
+        }
+        const dim3 grid((unsigned)R, 4);
+        hipLaunchKernelGGL(mixer_hyper_kernel<false>, grid, dim3(64), 0, s, L, a);
+        hipLaunchKernelGGL(mixer_mix_backward_kernel, dim3((unsigned)((R + 1) / 2)), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(mixer_hyper_kernel<true>, grid, dim3(64), 0, s, L, a);
         return 0;
-    }
-    MLG_REQUIRE(agent_qs && entities && entity_mask && g_qtot && d_agent_qs && workspace,
-                "refil_mixer_backward: null pointer (agent_qs, entities, entity_mask, g_qtot, d_agent_qs, workspace)");
-    MLG_REQUIRE(aligned16(workspace) && aligned16(packed), "refil_mixer_backward: workspace and packed must be 16-byte aligned");
-    const int D0 = d->entity_shape + (d->entity_last_action ? d->n_actions : 0);
-    const RHyper L = make_rhyper(D0);
-    MixGradArgs a{};
-    a.NA = d->n_agents;
-    a.NE = d->n_entities;
-    a.D0 = D0;
-    a.R = R;
-    a.softmax = softmax_mixing_weights;
-    a.imagine = imagine;
-    a.packed = packed;
-    a.qs = agent_qs;
-    a.ent = entities;
-    a.em = entity_mask;
-    a.wm = w_mask;
-    a.im = i_mask;
-    a.g = g_qtot;
-    a.X = workspace + pl.X;
-    a.dX = workspace + pl.dX;
-    a.dqs = d_agent_qs;
-    for (int k = 0; k < 4; ++k) {
-        const int64_t* h = pl.hw[k];
-        a.hw[k] = MixHyperWs{workspace + h[0], workspace + h[1], workspace + h[2], workspace + h[3],
-                             workspace + h[4], workspace + h[5], workspace + h[6]};
-    }
-    const dim3 grid((unsigned)R, 4);
-    hipLaunchKernelGGL(mixer_hyper_kernel<false>, grid, dim3(64), 0, s, L, a);
-    hipLaunchKernelGGL(mixer_mix_backward_kernel, dim3((unsigned)((R + 1) / 2)), dim3(64), 0, s, a);
-    hipLaunchKernelGGL(mixer_hyper_kernel<true>, grid, dim3(64), 0, s, L, a);
-    if (mlg::check_launch("refil_mixer_backward kernels")) return 1;
-    return run_jobs(pl.J, pl.n_tasks, pl.n_red, workspace + pl.slab, workspace + pl.nrm, s, "refil_mixer_backward wgrad");
+    });
 }
 
 extern "C" int64_t mlg_refil_attention_backward_workspace_floats(int32_t bs, int32_t ne, int32_t nq, int32_t n_heads) {
@@ -780,22 +654,17 @@ extern "C" int mlg_refil_attention_backward(const float* w_in, const float* w_ou
     MLG_REQUIRE(w_in && w_out && b_out, "refil_attention_backward: null parameter pointer (w_in, w_out, b_out)");
     MLG_REQUIRE(dparams, "refil_attention_backward: null dparams");
     hipStream_t s = (hipStream_t)stream;
-    AttnGradPlan pl = attn_grad_plan(bs, ne, nq, workspace, x, dparams);
-    if (bs == 0) {
-        if (hipMemsetAsync(dparams, 0, (size_t)pl.n_params * sizeof(float), s) != hipSuccess)
-            return mlg::fail("refil_attention_backward: zeroing dparams failed");
+    const AttnGradPlan pl = attn_grad_plan(bs, ne, nq, workspace, x, dparams);
+    return run_backward("refil_attention_backward", pl, bs, dparams, workspace, s, [&]() -> int {
+        MLG_REQUIRE(x && pre_mask && post_mask && gy && dx,
+                    "refil_attention_backward: null pointer (x, pre_mask, post_mask, gy, dx)");
+        MLG_REQUIRE(aligned16(w_in) && aligned16(w_out) && aligned16(dx),
+                    "refil_attention_backward: w_in, w_out and dx must be 16-byte aligned");
+        AttnGradWs w{workspace + pl.o, workspace + pl.dout, workspace + pl.dqkv};
+        hipLaunchKernelGGL(attention_backward_kernel, dim3((unsigned)bs), dim3(64), 0, s, w_in, w_out, x, pre_mask,
+                           post_mask, ne, nq, gy, w, dx);
         return 0;
-    }
-    MLG_REQUIRE(x && pre_mask && post_mask && gy && dx && workspace,
-                "refil_attention_backward: null pointer (x, pre_mask, post_mask, gy, dx, workspace)");
-    MLG_REQUIRE(aligned16(workspace) && aligned16(w_in) && aligned16(w_out) && aligned16(dx),
-                "refil_attention_backward: workspace, w_in, w_out and dx must be 16-byte aligned");
-    AttnGradWs w{workspace + pl.o, workspace + pl.dout, workspace + pl.dqkv};
-    hipLaunchKernelGGL(attention_backward_kernel, dim3((unsigned)bs), dim3(64), 0, s, w_in, w_out, x, pre_mask, post_mask,
-                       ne, nq, gy, w, dx);
-    if (mlg::check_launch("attention_backward_kernel")) return 1;
-    return run_jobs(pl.J, pl.n_tasks, pl.n_red, workspace + pl.slab, workspace + pl.nrm, s,
-                    "refil_attention_backward wgrad");
+    });
 }
 
 extern "C" int64_t mlg_refil_agent_backward_workspace_floats(const MlgRefilDims* d, int32_t R) {
@@ -816,22 +685,18 @@ extern "C" int mlg_refil_agent_backward(const MlgRefilDims* d, const float* pack
     MLG_REQUIRE(dparams, "refil_agent_backward: null dparams");
     MLG_REQUIRE(R >= 0, "refil_agent_backward: R=%d must be >= 0", R);
     hipStream_t s = (hipStream_t)stream;
-    RAgentGradPlan pl = ragent_grad_plan(*d, R, workspace, entities, h_in, dparams);
-    if (R == 0) {
-        if (hipMemsetAsync(dparams, 0, (size_t)pl.n_params * sizeof(float), s) != hipSuccess)
-            return mlg::fail("refil_agent_backward: zeroing dparams failed");
+    const RAgentGradPlan pl = ragent_grad_plan(*d, R, workspace, entities, h_in, dparams);
+    return run_backward("refil_agent_backward", pl, R, dparams, workspace, s, [&]() -> int {
+        MLG_REQUIRE(entities && obs_mask && entity_mask && h_in,
+                    "refil_agent_backward: null pointer (entities, obs_mask, entity_mask, h_in)");
+        MLG_REQUIRE(aligned16(packed) && aligned16(h_in) && aligned16(gh_out) && aligned16(d_h_in),
+                    "refil_agent_backward: packed, h_in, gh_out and d_h_in must be 16-byte aligned");
+        AgentGradWs w{workspace + pl.x1,  workspace + pl.dx1, workspace + pl.dqkv, workspace + pl.o,
+                      workspace + pl.dout, workspace + pl.x2,  workspace + pl.dx3,  workspace + pl.x3,
+                      workspace + pl.dgi, workspace + pl.dgh, workspace + pl.hp,   workspace + pl.gq};
+        hipLaunchKernelGGL(refil_agent_backward_kernel, dim3((unsigned)R), dim3(64), 0, s,
+                           make_ragent(refil_d0(d), d->n_actions), packed, d->n_agents, d->n_entities, entities, obs_mask,
+                           entity_mask, h_in, gq, gh_out, w, d_h_in);
         return 0;
-    }
-    MLG_REQUIRE(entities && obs_mask && entity_mask && h_in && workspace,
-                "refil_agent_backward: null pointer (entities, obs_mask, entity_mask, h_in, workspace)");
-    MLG_REQUIRE(aligned16(workspace) && aligned16(packed) && aligned16(h_in) && aligned16(gh_out) && aligned16(d_h_in),
-                "refil_agent_backward: workspace, packed, h_in, gh_out and d_h_in must be 16-byte aligned");
-    const RAgent L = make_ragent(d->entity_shape + (d->entity_last_action ? d->n_actions : 0), d->n_actions);
-    AgentGradWs w{workspace + pl.x1,  workspace + pl.dx1, workspace + pl.dqkv, workspace + pl.o,
-                  workspace + pl.dout, workspace + pl.x2,  workspace + pl.dx3,  workspace + pl.x3,
-                  workspace + pl.dgi, workspace + pl.dgh, workspace + pl.hp,   workspace + pl.gq};
-    hipLaunchKernelGGL(refil_agent_backward_kernel, dim3((unsigned)R), dim3(64), 0, s, L, packed, d->n_agents,
-                       d->n_entities, entities, obs_mask, entity_mask, h_in, gq, gh_out, w, d_h_in);
-    if (mlg::check_launch("refil_agent_backward_kernel")) return 1;
-    return run_jobs(pl.J, pl.n_tasks, pl.n_red, workspace + pl.slab, workspace + pl.nrm, s, "refil_agent_backward wgrad");
+    });
 }

@@ -508,19 +508,7 @@ __global__ void __launch_bounds__(256) prologue_kernel(Prologue P) {
     ein_body(P.c, bt, P.ein, blk);
 }
 
-// ---- masks -----------------------------------------------------------------------------------------------
-// a mask row of n <= NE bytes as bits (bit j = byte j != 0), bits >= n set: the NE loads are unrolled and issued
-// back to back (a loop over the runtime n waited for each byte in turn; these sit on every per-item kernel's
-// critical path)
-__device__ __forceinline__ uint32_t mask_row_bits(const uint8_t* row, int n) {
-    uint32_t m = ~((1u << n) - 1u) & 0xFFFFu;
-    uint8_t v[NE];
-#pragma unroll
-    for (int j = 0; j < NE; ++j) v[j] = row[j < n ? j : 0];
-#pragma unroll
-    for (int j = 0; j < NE; ++j) m |= (uint32_t)(j < n && v[j] != 0) << j;
-    return m;
-}
+// ---- masks (mask_row_bits, dead_rows: refil_device.h) ----------------------------------------------------
 // entity mask bits of (b, t); bits >= NE set (absent)
 __device__ __forceinline__ uint32_t em_bits(const RCfg& c, const MlgEntityBatch& bt, int b, int t) {
     return mask_row_bits(bt.entity_mask + (eslot(bt, b) * bt.T1 + t) * c.NE, c.NE);
@@ -546,7 +534,7 @@ __device__ __forceinline__ uint32_t interact_row(uint32_t gA, uint32_t gB, int q
 __device__ __forceinline__ uint32_t active_row(uint32_t em0, int q) { return ((em0 >> q) & 1u) ? 0xFFFFu : em0; }
 // dead agent rows of an item (bits < 8): entity-masked agents and padding slots >= NA
 __device__ __forceinline__ uint32_t dead_bits(const RCfg& c, uint32_t em) {
-    return ((em & ((1u << c.NA) - 1u)) | (~((1u << c.NA) - 1u))) & 0xFFu;
+    return dead_rows(em, c.NA, NAS);
 }
 
 // ---- agent entity block forward (online: 3 copies; target: plain) ---------------------------------------

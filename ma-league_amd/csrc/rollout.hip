@@ -2170,20 +2170,6 @@ int check_state(const MlgEnvState* st) {
 
 constexpr int LDS_LIMIT_BYTES = 160 * 1024;
 
-template <int H, int TPW, bool WLDS>
-int launch_rollout_t(int grid, int threads, hipStream_t s, const MlgEnvSpec& spec, const MlgEnvState& st,
-                     const AgentLayout& L, const Sides& sd, const MlgRunInfo& info, int tm, const RolloutLds& lay) {
-    const size_t bytes = (size_t)lay.total * 4;
-    auto kern = rollout_kernel<H, TPW, WLDS>;
-    if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)bytes);
-        if (e != hipSuccess) return mlg::fail("rollout: LDS attribute (%zu B): %s", bytes, hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), bytes, s, spec, st, L, sd, info, tm, lay);
-    return 0;
-}
-
 // v7 with a compile-time shape when the layout matches one (StaticShape), else the generic v7.
 template <int SN, int SU>
 bool static_shape_matches(const AgentLayout& L, const RolloutLds2& lay) {

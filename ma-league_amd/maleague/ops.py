@@ -130,7 +130,7 @@ def refil_attention(w_in: Tensor, w_out: Tensor, b_out: Tensor, x: Tensor, pre_m
     y = x.new_empty(bs, nq, w_out.shape[0])
     _native.call("mlg_refil_attention", _native.ptr(w_in), _native.ptr(w_out), _native.ptr(b_out), _native.ptr(x),
                  _native.ptr(pre_mask), _native.ptr(post_mask), int(bs), int(ne), int(nq), int(n_heads),
-                 _native.ptr(y), None, None, None, None, None, _stream(x))
+                 _native.ptr(y), _stream(x))
     return y
 
 

@@ -138,8 +138,9 @@ def test_rollout_fixed_team_sizes(device, rollout_variant):
 
 @pytest.mark.parametrize("tag,nq", [("na", 8), ("ne", 16)])
 def test_attention_layer_forward_backward_golden(device, golden, tag, nq):
-    """EntityAttentionLayer fwd + bwd (mlg_refil_attention) vs the reference's vectors (attention.py:24-79)."""
-    from maleague import _native
+    """EntityAttentionLayer fwd (mlg_refil_attention) + bwd (mlg_refil_attention_backward, dparams = in_trans.weight,
+    out_trans.weight, out_trans.bias, flat) vs the reference's vectors (attention.py:24-79)."""
+    from maleague import _native, ops
     d = golden("refil_layers.npz")
     t = lambda k, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(d[k])).to(device=device, dtype=dt)  # noqa
     w_in, w_out, b_out = t("attn.p.in_trans.weight"), t("attn.p.out_trans.weight"), t("attn.p.out_trans.bias")
@@ -149,11 +150,13 @@ def test_attention_layer_forward_backward_golden(device, golden, tag, nq):
     post = t("attn.em", torch.uint8)[:, :nq].contiguous()
     gy = t(f"attn.{tag}.g")
     y = torch.empty(bs, nq, 64, device=device)
-    dx = torch.empty_like(x)
-    dwi, dwo, dbo = torch.zeros_like(w_in), torch.zeros_like(w_out), torch.zeros_like(b_out)
     P = _native.ptr
-    _native.call("mlg_refil_attention", P(w_in), P(w_out), P(b_out), P(x), P(pre), P(post), bs, ne, nq, 4, P(y), P(gy),
-                 P(dx), P(dwi), P(dwo), P(dbo), _native.stream_ptr())
+    _native.call("mlg_refil_attention", P(w_in), P(w_out), P(b_out), P(x), P(pre), P(post), bs, ne, nq, 4, P(y),
+                 _native.stream_ptr())
+    dx, dflat = ops.refil_attention_backward(w_in, w_out, b_out, x, pre, post, gy, 4)
+    assert dx.shape == x.shape
+    dwi, dwo, dbo = (g.view_as(p) for g, p in zip(dflat.split([w_in.numel(), w_out.numel(), b_out.numel()]),
+                                                  (w_in, w_out, b_out)))
     np.testing.assert_allclose(y.cpu().numpy(), d[f"attn.{tag}.y"], atol=Q_TOL, rtol=0)
     np.testing.assert_allclose(dx.cpu().numpy(), d[f"attn.{tag}.dx"], atol=Q_TOL, rtol=0)
     np.testing.assert_allclose(dwi.cpu().numpy(), d[f"attn.{tag}.d.in_trans.weight"], atol=Q_TOL, rtol=1e-4)
