@@ -1,4 +1,5 @@
-"""CPU restatement (PyTorch fp32, autograd) of the reference's REFIL path (config 5).
+"""CPU restatement (PyTorch autograd; fp32, or float64 as the yardstick of fp32) of the reference's REFIL path
+(config 5).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/ as the checker; never by the product. Pinned against
 tests/golden/refil_*.npz, generated from the reference itself by tests/golden/make_refil_golden.py.
@@ -129,20 +130,24 @@ def imagine_masks(groupA_raw, entity_mask, obs_mask):
     return lor(within, obs_mask), lor(interact, obs_mask), W_noobs, I_noobs
 
 
-def build_entity_inputs(batch, n_agents, n_actions, T=None):
-    """EntityMAC._build_inputs for t = slice(0, T) (entity_controller.py:11-30, intended t=None semantics)."""
+def build_entity_inputs(batch, n_agents, n_actions, T=None, last_action=True):
+    """EntityMAC._build_inputs for t = slice(0, T) (entity_controller.py:11-30, intended t=None semantics). Without
+    ``last_action`` (args.entity_last_action False, :16) the entities go in as they are."""
     ent = batch["entities"]
     bs, T_all = ent.shape[:2]
     T = T_all if T is None else T
     ent = ent[:, :T]
-    acs = torch.zeros(bs, T, ent.shape[2], n_actions, dtype=ent.dtype)
-    acs[:, 1:, :n_agents] = batch["actions_onehot"][:, :T - 1]
-    return torch.cat([ent, acs], dim=3), batch["obs_mask"][:, :T], batch["entity_mask"][:, :T]
+    if last_action:
+        acs = torch.zeros(bs, T, ent.shape[2], n_actions, dtype=ent.dtype)
+        acs[:, 1:, :n_agents] = batch["actions_onehot"][:, :T - 1].to(ent.dtype)
+        ent = torch.cat([ent, acs], dim=3)
+    return ent, batch["obs_mask"][:, :T], batch["entity_mask"][:, :T]
 
 
 def mac_forward(p, batch, args, groupA=None):
     """The whole-episode EntityMAC forward; with groupA, the imagined within / interact copies as well."""
-    ent, om, em = build_entity_inputs(batch, args.n_agents, args.n_actions)
+    ent, om, em = build_entity_inputs(batch, args.n_agents, args.n_actions,
+                                      last_action=getattr(args, "entity_last_action", True))
     bs = ent.shape[0]
     h0 = torch.zeros(bs, args.n_agents, args.rnn_hidden_dim, dtype=p["fc1.weight"].dtype)  # float64 unroll: cast p
     if groupA is None:
@@ -155,35 +160,50 @@ def mac_forward(p, batch, args, groupA=None):
 
 
 class REFILLearnerRef:
-    """REFILLearner.train (marl/learners/refil_learner.py:67-177) with RMSprop (learner ctor :34-35)."""
+    """REFILLearner.train (marl/learners/refil_learner.py:67-177) with RMSprop (learner ctor :34-35). Every float
+    tensor (parameters, RMSprop state, the batch's float fields, masks) is computed in ``dtype``: torch.float64 is the
+    yardstick of the fp32 run. After train(), ``last_grads`` holds each parameter's .grad before the clip, in
+    ``self.params`` order. args.entity_last_action False: no one-hot columns in the agent's or the mixer's inputs."""
 
-    def __init__(self, agent_p, mixer_p, args):
+    def __init__(self, agent_p, mixer_p, args, dtype=torch.float32):
         self.args = args
+        self.dtype = dtype
         keep = lambda k: not k.endswith("scale_factor")  # noqa: E731  (a buffer, not a parameter)
-        self.agent = {k: torch.as_tensor(v).clone().requires_grad_(True) for k, v in agent_p.items() if keep(k)}
-        self.mixer = {k: torch.as_tensor(v).clone().requires_grad_(True) for k, v in mixer_p.items() if keep(k)}
+        own = lambda v: torch.as_tensor(v).detach().to(dtype).clone().requires_grad_(True)  # noqa: E731
+        self.agent = {k: own(v) for k, v in agent_p.items() if keep(k)}
+        self.mixer = {k: own(v) for k, v in mixer_p.items() if keep(k)}
         self.t_agent = {k: v.detach().clone() for k, v in self.agent.items()}
         self.t_mixer = {k: v.detach().clone() for k, v in self.mixer.items()}
         self.params = list(self.agent.values()) + list(self.mixer.values())
         self.opt = torch.optim.RMSprop(self.params, lr=args.lr, alpha=args.optim_alpha, eps=args.optim_eps,
                                        weight_decay=getattr(args, "weight_decay", 0))
         self.last_target_update_episode = 0
+        self.last_grads = None
+
+    def cast(self, batch):
+        """The batch with its float fields in self.dtype (integer and mask fields as they are)."""
+        return {k: v.to(self.dtype) if v.is_floating_point() else v for k, v in batch.items()}
+
+    def keep_grads(self):
+        self.last_grads = [p.grad.detach().clone() for p in self.params]
 
     def mixer_ins(self, batch):
-        ent = batch["entities"]
+        ent = batch["entities"].to(self.dtype)
         bs, T, ne, _ = ent.shape
-        la = torch.zeros(bs, T, ne, self.args.n_actions)
-        la[:, 1:, :self.args.n_agents] = batch["actions_onehot"][:, :-1]
-        ent = torch.cat([ent, la], dim=3)
+        if getattr(self.args, "entity_last_action", True):  # refil_learner.py:54-59
+            la = torch.zeros(bs, T, ne, self.args.n_actions, dtype=self.dtype)
+            la[:, 1:, :self.args.n_agents] = batch["actions_onehot"][:, :-1].to(self.dtype)
+            ent = torch.cat([ent, la], dim=3)
         em = batch["entity_mask"]
         return (ent[:, :-1], em[:, :-1]), (ent[:, 1:], em[:, 1:])
 
     def train(self, batch, groupA, episode_num):
         a = self.args
+        batch = self.cast(batch)
         rewards = batch["reward"][:, :-1]
         actions = batch["actions"][:, :-1]
-        terminated = batch["terminated"][:, :-1].float()
-        mask = batch["filled"][:, :-1].float()
+        terminated = batch["terminated"][:, :-1].to(self.dtype)
+        mask = batch["filled"][:, :-1].to(self.dtype)
         mask[:, 1:] = mask[:, 1:] * (1 - terminated[:, :-1])
         avail = batch["avail_actions"]
         all_q, groups = mac_forward(self.agent, batch, a, groupA=groupA)
@@ -218,6 +238,7 @@ class REFILLearnerRef:
         loss = (1 - a.lmbda) * loss + a.lmbda * im_loss
         self.opt.zero_grad()
         loss.backward()
+        self.keep_grads()
         gn = torch.nn.utils.clip_grad_norm_(self.params, a.grad_norm_clip)
         self.opt.step()
         if (episode_num - self.last_target_update_episode) / a.target_update_interval >= 1.0:

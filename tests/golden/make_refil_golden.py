@@ -3,7 +3,8 @@
 TEST INFRASTRUCTURE ONLY; runs in the build container with the reference mounted read-only at
 /root/reference and records inputs/outputs of the reference's own modules as .npz data.
 
-Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_refil_golden.py
+Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_refil_golden.py          (the first two files)
+        PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_refil_golden.py nola     (the last two)
 
 refil_layers.npz
   attn.*      EntityAttentionLayer.forward + backward   src/marl/modules/layers/attention.py:24-79
@@ -18,6 +19,12 @@ refil_learner.npz
   EntityMAC cannot serve ``forward(batch, t=None)`` (entity_controller.py:14-20 dereferences t.start; SURVEY
   §0.7); the fixture uses the intended semantics -- t=None means the whole episode, t = slice(0, T) -- with
   the reference's own EntityMAC._build_inputs and agent networks.
+refil_learner_nola.npz, refil_learner_nola_after.npz
+  One REFILLearner.train call with entity_last_action False (entity_controller.py:16, refil_learner.py:54,
+  flex_qmix.py:23: no last-action one-hot in the agent's or the mixer's inputs) at NA 5, NE 9, ED 8, A 16; B = 3,
+  T = 6. The parameters dominate the size (124k floats per copy), so as for qlearner_qmix_9v9_h128 the fixture is
+  two files of about half the committed-file limit each: the first holds the batch, the group draw, the initial
+  parameters and the call's statistics, the ``_after`` file the agent and the mixer after the call.
 """
 import os
 import sys
@@ -270,7 +277,85 @@ def learner_fixture(rng):
     np.savez_compressed(os.path.join(OUT, "refil_learner.npz"), **out)
 
 
+def nola_fixture():
+    """learner_fixture's recipe without the last-action columns, off the refil_8 dims, one call."""
+    from marl.modules.agents import REGISTRY as agent_REGISTRY
+    agent_REGISTRY["imagine_entity_attend_rnn"] = ImagineEntityAttentionRNNAgent
+    na, ne, ed, A = 5, 9, 8, 16
+    args = refil_args(n_agents=na, n_entities=ne, n_actions=A, entity_shape=ed, entity_last_action=False)
+    rng = np.random.RandomState(11)
+    B, T = 3, 6
+    scheme = {"entities": {"vshape": ed, "group": "entities"},
+              "obs_mask": {"vshape": (ne,), "group": "entities", "dtype": th.uint8},
+              "entity_mask": {"vshape": (ne,), "dtype": th.uint8},
+              "actions": {"vshape": (1,), "group": "agents", "dtype": th.long},
+              "avail_actions": {"vshape": (A,), "group": "agents", "dtype": th.int},
+              "reward": {"vshape": (1,)}, "terminated": {"vshape": (1,), "dtype": th.uint8}}
+    groups = {"agents": na, "entities": ne}
+    pre = {"actions": ("actions_onehot", [OneHot(out_dim=A)])}
+    batch = EpisodeBatch(scheme, groups, B, T, preprocess=pre)
+    lens = [5, 3, 4]
+    ent = rng.randn(B, T, ne, ed).astype(np.float32)
+    em = np.ones((B, T, ne), np.uint8)
+    for b in range(B):
+        k = rng.randint(2, na + 1)  # active agents, as many other entities; presence is fixed per episode
+        em[b, :, :k] = 0
+        em[b, :, na:min(ne, na + k)] = 0
+    om = (rng.rand(B, T, ne, ne) < 0.3).astype(np.uint8)
+    om |= em[:, :, None, :] | em[:, :, :, None]
+    for i in range(ne):
+        om[:, :, i, i] = em[:, :, i]  # an active entity always sees itself
+    avail = (rng.rand(B, T, na, A) < 0.6).astype(np.int32)
+    avail[..., 0] = 1
+    acts = np.zeros((B, T, na, 1), np.int64)
+    for b in range(B):
+        for t in range(T):
+            for n in range(na):
+                acts[b, t, n, 0] = rng.choice(np.nonzero(avail[b, t, n])[0])
+    rew = rng.randn(B, T, 1).astype(np.float32)
+    tt = th.from_numpy
+    for b, L in enumerate(lens):
+        batch.update({"entities": tt(ent[b, :L + 1]), "obs_mask": tt(om[b, :L + 1]),
+                      "entity_mask": tt(em[b, :L + 1]), "avail_actions": tt(avail[b, :L + 1])},
+                     bs=b, ts=slice(0, L + 1))
+        batch.update({"actions": tt(acts[b, :L + 1])}, bs=b, ts=slice(0, L + 1), mark_filled=False)
+        term = np.zeros((L, 1), np.uint8)
+        term[-1] = 1 if b != 1 else 0
+        batch.update({"reward": tt(rew[b, :L]), "terminated": tt(term)}, bs=b, ts=slice(0, L), mark_filled=False)
+    th.manual_seed(15)
+    mac = _IntendedEntityMAC(batch.scheme, groups, args)
+    learner = REFILLearner(mac, batch.scheme, _Log(), args)
+    assert mac.agent.fc1.in_features == ed and learner.mixer.hyper_w_1.fc1.in_features == ed
+    out = {f"b.{k}": v.numpy().copy() for k, v in batch.data.transition_data.items()}
+    out["dims"] = np.array([na, ne, ed, A], np.int64)
+    out.update(sd("p0.agent.", mac.agent))
+    out.update(sd("p0.mixer.", learner.mixer))
+    drawn = []
+    orig = th.bernoulli
+
+    def rec(p, *a, **k):
+        r = orig(p, *a, **k)
+        drawn.append(r.clone())
+        return r
+
+    th.bernoulli = rec
+    th.manual_seed(100)
+    learner.train(batch, t_env=1000, episode_num=0)
+    th.bernoulli = orig
+    out["c0.groupA"] = drawn[-1].numpy().astype(np.uint8)
+    for k, v in learner.logger.stats.items():
+        out[f"c0.stat.{k}"] = np.array(v)
+    after = {}
+    after.update(sd("c0.agent.", mac.agent))
+    after.update(sd("c0.mixer.", learner.mixer))
+    np.savez_compressed(os.path.join(OUT, "refil_learner_nola.npz"), **out)
+    np.savez_compressed(os.path.join(OUT, "refil_learner_nola_after.npz"), **after)
+    print("refil_learner_nola fixtures written to", OUT)
+
+
 def main():
+    if sys.argv[1:] == ["nola"]:
+        return nola_fixture()
     rng = np.random.RandomState(7)
     out = {}
     attn_fixture(out, rng)

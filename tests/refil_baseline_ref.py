@@ -15,12 +15,13 @@ import refil_ref as RR
 
 class REFILBaselineRef(RR.REFILLearnerRef):
     """The non-imagine branch: one online MAC unroll, no groups, loss = the masked TD loss (no lambda); RMSprop
-    and the target update as REFILLearnerRef. args.mixer in {"flex_qmix", "vdn"}; vdn: mixer_p empty."""
+    and the target update as REFILLearnerRef, with its ``dtype``, ``last_grads`` and entity_last_action handling.
+    args.mixer in {"flex_qmix", "vdn"}; vdn: mixer_p empty."""
 
-    def __init__(self, agent_p, mixer_p, args):
+    def __init__(self, agent_p, mixer_p, args, dtype=torch.float32):
         if args.mixer not in ("flex_qmix", "vdn"):
             raise ValueError(f"mixer {args.mixer!r}")
-        super().__init__(agent_p, {} if args.mixer == "vdn" else mixer_p, args)
+        super().__init__(agent_p, {} if args.mixer == "vdn" else mixer_p, args, dtype=dtype)
 
     def mix(self, p, qs, ins):
         if self.args.mixer == "vdn":
@@ -29,10 +30,11 @@ class REFILBaselineRef(RR.REFILLearnerRef):
 
     def train(self, batch, episode_num):
         a = self.args
+        batch = self.cast(batch)
         rewards = batch["reward"][:, :-1]
         actions = batch["actions"][:, :-1]
-        terminated = batch["terminated"][:, :-1].float()
-        mask = batch["filled"][:, :-1].float()
+        terminated = batch["terminated"][:, :-1].to(self.dtype)
+        mask = batch["filled"][:, :-1].to(self.dtype)
         mask[:, 1:] = mask[:, 1:] * (1 - terminated[:, :-1])
         avail = batch["avail_actions"]
         mac_out, _ = RR.mac_forward(self.agent, batch, a, groupA=None)
@@ -59,6 +61,7 @@ class REFILBaselineRef(RR.REFILLearnerRef):
         loss = (mtd ** 2).sum() / mask.sum()
         self.opt.zero_grad()
         loss.backward()
+        self.keep_grads()
         gn = torch.nn.utils.clip_grad_norm_(self.params, a.grad_norm_clip)
         self.opt.step()
         if (episode_num - self.last_target_update_episode) / a.target_update_interval >= 1.0:

@@ -15,7 +15,8 @@ import torch
 
 import refil_baseline_ref as BR
 from helpers import batch_mask_sum, refil_args
-from test_gpu_refil_learner import _Log, _batch_from, _learner, _pre, _synthetic_entity_batch
+from refil_learner_shapes import synthetic_entity_batch as _synthetic_entity_batch
+from test_gpu_refil_learner import _Log, _batch_from, _learner, _pre
 
 pytestmark = pytest.mark.gpu
 

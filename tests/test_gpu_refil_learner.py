@@ -12,6 +12,7 @@ import torch
 
 import refil_ref as RR
 from helpers import batch_mask_sum, entity_scheme_for, refil_args
+from refil_learner_shapes import synthetic_entity_batch as _synthetic_entity_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -258,52 +259,6 @@ def test_refil_learner_sampled_view_matches_copy(device):
             assert s1[k] == s2[k], (call, k, s1[k], s2[k])
         assert torch.equal(L1._flat.flat, L2._flat.flat), call
     assert view._rows is None  # the slot map never went to the device
-
-
-def _synthetic_entity_batch(B, T1, NA, NE, ED, A, lens, seed):
-    """A random entity-scheme batch of any shape (the env variant only produces NA = 8): episode b holds lens[b]
-    transitions (filled t <= lens[b], terminated at lens[b] - 1 for even b), a random number of active entities
-    (the rest padded: entity_mask 1, zero features), random observability, availability (>= 1 per agent row) and
-    actions among the available ones. Keys as EpisodeBatch.transition_data."""
-    rng = np.random.RandomState(seed)
-    ent = (0.5 * rng.randn(B, T1, NE, ED)).astype(np.float32)
-    emask = np.zeros((B, T1, NE), np.uint8)
-    omask = (rng.rand(B, T1, NE, NE) < 0.3).astype(np.uint8)
-    avail = (rng.rand(B, T1, NA, A) < 0.5).astype(np.int32)
-    avail[..., 0] = np.maximum(avail[..., 0], (avail.sum(-1) == 0).astype(np.int32))
-    acts = np.zeros((B, T1, NA, 1), np.int64)
-    filled = np.zeros((B, T1, 1), np.int64)
-    term = np.zeros((B, T1, 1), np.uint8)
-    rew = rng.randn(B, T1, 1).astype(np.float32)
-    for b in range(B):
-        k = rng.randint(max(1, NA - 3), NA + 1)  # active agents
-        kn = rng.randint(k, NE + 1)               # active entities
-        emask[b, :, kn:] = 1
-        emask[b, :, k:NA] = 1
-        L = int(lens[b])
-        filled[b, :L + 1] = 1
-        if b % 2 == 0:
-            term[b, L - 1] = 1
-        for t in range(T1):
-            dead = rng.rand(NE) < 0.1
-            emask[b, t, dead] = 1
-            for n in range(NA):
-                ok = np.nonzero(avail[b, t, n])[0]
-                acts[b, t, n, 0] = ok[rng.randint(len(ok))]
-        emask[b, L + 1:] = 0
-    ent[emask.astype(bool)] = 0.0
-    omask = np.maximum(omask, emask[:, :, None, :])
-    omask = np.maximum(omask, emask[:, :, :, None])
-    for x in (ent, rew, avail, acts):
-        for b in range(B):
-            x[b, int(lens[b]) + 1:] = 0
-    omask[filled[..., 0] == 0] = 0
-    emask[filled[..., 0] == 0] = 0
-    onehot = np.zeros((B, T1, NA, A), np.float32)
-    np.put_along_axis(onehot, acts, 1.0, axis=-1)
-    onehot[filled[..., 0] == 0] = 0
-    return {"entities": ent, "obs_mask": omask, "entity_mask": emask, "actions": acts, "avail_actions": avail,
-            "reward": rew, "terminated": term, "actions_onehot": onehot, "filled": filled}
 
 
 @pytest.mark.parametrize("NA,NE", [(5, 12), (3, 7)])
