@@ -11,73 +11,19 @@
 // same tile layout (side s owns tiles [s tps, (s + 1) tps), row r = env r / nh, agent s nh + r % nh), same MFMA cell
 // (agent_cell_hidden / agent_q_tile / argmax_*) in the same order, same env step. Env (pair k, episode e) runs as env
 // index e with episode counter episode0, so the results are bit-identical to one mlg_rollout_selfplay per pair.
+//
+// RE, SpecShared, load_spec_tables and ro_take come from rollout_env_device.h, check_spec, LDS_LIMIT_BYTES and allow_lds
+// from rollout_host.h (shared with rollout.hip). cp_observe / cp_env_step are this file's own: the env step without an
+// EpisodeBatch.
 #include <cstdlib>
 
 #include "agent_device.h"
-#include "mlg_host.h"
+#include "rollout_env_device.h"
+#include "rollout_host.h"
 
 int check_agent_dims(const MlgAgentDims* d);  // agent.hip
 
 namespace {
-
-// RE, SpecShared, load_spec_tables and check_spec restate rollout.hip's (file-local there). They are repeated here,
-// not moved to a shared header, because rollout.hip is pinned: the committed one-env step stamp behind the bench's
-// latency floor (profiles/counters.json, tests/test_bench_counters.py) is tied to that file's last commit.
-constexpr int RE = 16;  // envs per workgroup
-constexpr int LDS_LIMIT_BYTES = 160 * 1024;
-
-struct SpecShared {
-    int team[MLG_MAXU], role[MLG_MAXU], melee[MLG_MAXU], agent[MLG_MAXU];
-    int aunit[MLG_MAXU];  // unit of agent a
-    int team_first[2], team_size[2];
-};
-
-// `spec` lives in device memory here (the pair's entry of the spec array), not in a by-value kernel argument.
-__device__ void load_spec_tables(const MlgEnvSpec& spec, SpecShared& s) {
-    const int tid = threadIdx.x;
-    for (int u = tid; u < MLG_MAXU; u += blockDim.x) {
-        const bool in = u < spec.U;
-        s.team[u] = in ? spec.team[u] : 0;
-        s.role[u] = in ? spec.role[u] : 0;
-        s.melee[u] = in ? spec.melee[u] : 0;
-        s.agent[u] = 0;
-    }
-    __syncthreads();
-    for (int a = tid; a < spec.n_agents; a += blockDim.x) {
-        s.agent[spec.agent_unit[a]] = a + 1;
-        s.aunit[a] = spec.agent_unit[a];
-    }
-    if (tid == 0) {
-        for (int tm = 0; tm < 2; ++tm) {
-            s.team_first[tm] = -1;
-            s.team_size[tm] = 0;
-        }
-        for (int u = 0; u < spec.U; ++u) {
-            const int tm = spec.team[u];
-            if (s.team_first[tm] < 0) s.team_first[tm] = u;
-            s.team_size[tm]++;
-        }
-    }
-    __syncthreads();
-}
-
-int check_spec(const MlgEnvSpec* s) {
-    MLG_REQUIRE(s != nullptr, "null spec");
-    MLG_REQUIRE(s->U >= 2 && s->U <= MLG_MAXU, "spec.U=%d out of range [2, %d]", s->U, MLG_MAXU);
-    MLG_REQUIRE(s->n_agents >= 1 && s->n_agents <= s->U, "spec.n_agents=%d invalid", s->n_agents);
-    MLG_REQUIRE(s->n_actions == MLG_ACT_BASE + s->U, "spec.n_actions must be 5+U");
-    MLG_REQUIRE(s->grid >= 2 && s->grid <= 4096, "spec.grid=%d invalid", s->grid);
-    MLG_REQUIRE(s->episode_limit >= 1 && s->episode_limit < 65535, "spec.episode_limit invalid");
-    MLG_REQUIRE(s->policy_team == 0 || s->policy_team == 1, "spec.policy_team invalid");
-    for (int u = 0; u < s->U; ++u) {
-        MLG_REQUIRE(s->team[u] == 0 || s->team[u] == 1, "unit %d team invalid", u);
-        MLG_REQUIRE(s->role[u] >= 0 && s->role[u] <= 2, "unit %d role invalid", u);
-        MLG_REQUIRE(s->melee[u] == 0 || s->melee[u] == 1, "unit %d attack type invalid", u);
-    }
-    for (int a = 0; a < s->n_agents; ++a)
-        MLG_REQUIRE(s->agent_unit[a] >= 0 && s->agent_unit[a] < s->U, "agent %d unit invalid", a);
-    return 0;
-}
 
 // What every spec of a launch agrees on (host-checked), as one kernel argument.
 struct CpShape {
@@ -92,37 +38,31 @@ struct CpLds {
     int32_t ldo, obs_words, avail_words;
 };
 
-__host__ __device__ constexpr int64_t cp_take(int64_t& o, int64_t n) {
-    const int64_t v = o;
-    o += mlg_align4(n);
-    return v;
-}
-
 __host__ __device__ inline CpLds make_cp_lds(int U, int N, int A, bool rows_in_lds) {
     CpLds r{};
     int64_t o = 0;
     const int64_t eu = (int64_t)RE * U, en = (int64_t)RE * N;
-    r.spec = cp_take(o, (int64_t)(sizeof(SpecShared) / 4));
-    r.x = cp_take(o, eu);
-    r.y = cp_take(o, eu);
-    r.hp = cp_take(o, eu);
-    r.nhp = cp_take(o, eu);
-    r.act = cp_take(o, eu);
-    r.pact = cp_take(o, en);
-    r.prev = cp_take(o, en);
-    r.status = cp_take(o, RE);
-    r.stepped = cp_take(o, RE);
-    r.len = cp_take(o, RE);
-    r.ret = cp_take(o, RE);
-    r.ret2 = cp_take(o, RE);
-    r.misc = cp_take(o, 4);  // [0] any env running
+    r.spec = ro_take(o, (int64_t)(sizeof(SpecShared) / 4));
+    r.x = ro_take(o, eu);
+    r.y = ro_take(o, eu);
+    r.hp = ro_take(o, eu);
+    r.nhp = ro_take(o, eu);
+    r.act = ro_take(o, eu);
+    r.pact = ro_take(o, en);
+    r.prev = ro_take(o, en);
+    r.status = ro_take(o, RE);
+    r.stepped = ro_take(o, RE);
+    r.len = ro_take(o, RE);
+    r.ret = ro_take(o, RE);
+    r.ret2 = ro_take(o, RE);
+    r.misc = ro_take(o, 4);  // [0] any env running
     r.ldo = 8 * U + 4;
     r.obs_words = (int32_t)mlg_align4(en * r.ldo);
     r.avail_words = (int32_t)mlg_align4(en * A);
     r.avail = r.obs = -1;
     if (rows_in_lds) {
-        r.avail = cp_take(o, r.avail_words);
-        r.obs = cp_take(o, r.obs_words);
+        r.avail = ro_take(o, r.avail_words);
+        r.obs = ro_take(o, r.obs_words);
     }
     r.total = (int32_t)o;
     return r;
@@ -472,11 +412,7 @@ int launch_crossplay(int grid, int threads, hipStream_t s, const CpArgs& a, cons
                      const CpLds& lay) {
     const size_t bytes = (size_t)lay.total * 4;
     auto kern = crossplay_kernel<H, TPW>;
-    if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)bytes);
-        if (e != hipSuccess) return mlg::fail("crossplay: LDS attribute (%zu B): %s", bytes, hipGetErrorString(e));
-    }
+    if (int rc = allow_lds(kern, bytes, "crossplay")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), bytes, s, a, sh, L, lay);
     return 0;
 }

@@ -26,7 +26,8 @@ def test_v7_latency_floor_annotation_present():
     assert "stamps" in c.get("one_env_step_source", "")
 
 
-V7_SOURCES = ("ma-league_amd/csrc/rollout.hip", "ma-league_amd/csrc/mlg_device.h", "ma-league_amd/csrc/agent_device.h")
+V7_SOURCES = ("ma-league_amd/csrc/rollout.hip", "ma-league_amd/csrc/rollout_env_device.h",
+              "ma-league_amd/csrc/mlg_device.h", "ma-league_amd/csrc/agent_device.h")
 
 
 def test_v7_latency_floor_stamp_is_current():
