@@ -537,6 +537,14 @@ int mlg_rollout_policy(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgentDi
                        MlgBatch *batch, MlgRunInfo *info, float epsilon, int32_t test_mode,
                        int32_t mask_before_softmax, int32_t test_greedy, void *stream);
 
+/* Host only, launches nothing (the contract of mlg_rollout_describe). Writes the name of the instantiation
+ * mlg_rollout_policy would launch for this spec and agent dims, and the dynamic LDS bytes of that launch. Names:
+ * "policy-lds/tpwK" / "policy-global/tpwK" (the policy's weights in LDS / read from global memory, K = 1..4 agent tiles
+ * per wave). mlg_rollout_policy takes its decision from the same function. Nonzero (mlg_last_error) where it would
+ * refuse the spec or the dims. */
+int mlg_rollout_policy_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, char *name, int32_t name_cap,
+                                int64_t *lds_bytes);
+
 /* The COMA actor loss (coma_learner.py:75-96), forward and d loss / d pi in one launch. rows = B (T - 1) mask entries,
  * pi / avail / q_vals [rows][N][A], actions [rows][N], mask [rows]: pi is zeroed where unavailable and renormalised,
  * baseline = sum pi q, advantage = q_taken - baseline (a constant for the gradient), pi_taken = 1 where mask == 0,

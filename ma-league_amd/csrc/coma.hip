@@ -237,6 +237,7 @@ __device__ __forceinline__ float critic_x(const ComaDev& c, int slot, int t, int
 
 // acc[ot] (16 output features x 16 rows, mlg_device.h orientation: lane l, reg r = feature 16 ot + 4 (l >> 4) + r of
 // row l & 15) = bias + W x over K inputs; W element (o, k) at W[o * so + k * sk], x of row `col` from xs(k).
+constexpr int DENSE_KB = 32;  // inputs per partial chain of dense16 (a multiple of 4)
 template <int OT, class XF>
 __device__ __forceinline__ void dense16(floatx4 (&acc)[OT], const float* __restrict__ W, int64_t so, int64_t sk,
                                         const float* __restrict__ bias, int O, int K, int lane, XF xs) {
@@ -248,16 +249,27 @@ __device__ __forceinline__ void dense16(floatx4 (&acc)[OT], const float* __restr
             const int o = 16 * ot + 4 * g + r;
             acc[ot][r] = (bias && o < O) ? bias[o] : 0.f;
         }
-    for (int k0 = 0; k0 < K; k0 += 4) {
-        const int k = k0 + g;
-        const bool kin = k < K;
-        const float x = kin ? xs(k) : 0.f;
+    // Blocked sum: DENSE_KB inputs at a time go into a fresh chain that is then added to the total, so the rounding
+    // error grows with the number of blocks and the block length, not with K (fc1 has K up to S + d_obs + 2 N A + N in
+    // the thousands). One sequential chain over K = 400 was 4-5x further from float64 than a blocked fp32 sum.
+    for (int kb = 0; kb < K; kb += DENSE_KB) {
+        floatx4 part[OT];
 #pragma unroll
-        for (int ot = 0; ot < OT; ++ot) {
-            const int o = 16 * ot + col;
-            const float w = (kin && o < O) ? W[o * so + k * sk] : 0.f;
-            acc[ot] = mfma4(w, x, acc[ot]);
+        for (int ot = 0; ot < OT; ++ot) part[ot] = floatx4{0.f, 0.f, 0.f, 0.f};
+        const int ke = kb + DENSE_KB < K ? kb + DENSE_KB : K;
+        for (int k0 = kb; k0 < ke; k0 += 4) {
+            const int k = k0 + g;
+            const bool kin = k < K;
+            const float x = kin ? xs(k) : 0.f;
+#pragma unroll
+            for (int ot = 0; ot < OT; ++ot) {
+                const int o = 16 * ot + col;
+                const float w = (kin && o < O) ? W[o * so + k * sk] : 0.f;
+                part[ot] = mfma4(w, x, part[ot]);
+            }
         }
+#pragma unroll
+        for (int ot = 0; ot < OT; ++ot) acc[ot] += part[ot];
     }
 }
 

@@ -223,19 +223,64 @@ int launch_policy_t(int grid, int threads, hipStream_t s, const MlgEnvSpec& spec
     return 0;
 }
 
-// Weights in LDS when the policy's image fits next to the env state, else read from HBM / L2.
+// ---- the dispatch decision (host only) ------------------------------------------------------------------------------
+// plan_policy is the one place that decides which rollout_policy_kernel<H, TPW, WLDS> runs; mlg_rollout_policy launches
+// what it returns and mlg_rollout_policy_describe reports it.
+struct PolicyPlan {
+    AgentLayout L;
+    int tpw, waves;  // agent tiles per wave, waves per workgroup
+    bool wlds;       // the policy's weights in LDS (else read from global memory)
+    RolloutLds lay;
+    char name[24];
+};
+
+// Checks what depends on the spec and the agent dims alone, in the entry point's order. Weights in LDS when the policy's
+// image fits next to the env state, else read from HBM / L2.
+int plan_policy(const MlgEnvSpec* spec, const MlgAgentDims* dims, PolicyPlan* p) {
+    MLG_REQUIRE(dims->n_agents == spec->n_agents && dims->n_actions == spec->n_actions && dims->d_obs == 8 * spec->U,
+                "rollout_policy: agent dims do not match env spec (N=%d/%d A=%d/%d d_obs=%d/%d)", dims->n_agents,
+                spec->n_agents, dims->n_actions, spec->n_actions, dims->d_obs, 8 * spec->U);
+    p->L = make_agent_layout(*dims);
+    MLG_REQUIRE(p->L.Ap <= 16 * RO_MAXAT, "rollout_policy: n_actions=%d does not fit %d action tiles", dims->n_actions,
+                RO_MAXAT);
+    const int tiles = (RE * spec->n_agents + 15) / 16;
+    p->waves = tiles < 8 ? tiles : 8;
+    p->tpw = (tiles + p->waves - 1) / p->waves;
+    MLG_REQUIRE(p->tpw <= 4, "rollout_policy: %d agent tiles per wave > 4 (too many agents per env)", p->tpw);
+    MLG_REQUIRE(p->L.H == 32 || p->L.H == 64 || p->L.H == 128,
+                "rollout_policy: rnn_hidden_dim=%d unsupported (32, 64, 128)", p->L.H);
+    p->lay = make_rollout_lds(p->L, spec->U, spec->n_agents, true);
+    p->wlds = p->lay.total * 4 <= LDS_LIMIT_BYTES;
+    if (!p->wlds) {
+        p->lay = make_rollout_lds(p->L, spec->U, spec->n_agents, false);
+        MLG_REQUIRE(p->lay.total * 4 <= LDS_LIMIT_BYTES, "rollout_policy: the env state of %d units does not fit in LDS",
+                    spec->U);
+    }
+    snprintf(p->name, sizeof p->name, "policy-%s/tpw%d", p->wlds ? "lds" : "global", p->tpw);
+    return 0;
+}
+
 template <int H, int TPW>
-int launch_policy(int grid, int threads, hipStream_t s, const MlgEnvSpec& spec, const MlgEnvState& st,
-                  const AgentLayout& L, const Sides& sd, const MlgRunInfo& info, int flags) {
-    RolloutLds lay = make_rollout_lds(L, spec.U, spec.n_agents, true);
-    if (lay.total * 4 <= LDS_LIMIT_BYTES)
-        return launch_policy_t<H, TPW, true>(grid, threads, s, spec, st, L, sd, info, flags, lay);
-    lay = make_rollout_lds(L, spec.U, spec.n_agents, false);
-    MLG_REQUIRE(lay.total * 4 <= LDS_LIMIT_BYTES, "rollout_policy: the env state of %d units does not fit in LDS", spec.U);
-    return launch_policy_t<H, TPW, false>(grid, threads, s, spec, st, L, sd, info, flags, lay);
+int launch_policy(const PolicyPlan& p, int grid, hipStream_t s, const MlgEnvSpec& spec, const MlgEnvState& st,
+                  const Sides& sd, const MlgRunInfo& info, int flags) {
+    if (p.wlds) return launch_policy_t<H, TPW, true>(grid, p.waves * 64, s, spec, st, p.L, sd, info, flags, p.lay);
+    return launch_policy_t<H, TPW, false>(grid, p.waves * 64, s, spec, st, p.L, sd, info, flags, p.lay);
 }
 
 }  // namespace
+
+extern "C" int mlg_rollout_policy_describe(const MlgEnvSpec* spec, const MlgAgentDims* dims, char* name,
+                                           int32_t name_cap, int64_t* lds_bytes) {
+    if (check_spec(spec) || check_agent_dims(dims)) return 1;
+    MLG_REQUIRE(name && name_cap > 0 && lds_bytes, "rollout_policy_describe: null output");
+    PolicyPlan plan;
+    if (int rc = plan_policy(spec, dims, &plan)) return rc;
+    MLG_REQUIRE((size_t)name_cap > strlen(plan.name), "rollout_policy_describe: name buffer of %d bytes too small",
+                name_cap);
+    strcpy(name, plan.name);
+    *lds_bytes = (int64_t)plan.lay.total * 4;
+    return 0;
+}
 
 extern "C" int mlg_rollout_policy(const MlgEnvSpec* spec, MlgEnvState* st, const MlgAgentDims* dims,
                                   const float* packed, MlgBatch* batch, MlgRunInfo* info, float epsilon,
@@ -244,12 +289,8 @@ extern "C" int mlg_rollout_policy(const MlgEnvSpec* spec, MlgEnvState* st, const
     MLG_REQUIRE(packed && batch && info, "rollout_policy: null pointer");
     if (check_rollout_batch(batch, spec, st, "rollout_policy")) return 1;
     MLG_REQUIRE(info->ep_len && info->ret && info->won && info->draw, "rollout_policy: run info has null tensors");
-    MLG_REQUIRE(dims->n_agents == spec->n_agents && dims->n_actions == spec->n_actions && dims->d_obs == 8 * spec->U,
-                "rollout_policy: agent dims do not match env spec (N=%d/%d A=%d/%d d_obs=%d/%d)", dims->n_agents,
-                spec->n_agents, dims->n_actions, spec->n_actions, dims->d_obs, 8 * spec->U);
-    const AgentLayout L = make_agent_layout(*dims);
-    MLG_REQUIRE(L.Ap <= 16 * RO_MAXAT, "rollout_policy: n_actions=%d does not fit %d action tiles", dims->n_actions,
-                RO_MAXAT);
+    PolicyPlan plan;
+    if (int rc = plan_policy(spec, dims, &plan)) return rc;
     hipStream_t s = (hipStream_t)stream;
     Sides sd;
     sd.bt[0] = sd.bt[1] = *batch;
@@ -258,27 +299,20 @@ extern "C" int mlg_rollout_policy(const MlgEnvSpec* spec, MlgEnvState* st, const
     sd.ns = 1;
     sd.nh = spec->n_agents;
     const int flags = (test_mode ? 1 : 0) | (mask_before_softmax ? 2 : 0) | (test_greedy ? 4 : 0);
-    const int tiles = (RE * sd.nh + 15) / 16;
-    const int W = tiles < 8 ? tiles : 8;
-    const int tpw = (tiles + W - 1) / W;
     const int grid = (st->B + RE - 1) / RE;
-    const int threads = W * 64;
     int rc = 0;
-    MLG_REQUIRE(tpw <= 4, "rollout_policy: %d agent tiles per wave > 4 (too many agents per env)", tpw);
-#define MLG_RO(HH, TT) rc = launch_policy<HH, TT>(grid, threads, s, *spec, *st, L, sd, *info, flags)
-#define MLG_RO_H(HH)          \
-    if (tpw == 1) MLG_RO(HH, 1);      \
-    else if (tpw == 2) MLG_RO(HH, 2); \
-    else if (tpw == 3) MLG_RO(HH, 3); \
+#define MLG_RO(HH, TT) rc = launch_policy<HH, TT>(plan, grid, s, *spec, *st, sd, *info, flags)
+#define MLG_RO_H(HH)               \
+    if (plan.tpw == 1) MLG_RO(HH, 1);      \
+    else if (plan.tpw == 2) MLG_RO(HH, 2); \
+    else if (plan.tpw == 3) MLG_RO(HH, 3); \
     else MLG_RO(HH, 4)
-    if (L.H == 64) {
+    if (plan.L.H == 64) {
         MLG_RO_H(64);
-    } else if (L.H == 32) {
+    } else if (plan.L.H == 32) {
         MLG_RO_H(32);
-    } else if (L.H == 128) {
-        MLG_RO_H(128);
     } else {
-        return mlg::fail("rollout_policy: rnn_hidden_dim=%d unsupported (32, 64, 128)", L.H);
+        MLG_RO_H(128);
     }
 #undef MLG_RO_H
 #undef MLG_RO

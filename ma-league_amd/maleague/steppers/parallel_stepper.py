@@ -196,7 +196,7 @@ class ParallelStepper(EnvStepper):
         if self.home_mac is None:
             raise MultiAgentControllerNotInitialized()
         if getattr(self.home_mac, "agent_output_type", "q") == "pi_logits":
-            raise NotImplementedError("mlg_rollout_policy has one kernel: there is no dispatch to describe")
+            return _native.rollout_policy_describe(self._cspec, self.home_mac.agent.dims())
         return _native.rollout_describe(self._cspec, self.home_mac.agent.dims(), self._SELFPLAY)
 
     def initialize(self, scheme, groups, preprocess, home_mac, away_mac=None):

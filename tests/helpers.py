@@ -516,3 +516,206 @@ def refil_teacher_check(spec, ag, a, nb, summ, B, T, seed, eps, test_mode, envs=
         assert nb["filled"][b, L + 1:].sum() == 0 and nb["reward"][b, L:].sum() == 0
     assert n_greedy > 0 and (test_mode or n_rand > 0)
     return {"greedy": n_greedy, "decisions": n_dec, "near_ties": n_tie, "epsilon_draws": n_rand}
+
+
+# ---- COMA: args, the policy rollout checker, the critic harness, random batches ----
+
+DELTA = 2e-4
+NEAR_TIE_CAP = 0.02
+
+
+def coma_args(**kw):
+    a = dict(agent_output_type="pi_logits", action_selector="multinomial", epsilon_start=0.5, epsilon_finish=0.01,
+             epsilon_anneal_time=100000, mask_before_softmax=False, critic_lr=0.0005, td_lambda=0.8, learner="coma",
+             critic_train_mode="seq", q_nstep=0, test_greedy=True, target_update_interval=200, mixer=None)
+    a.update(kw)
+    return qmix_args(**a)
+
+
+def _golden_batch(b, device):
+    import torch
+    from maleague.components.episode_batch import EpisodeBatch
+    B, T, N, _ = b["obs"].shape
+    info = {"state_shape": b["state"].shape[-1], "obs_shape": b["obs"].shape[-1],
+            "n_actions": b["avail_actions"].shape[-1], "n_agents": N}
+    scheme, groups, preprocess = scheme_for(info, torch)
+    eb = EpisodeBatch(scheme, groups, B, T, preprocess=preprocess, device=device)
+    for k, v in b.items():
+        eb.data.transition_data[k].copy_(torch.as_tensor(v))
+    return eb
+
+
+def _policy_stepper(device, plan, H, mask, B=17, episode_limit=12, seed=5, agent_params=None, fc2_scale=8.0,
+                    test_greedy=True):
+    """A ParallelStepper with a pi_logits BasicMAC (epsilon 0.3 flat). The agent: torch-seeded, or ``agent_params``, a
+    callable (d_in, H, n_actions) -> state_dict arrays; fc2.weight is multiplied by ``fc2_scale`` either way."""
+    import torch
+    from maleague.components.episode_batch import EpisodeBatch
+    from maleague.controllers import BasicMAC
+    from maleague.custom_logging import MainLogger
+    from maleague.steppers import ParallelStepper
+    args = coma_args(batch_size_run=B, seed=seed, rnn_hidden_dim=H, mask_before_softmax=mask, epsilon_start=0.3,
+                     epsilon_finish=0.3, test_greedy=test_greedy,
+                     env_args={"match_build_plan": plan, "grid_size": 20, "stochastic_spawns": True,
+                               "episode_limit": episode_limit})
+    stepper = ParallelStepper(args, MainLogger())
+    info = stepper.get_env_info()
+    args.n_agents, args.n_actions, args.state_shape = info["n_agents"], info["n_actions"], info["state_shape"]
+    scheme, groups, preprocess = scheme_for(info, torch)
+    proto = EpisodeBatch(scheme, groups, 1, 2, preprocess=preprocess, device=device)
+    torch.manual_seed(seed)
+    mac = BasicMAC(proto.scheme, groups, args)
+    if agent_params is not None:
+        d = mac.agent.dims()
+        mac.agent.load_state_dict({k: torch.from_numpy(v) for k, v in agent_params(d.d_in, H, d.n_actions).items()})
+    with torch.no_grad():  # a sharper policy than the initialisation's near-uniform one: few near-tie rows
+        mac.agent.fc2.weight.mul_(fc2_scale)
+    mac.agent.mark_dirty()
+    stepper.initialize(scheme, groups, preprocess, mac)
+    return stepper, mac, args, (scheme, groups, preprocess)
+
+
+def _check_policy_run(stepper, mac, args, batch, episode, test_mode, mask, test_greedy=True, stats=None):
+    """Env tensors bit-exact against the C env under teacher forcing; every pick against the float64 policy along the
+    recorded batch: a draw (train mode, or test mode without test_greedy: the floor-less probabilities) within DELTA
+    of the restated cdf, a greedy pick the argmax but for near ties (at most NEAR_TIE_CAP of the rows). ``stats``: a
+    dict that receives rows, near_ties and the largest distance of a draw's threshold outside its cdf interval."""
+    import torch
+    import coma_ref as CR
+    import envref
+    import learner_ref as LR
+    spec = stepper.spec
+    B, N, A, T1 = stepper.batch_size, spec.n_agents, spec.n_actions, stepper.episode_limit + 1
+    nb = np_batch(batch)
+    ep_len = stepper.last_run["ep_len"].numpy()
+    refs = ref_envs_for(spec, B, seed=args.seed)
+    for b, r in enumerate(refs):  # env tensors bit-exact against the C env, teacher forced with the recorded actions
+        r.episode = episode
+        r.reset()
+        L = int(ep_len[b])
+        np.testing.assert_array_equal(nb["obs"][b, 0], r.obs())
+        np.testing.assert_array_equal(nb["avail_actions"][b, 0], r.avail())
+        for t in range(L):
+            rew, done, _ = r.step(nb["actions"][b, t, :, 0])
+            assert nb["reward"][b, t, 0] == np.float32(rew[0])
+            assert nb["terminated"][b, t, 0] == int(done) and done == (t == L - 1)
+            np.testing.assert_array_equal(nb["obs"][b, t + 1], r.obs())
+            np.testing.assert_array_equal(nb["state"][b, t + 1], r.state())
+            np.testing.assert_array_equal(nb["avail_actions"][b, t + 1], r.avail())
+        np.testing.assert_array_equal(nb["filled"][b, :, 0], (np.arange(T1) <= L).astype(np.int64))
+        assert (nb["actions"][b, L + 1:] == 0).all() and (nb["actions_onehot"][b, L + 1:] == 0).all()
+        oh = np.zeros((L + 1, N, A), np.float32)
+        oh[np.arange(L + 1)[:, None], np.arange(N)[None, :], nb["actions"][b, :L + 1, :, 0]] = 1
+        np.testing.assert_array_equal(nb["actions_onehot"][b, :L + 1], oh)
+    params = {k: v.detach().cpu().double() for k, v in mac.agent.state_dict().items()}
+    tb = {k: torch.from_numpy(nb[k]).double() for k in ("obs", "actions_onehot")}
+    Tm = int(ep_len.max()) + 1
+    with torch.no_grad():
+        logits, _ = LR.mac_unroll(params, tb, N, T=Tm, h0=torch.zeros(B * N, args.rnn_hidden_dim, dtype=torch.float64))
+    probs = CR.softmax_policy(logits.numpy(), nb["avail_actions"][:, :Tm], 0.3, mask, test_mode)
+    m = np.where(nb["avail_actions"][:, :Tm] != 0, probs, 0.0)
+    rows = near = 0
+    greedy, worst = test_mode and test_greedy, 0.0
+    for b in range(B):
+        key = envref.env_key(args.seed, b)
+        for t in range(int(ep_len[b]) + 1):
+            for n in range(N):
+                a = int(nb["actions"][b, t, n, 0])
+                assert nb["avail_actions"][b, t, n, a] != 0, (b, t, n, a)
+                rows += 1
+                if greedy:
+                    srt = np.sort(m[b, t, n])
+                    if srt[-1] - srt[-2] < DELTA:
+                        near += 1
+                        assert m[b, t, n, a] >= srt[-1] - DELTA
+                    else:
+                        assert a == int(np.argmax(m[b, t, n])), (b, t, n)
+                    continue
+                cdf = np.cumsum(m[b, t, n])
+                thr = float(CR.policy_u(key, episode, t, n)) * cdf[-1]
+                lo = cdf[a - 1] if a > 0 else 0.0
+                worst = max(worst, lo - thr, thr - cdf[a])
+                assert lo - DELTA <= thr < cdf[a] + DELTA, (b, t, n, a, lo, thr, cdf[a])
+    assert rows == int((ep_len + 1).sum()) * N
+    if stats is not None:
+        stats.update(rows=rows, near_ties=near, cdf_excess=worst)
+    if greedy:
+        assert near <= NEAR_TIE_CAP * rows, f"{near} near-tie rows of {rows}"
+    return rows
+
+
+class CriticHarness:
+    """Flat device buffers around mlg_coma_critic_train / mlg_coma_target_update."""
+
+    def __init__(self, params, device, B, T, N, A, d_obs, S, interval=200, ws_fill=float("nan")):
+        import torch
+        import coma_ref as CR
+        from maleague import _native
+        self.n = _native
+        self.cfg = _native.MlgComaCfg(B=B, T=T, N=N, A=A, d_obs=d_obs, S=S, hidden=128, lr=5e-4, optim_alpha=0.99,
+                                      optim_eps=1e-5, grad_norm_clip=10.0, gamma=0.99, td_lambda=0.8)
+        lib = _native.load(require_gpu=True)
+        flat = np.concatenate([np.asarray(params[k], np.float32).reshape(-1) for k in CR.CRITIC_KEYS])
+        assert lib.mlg_coma_param_count(_native.byref(self.cfg)) == flat.size
+        self.params = torch.tensor(flat, device=device)
+        self.target = self.params.clone()
+        self.grads, self.sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self.ws = torch.full((lib.mlg_coma_workspace_floats(_native.byref(self.cfg)),), ws_fill, device=device)
+        self.q_vals = torch.full((B, T - 1, N, A), float("nan"), device=device)
+        self.targets = torch.full((B, T - 1, N), float("nan"), device=device)
+        self.stats = torch.full((6,), float("nan"), device=device)
+        self.counters = torch.zeros(2, dtype=torch.int64, device=device)
+        self.interval = interval
+        self.ws_fill = ws_fill
+
+    def refill(self):
+        """The workspace and the outputs back to their fill values: a call must not read what the last one left."""
+        self.ws.fill_(self.ws_fill)
+        for v in (self.q_vals, self.targets, self.stats):
+            v.fill_(float("nan"))
+
+    def train(self, eb, rows=None):
+        from maleague.components.batch_view import mlg_batch
+        n = self.n
+        mb, keep = mlg_batch(eb)
+        if rows is not None:
+            mb.B, mb.rows = len(rows), rows.data_ptr()
+        bufs = n.MlgComaBufs(mb, self.params.data_ptr(), self.grads.data_ptr(), self.sq.data_ptr(),
+                             self.target.data_ptr(), self.ws.data_ptr(), self.q_vals.data_ptr(),
+                             self.targets.data_ptr(), self.stats.data_ptr(), self.counters.data_ptr())
+        n.call("mlg_coma_critic_train", n.byref(self.cfg), n.byref(bufs), n.stream_ptr())
+        n.call("mlg_coma_target_update", self.params.data_ptr(), self.target.data_ptr(), self.params.numel(),
+               self.counters.data_ptr(), self.interval, n.stream_ptr())
+        del keep
+        return self.q_vals.cpu().numpy(), self.targets.cpu().numpy(), self.stats.cpu().numpy()
+
+
+def _random_batch(B, T, N, A, d_obs, S, lengths, seed):
+    rng = np.random.RandomState(seed)
+    b = {"state": np.zeros((B, T, S), np.float32), "obs": np.zeros((B, T, N, d_obs), np.float32),
+         "actions": np.zeros((B, T, N, 1), np.int64), "avail_actions": np.zeros((B, T, N, A), np.int32),
+         "reward": np.zeros((B, T, 1), np.float32), "terminated": np.zeros((B, T, 1), np.uint8),
+         "actions_onehot": np.zeros((B, T, N, A), np.float32), "filled": np.zeros((B, T, 1), np.int64)}
+    for e, L in enumerate(lengths):
+        n = min(L + 1, T)
+        b["state"][e, :n] = rng.randn(n, S)
+        b["obs"][e, :n] = rng.randn(n, N, d_obs)
+        b["avail_actions"][e, :n] = 1
+        acts = rng.randint(A, size=(n, N))
+        b["actions"][e, :n, :, 0] = acts
+        b["actions_onehot"][e, :n] = np.eye(A, dtype=np.float32)[acts]
+        b["filled"][e, :n] = 1
+        b["reward"][e, :min(L, T)] = rng.randn(min(L, T), 1)
+        if L <= T - 1:
+            b["terminated"][e, L - 1] = 1
+    return b
+
+
+def _random_critic(D, A, seed):
+    rng = np.random.RandomState(seed)
+    shapes = {"fc1.weight": (128, D), "fc1.bias": (128,), "fc2.weight": (128, 128), "fc2.bias": (128,),
+              "fc3.weight": (A, 128), "fc3.bias": (A,)}
+    return {k: (rng.uniform(-1, 1, s) / np.sqrt(s[-1] if len(s) > 1 else 128)).astype(np.float32)
+            for k, s in shapes.items()}
+
+

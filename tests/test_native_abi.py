@@ -19,7 +19,8 @@ def declared_symbols():
 def test_header_declares_entry_points():
     syms = declared_symbols()
     for need in ["mlg_rollout", "mlg_env_reset", "mlg_env_step", "mlg_env_observe", "mlg_agent_forward",
-                 "mlg_mac_forward", "mlg_select_actions", "mlg_pack_agent", "mlg_qmix_forward", "mlg_last_error"]:
+                 "mlg_mac_forward", "mlg_select_actions", "mlg_pack_agent", "mlg_qmix_forward", "mlg_last_error",
+                 "mlg_rollout_policy", "mlg_rollout_policy_describe"]:
         assert need in syms
 
 
