@@ -22,6 +22,9 @@
  *   mlg_mac_forward    BasicMAC.forward + _build_inputs  src/marl/controllers/basic_controller.py:38-50,80-92
  *   mlg_select_actions EpsilonGreedyActionSelector.select src/marl/components/action_selectors.py:44-62
  *   mlg_pack_agent     (layout step feeding the above; no reference counterpart)
+ *   mlg_ff_forward     DQNAgentNetwork.forward      src/marl/modules/agents/dqn_agent.py:34-37
+ *   mlg_ff_mac_forward / mlg_rollout_ff  BasicMAC.forward / ParallelStepper.run with agent: dqn (Feed-forward agent
+ *                      section below)
  *   mlg_qmix_forward   QMixer.forward               src/marl/modules/mixers/qmix.py:41-59
  *   mlg_agent_backward / mlg_qmix_backward  loss.backward() through the two above, one step / one call at a time
  *                      (src/marl/learners/q_learner.py:47-52,103 with any loss)
@@ -236,12 +239,19 @@ int mlg_qmix_backward(const MlgQMixParams *p, const float *agent_qs, const float
  * term[b,t]) target[b,t+1,n]) with the per-agent double-Q / masked-max target of VDN/QMIX; the mask is expanded
  * over the agents, mask_elems = N sum(mask): loss = sum(mask td^2) / mask_elems, td_error_abs = sum|mask td| /
  * mask_elems, q_taken_mean and target_mean divide by mask_elems * N (the reference's double division, kept).
- * stats[5] = mask_elems, stats[6] = count_nonzero of the expanded mask; trained_steps grows by the latter. */
+ * stats[5] = mask_elems, stats[6] = count_nonzero of the expanded mask; trained_steps grows by the latter.
+ * agent = 1 (feed-forward, DQNAgentNetwork): the flat agent vector is fc1.weight [H][d_in], fc1.bias [H], fc2.weight
+ * [A][H], fc2.bias [A]; H = rnn_hidden_dim is the width of fc1. No recurrence runs: one time-parallel kernel computes
+ * relu(fc1) of every live (16-row tile, t) block for the online and the target network, one backward kernel turns the
+ * mixer's deltas into the fc1 delta rows, and the workspace holds no GRU buffers. Mask scan, skip rules, mixers, the
+ * weight-gradient reduce, clip, RMSprop, target_sync, trained_steps and stats are those of agent = 0; the supported
+ * ranges too. A zero-initialised cfg keeps today's meaning. */
 typedef struct {
     int32_t B, T, N, A, d_obs, H, S, E, HE, hypernet_layers;
     int32_t mixer; /* 0 none (IQL), 1 vdn, 2 qmix */
     int32_t double_q, obs_last_action, obs_agent_id;
     float gamma, lr, optim_alpha, optim_eps, grad_norm_clip;
+    int32_t agent; /* 0 DRQN (rnn: everything above), 1 feed-forward (dqn): see above */
 } MlgLearnerCfg;
 
 typedef struct {
@@ -277,8 +287,9 @@ int mlg_qlearner_train(const MlgLearnerCfg *c, const MlgLearnerBufs *b, void *st
  * mixer's weight gradients ride in the reverse-recurrence launch, bwd4_wgrad_kernel) or bwd-split, q1..q6 (16-action
  * tiles of agent_q_kernel). Mixer part: iql, vdn-fast / vdn and qmix-split / qmix-generic (default widths E = 32,
  * HE = 64: the prefetching forms up to N = 8, A = 16, S = 64 / the generic mix_td_kernel<64, 32>), qmix1-e{E} (one
- * hypernet layer), qmix-he{HE}-e{E} (the other widths). Nonzero (mlg_last_error) where mlg_qlearner_train would
- * refuse the cfg. */
+ * hypernet layer), qmix-he{HE}-e{E} (the other widths). With agent = 1 the agent part is ff-h32 | ff-h64 | ff-h128 followed by /q1..q6,
+ * and QMIX at the default widths runs qmix-generic (no recurrence launch carries the split form). Nonzero
+ * (mlg_last_error) where mlg_qlearner_train would refuse the cfg. */
 int mlg_qlearner_describe(const MlgLearnerCfg *c, char *name, int32_t name_cap);
 
 
@@ -595,6 +606,49 @@ int mlg_coma_critic_train(const MlgComaCfg *c, const MlgComaBufs *b, void *strea
  * counters[1] = counters[0]. Two launches, no host sync. */
 int mlg_coma_target_update(const float *params, float *target_params, int64_t n, int64_t *counters, int32_t interval,
                            void *stream);
+
+/* ---- Feed-forward agent (agent: dqn): q = fc2(relu(fc1(inputs))), no recurrence ------------------------------
+ * DQNAgentNetwork (src/marl/modules/agents/dqn_agent.py:9-37); MlgAgentDims as for the DRQN, hidden = rnn_hidden_dim
+ * (the width of fc1), H in {32, 64, 128}. Canonical nn.Module layout (state_dict / named_parameters() order): */
+typedef struct {
+    const float *fc1_w, *fc1_b; /* [H][d_in], [H] */
+    const float *fc2_w, *fc2_b; /* [A][H], [A] */
+} MlgFFParams;
+
+/* Packed block (floats): w1d [H][Dip], w1o [H][Dob], w1a [A][H] (iff obs_last_action), w1n [N][H] (iff obs_agent_id),
+ * b1 [H], w2 [Ap][H], b2 [Ap]: the paddings and transposes of the DRQN block (Dip / Dob / Ap = d_in / d_obs / A rounded
+ * up to 16, zero padded) without the GRU blocks and the split-bf16 images. -1 (mlg_last_error()) on bad dims. */
+int64_t mlg_ff_packed_size(const MlgAgentDims *d);
+int mlg_ff_pack(const MlgAgentDims *d, const MlgFFParams *p, float *packed, void *stream);
+
+/* DQNAgentNetwork.forward over R rows: q [R][A] from inputs [R][d_in]. */
+int mlg_ff_forward(const MlgAgentDims *d, const float *packed, const float *inputs, float *q, int32_t R, void *stream);
+/* BasicMAC.forward(ep_batch, t) with a feed-forward agent: inputs built from the batch at t as mlg_mac_forward builds
+ * them (obs, onehot(a_{t-1}), agent id); batch->rows honoured. */
+int mlg_ff_mac_forward(const MlgAgentDims *d, const float *packed, const MlgBatch *batch, int32_t t,
+                       float *q /*[B][N][A]*/, void *stream);
+
+/* Backward of mlg_ff_forward (autograd of torch.ops.maleague.dqn_forward), the contract of mlg_agent_backward: it
+ * recomputes its forward from `inputs`, writes row activations and deltas to `workspace`
+ * (mlg_ff_backward_workspace_floats(dims, R) floats, 16-byte aligned, any contents) and reduces dparams (fc1.weight,
+ * fc1.bias, fc2.weight, fc2.bias) in a fixed order without float atomics. dparams is overwritten; R == 0 zeroes it.
+ * gq [R][A] NULL = zero upstream gradient, d_inputs [R][d_in] NULL = not wanted. `packed` must be the mlg_ff_pack()
+ * block of `p`, 16-byte aligned. */
+int64_t mlg_ff_backward_workspace_floats(const MlgAgentDims *d, int32_t R);
+int mlg_ff_backward(const MlgAgentDims *d, const MlgFFParams *p, const float *packed, const float *inputs,
+                    const float *gq, float *d_inputs, float *dparams, float *workspace, int32_t R, void *stream);
+
+/* One full ParallelStepper.run with a feed-forward agent: mlg_rollout's arguments, run semantics, ring / full-write
+ * modes, slot_extent and MlgRunInfo, on the generic fp32 rollout kernel's structure with no hidden state carried
+ * across steps; `packed` is the mlg_ff_pack() block. One launch. */
+int mlg_rollout_ff(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgentDims *dims, const float *packed,
+                   MlgBatch *batch, MlgRunInfo *info, float epsilon, int32_t test_mode, void *stream);
+/* Host only, launches nothing (the contract of mlg_rollout_describe). Names: "ff-lds/tpwK" / "ff-global/tpwK" (the
+ * weights w1o, w1a, w1n, b1, w2, b2 in LDS beside the env state / read from global memory, K = 1..4 agent tiles per
+ * wave). mlg_rollout_ff takes its decision from the same function. Nonzero (mlg_last_error) where it would refuse the
+ * spec or the dims. */
+int mlg_rollout_ff_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, char *name, int32_t name_cap,
+                            int64_t *lds_bytes);
 
 const char *mlg_last_error(void);
 const char *mlg_version(void);

@@ -38,6 +38,7 @@
 #include <cstring>
 
 #include "agent_device.h"
+#include "agent_ff_device.h"
 #include "batch_mask_device.h"
 #include "gru4_device.h"
 #include "mlg_host.h"
@@ -61,6 +62,19 @@ __host__ __device__ inline AgentOffs agent_offs(int H, int d_in, int A) {
     o.whh = p; p += (int64_t)3 * H * H;
     o.bih = p; p += 3 * H;
     o.bhh = p; p += 3 * H;
+    o.fc2w = p; p += (int64_t)A * H;
+    o.fc2b = p; p += A;
+    o.total = p;
+    return o;
+}
+
+// Feed-forward agent (MlgLearnerCfg.agent = 1): fc1.weight, fc1.bias, fc2.weight, fc2.bias; the GRU entries are empty.
+__host__ __device__ inline AgentOffs ff_offs(int H, int d_in, int A) {
+    AgentOffs o;
+    int64_t p = 0;
+    o.fc1w = p; p += (int64_t)H * d_in;
+    o.fc1b = p; p += H;
+    o.wih = o.whh = o.bih = o.bhh = p;
     o.fc2w = p; p += (int64_t)A * H;
     o.fc2b = p; p += A;
     o.total = p;
@@ -130,6 +144,7 @@ struct LCfg {
     int R, RM;
     float gamma;
     int full;  // MLG_LEARNER_FULL: no skipping
+    int ff;    // MlgLearnerCfg.agent = 1: the feed-forward agent (no recurrence kernels, no GRU buffers)
 };
 
 // What a call skips, from prep_kernel (workspace; every kernel after it reads the same three):
@@ -240,11 +255,17 @@ struct PrepJob {
     int64_t n_cmp;
     int cmp_vec;            // both 16-byte aligned
     int R, full;
+    int ff;                 // pack the feed-forward block (agent_ff_device.h) instead of the DRQN block
     int n_rows_in;          // > 0: the slot map travels here (host_rows); block 0 stores it to rows_dst
     int32_t* rows_dst;
     int32_t rows_in[MLG_INLINE_ROWS];
 };
 static_assert(sizeof(PrepJob) <= 3072, "PrepJob must fit the kernel-argument segment");
+
+__device__ __forceinline__ float prep_pack_agent(const PrepJob& J, const MlgAgentParams& ap, int64_t k) {
+    if (J.ff) return pack_ff_elem(J.L, MlgFFParams{ap.fc1_w, ap.fc1_b, ap.fc2_w, ap.fc2_b}, k);
+    return pack_agent_elem(J.L, ap, k);
+}
 
 __global__ void __launch_bounds__(1024) prep_kernel(PrepJob J) {
     if (blockIdx.x == 0) {
@@ -310,15 +331,15 @@ __global__ void __launch_bounds__(1024) prep_kernel(PrepJob J) {
         }
         return;
     }
-    const int64_t na = J.L.gsp,  // the learner reads no pre-split rollout sections (gsp, w1s)
+    const int64_t na = J.ff ? J.L.total : J.L.gsp,  // the learner reads no pre-split rollout sections (gsp, w1s)
                    nt = (int64_t)J.rows3 * J.cols, nm = J.mixer == 2 ? J.mp.total : 0;
     const int64_t total = 2 * na + nt + 2 * nm + J.n_d2 + J.n_dq + (J.n_cmp + 3) / 4;
     for (int64_t i = (int64_t)(blockIdx.x - 1) * blockDim.x + threadIdx.x; i < total;
          i += (int64_t)(gridDim.x - 1) * blockDim.x) {
         int64_t k = i;
-        if (k < na) { J.p_on[k] = pack_agent_elem(J.L, J.ap_on, k); continue; }
+        if (k < na) { J.p_on[k] = prep_pack_agent(J, J.ap_on, k); continue; }
         k -= na;
-        if (k < na) { J.p_tg[k] = pack_agent_elem(J.L, J.ap_tg, k); continue; }
+        if (k < na) { J.p_tg[k] = prep_pack_agent(J, J.ap_tg, k); continue; }
         k -= na;
         if (k < nt) {  // wihT[c][r] = wih[r][c]
             const int r = (int)(k / J.cols), c = (int)(k % J.cols);
@@ -538,6 +559,86 @@ __global__ void __launch_bounds__(512) agent_q_kernel(LCfg c, AgentLayout L, con
             const int a = at * 16 + 4 * g + k;
             if (a < c.A) qout[((int64_t)t * c.R + r) * c.A + a] = q[k];
         }
+    }
+}
+
+// ================================================================================================
+// Feed-forward agent (cfg.agent = 1): no recurrence, so the hidden rows of every (tile, t) block are independent.
+//   ff_hidden_kernel (t, tile, net): x = relu(fc1(inputs)) into the hidden rows agent_q_kernel reads (row block t + 1
+//                    of hs / hs_tg), and for the online net the dense input row the fc1 weight-gradient job reads.
+//                    agent_in_kernel's fc1 part, line for line: the same sums in the same order.
+//   ff_bwd_kernel    (t, tile): dh = W2^T d2 (d2 [T][R][A], the mixer's deltas), masked by the ReLU -> the fc1 delta rows.
+// grid (ntiles, T, 2) / (ntiles, T), HC waves: wave w computes feature chunk w.
+template <int H>
+__global__ void __launch_bounds__(512) ff_hidden_kernel(LCfg c, MlgBatch bt, AgentLayout L, const float* __restrict__ Pon,
+                                                        const float* __restrict__ Ptg, float* __restrict__ ws_in,
+                                                        float* __restrict__ hs_on, float* __restrict__ hs_tg, Skip sk) {
+    const int tile = blockIdx.x, t = blockIdx.y;
+    if (t >= tile_steps(sk, tile)) return;
+    const bool online = blockIdx.z == 0;
+    if (!online && !target_runs(c, sk)) return;
+    const float* P = online ? Pon : Ptg;
+    float* hs = (online ? hs_on : hs_tg) + (int64_t)(t + 1) * c.R * H;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int col = lane & 15, g = lane >> 4;
+    const int N = c.N, A = c.A, R = c.R;
+    const int r = tile * 16 + col;
+    const bool valid = r < R;
+    const int b = valid ? r / N : 0, n = valid ? r % N : 0;
+    const int64_t boff = (bslot(bt, b) * bt.T1 + t) * N + n;
+    floatx4 acc = ld4(P + L.b1 + w * 16 + 4 * g);
+    if (valid) {
+        if (L.last_action && t > 0) {
+            const int a = (int)bt.actions[boff - N];
+            const float v = (a >= 0 && a < A) ? bt.actions_onehot[(boff - N) * A + a] : 0.f;
+            if (v != 0.f) acc += v * ld4(P + L.w1a + (int64_t)a * H + w * 16 + 4 * g);
+        }
+        if (L.agent_id) acc += ld4(P + L.w1n + (int64_t)n * H + w * 16 + 4 * g);
+    }
+    const float* orow = valid ? bt.obs + boff * c.d_obs : nullptr;
+    const float* wrow = P + L.w1o + (int64_t)(w * 16 + col) * L.Dob + 4 * g;
+    for (int kc = 0; kc < L.Dob / 16; ++kc)
+        acc = mfma_chunk(ld4(wrow + kc * 16), load_chunk(orow, kc * 16 + 4 * g, c.d_obs), acc);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] = fmaxf(acc[q], 0.f);
+    if (valid) *reinterpret_cast<floatx4*>(hs + (int64_t)r * H + w * 16 + 4 * g) = acc;
+    if (!online) return;
+    // dense input row for dW1 (basic_controller.py:80-92 layout): 16 threads per row
+    const int l = tid & 15, oa = c.d_obs + (L.last_action ? A : 0);
+    for (int i = tid >> 4; i < 16; i += blockDim.x >> 4) {
+        const int rr = tile * 16 + i;
+        if (rr >= R) break;
+        const int bb = rr / N, nn = rr - bb * N;
+        const int64_t bo = (bslot(bt, bb) * bt.T1 + t) * N + nn;
+        float* dst = ws_in + ((int64_t)t * R + rr) * c.d_in;
+        const float* src = bt.obs + bo * c.d_obs;
+        for (int k = l; k < c.d_obs; k += 16) dst[k] = src[k];
+        if (L.last_action)
+            for (int k = l; k < A; k += 16) dst[c.d_obs + k] = t > 0 ? bt.actions_onehot[(bo - N) * A + k] : 0.f;
+        for (int k = l; k < c.d_in - oa; k += 16) dst[oa + k] = k == nn ? 1.f : 0.f;
+    }
+}
+
+template <int H>
+__global__ void __launch_bounds__(512) ff_bwd_kernel(LCfg c, AgentLayout L, const float* __restrict__ P,
+                                                     const float* __restrict__ hs_on, const float* __restrict__ d2,
+                                                     float* __restrict__ da, Skip sk) {
+    const int tile = blockIdx.x, t = blockIdx.y;
+    if (t >= tile_steps(sk, tile)) return;  // the fc1 weight gradient skips the block's rows
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int col = lane & 15, g = lane >> 4;
+    const int r = tile * 16 + col;
+    const bool valid = r < c.R;
+    const int64_t row = (int64_t)t * c.R + (valid ? r : 0);
+    const float* drow = valid ? d2 + row * c.A : nullptr;
+    const floatx4 xv = ld4(hs_on + (int64_t)(t + 1) * c.R * H + (int64_t)(valid ? r : 0) * H + w * 16 + 4 * g);
+    floatx4 dh = {0.f, 0.f, 0.f, 0.f};
+    for (int at = 0; at < L.Ap / 16; ++at)  // fc2 rows past A are zero in the packed block
+        dh = mfma_chunk(ld_col4(P + L.w2, at * 16 + 4 * g, H, w * 16 + col), load_chunk(drow, at * 16 + 4 * g, c.A), dh);
+    if (valid) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dh[q] = xv[q] > 0.f ? dh[q] : 0.f;
+        *reinterpret_cast<floatx4*>(da + row * H + w * 16 + 4 * g) = dh;
     }
 }
 
@@ -1903,6 +2004,7 @@ int check_cfg(const MlgLearnerCfg* c) {
                 "learner: T*B*N*3H=%lld floats exceeds the 2 GB buffer-store range",
                 (long long)c->T * c->B * c->N * 3 * c->H);
     MLG_REQUIRE(c->mixer >= 0 && c->mixer <= 2, "learner: mixer=%d unsupported (0 none, 1 vdn, 2 qmix)", c->mixer);
+    MLG_REQUIRE(c->agent == 0 || c->agent == 1, "learner: agent=%d unsupported (0 rnn: DRQN, 1 dqn: feed-forward)", c->agent);
     if (c->mixer == 2) {
         MLG_REQUIRE(c->hypernet_layers == 1 || c->hypernet_layers == 2, "learner: qmix hypernet_layers=%d unsupported (1, 2)",
                     c->hypernet_layers);
@@ -1937,10 +2039,11 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
     c.RM = cfg->B * (cfg->T - 1);
     c.gamma = cfg->gamma;
     c.full = getenv("MLG_LEARNER_FULL") != nullptr;  // read per call, so a test can set it
+    c.ff = cfg->agent == 1;
     p.layers = cfg->mixer == 2 ? cfg->hypernet_layers : 2;
     MlgAgentDims d{cfg->d_obs, cfg->A, cfg->N, cfg->H, c.d_in, cfg->obs_last_action, cfg->obs_agent_id};
-    p.L = make_agent_layout(d);
-    p.ao = agent_offs(c.H, c.d_in, c.A);
+    p.L = c.ff ? make_ff_layout(d) : make_agent_layout(d);
+    p.ao = c.ff ? ff_offs(c.H, c.d_in, c.A) : agent_offs(c.H, c.d_in, c.A);
     p.mo = mix_offs(c.N, c.S, c.E, c.HE, p.layers);
     p.mp = mix_pack(c.N, c.S, c.E, c.HE, p.layers);
     p.n_agent = p.ao.total;
@@ -1953,25 +2056,27 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
     auto take = [&](int64_t n) { int64_t r = o; o += a4(n); return r; };
     w.p_on = take(p.L.total);
     w.p_tg = take(p.L.total);
-    w.wihT = take(3 * H * H);
+    const int64_t G = c.ff ? 0 : 1;  // the feed-forward layout has no W_ih^T, gate, GI or gate-delta buffers
+    w.wihT = take(G * 3 * H * H);
     w.mix_on = take(p.mp.total);
     w.mix_tg = take(p.mp.total);
     w.in = take(T * R * c.d_in);
-    w.x = take(T * R * H);
+    w.x = take(G * T * R * H);
+    // feed-forward: row block t + 1 holds relu(fc1) of step t (what agent_q_kernel reads); block 0 is never touched
     w.hs = take((T + 1) * R * H);
     w.hs_tg = take((T + 1) * R * H);
-    w.gi_on = take(T * R * 3 * H);
-    w.gi_tg = take(T * R * 3 * H);
-    w.gr = take(T * R * H);
-    w.gz = take(T * R * H);
-    w.gn = take(T * R * H);
-    w.ghn = take(T * R * H);
+    w.gi_on = take(G * T * R * 3 * H);
+    w.gi_tg = take(G * T * R * 3 * H);
+    w.gr = take(G * T * R * H);
+    w.gz = take(G * T * R * H);
+    w.gn = take(G * T * R * H);
+    w.ghn = take(G * T * R * H);
     w.mac = take(T * R * c.A);
     w.tmac = take(T * R * c.A);
     w.dq = take(T * R);
     w.d2 = take(T * R * c.A);
-    w.dgi = take(T * R * 3 * H);
-    w.dgh = take(T * R * 3 * H);
+    w.dgi = take(G * T * R * 3 * H);
+    w.dgh = take(G * T * R * 3 * H);
     w.da = take(T * R * H);
     w.srow = take(RM * c.S);
     w.l1act = take(RM * (one ? c.E : L1));
@@ -2010,8 +2115,10 @@ WJobs make_jobs(Plan& p, float* ws, float* grads, int64_t* slab_floats, int* n_t
     J.n = 0;
     const AgentOffs& a = p.ao;
     J.j[J.n++] = mlg::bjob(at(p.w.da), H, at(p.w.in), c.d_in, gp(a.fc1w), gp(a.fc1b), H, c.d_in, TR);
-    J.j[J.n++] = mlg::bjob(at(p.w.dgi), 3 * H, at(p.w.x), H, gp(a.wih), gp(a.bih), 3 * H, H, TR);
-    J.j[J.n++] = mlg::bjob(at(p.w.dgh), 3 * H, at(p.w.hs), H, gp(a.whh), gp(a.bhh), 3 * H, H, TR);
+    if (!c.ff) {
+        J.j[J.n++] = mlg::bjob(at(p.w.dgi), 3 * H, at(p.w.x), H, gp(a.wih), gp(a.bih), 3 * H, H, TR);
+        J.j[J.n++] = mlg::bjob(at(p.w.dgh), 3 * H, at(p.w.hs), H, gp(a.whh), gp(a.bhh), 3 * H, H, TR);
+    }
     J.j[J.n++] = mlg::bjob(at(p.w.d2), c.A, at(p.w.hs) ? at(p.w.hs) + (int64_t)c.R * H : nullptr, H, gp(a.fc2w), gp(a.fc2b),
                      c.A, H, TR);
     const int n_agent_jobs = J.n;
@@ -2084,11 +2191,13 @@ int make_dispatch(const Plan& p, Dispatch* out) {
     // forces its generic form (the path of the other shapes)
     d.dflt_mix = c.mixer == 1 || (c.mixer == 2 && p.layers == 2 && c.E == 32 && c.HE == 64);
     d.fast_mix = d.dflt_mix && p.mp.Sp <= 64 && c.N <= MIXPF_N && c.A <= MIXPF_A && !getenv("MLG_MIX_GENERIC");
+    // feed-forward: no recurrence launch for the hypernet forward to ride in, so QMIX runs its one-kernel generic form
+    if (c.ff && c.mixer == 2) d.fast_mix = false;
     d.threads = (c.H / 16) * 64;
     d.split_mix = c.mixer == 2 && d.fast_mix && d.threads % 128 == 0;
     d.per = d.threads / 128;
     d.q_tiles = c.Ap / 16;
-    d.fused = Dispatch::fused_for(c.H);
+    d.fused = !c.ff && Dispatch::fused_for(c.H);
     if (c.mixer == 0) {
         d.mix = MIX_IQL;
     } else if (d.split_mix) {
@@ -2121,7 +2230,24 @@ void dispatch_name(const LCfg& c, const Dispatch& d, char* name, size_t cap) {
         case MIX_QMIX1: snprintf(mix, sizeof mix, "qmix1-e%d", c.E); break;
         case MIX_QMIX_WIDTHS: snprintf(mix, sizeof mix, "qmix-he%d-e%d", c.HE, c.E); break;
     }
-    snprintf(name, cap, "h%d/%s/q%d + %s", c.H, d.fused ? "bwd-fused" : "bwd-split", d.q_tiles, mix);
+    if (c.ff) snprintf(name, cap, "ff-h%d/q%d + %s", c.H, d.q_tiles, mix);
+    else snprintf(name, cap, "h%d/%s/q%d + %s", c.H, d.fused ? "bwd-fused" : "bwd-split", d.q_tiles, mix);
+}
+
+// the one reduce over the job table, then clip + RMSprop + statistics (both agents end a call the same way)
+int run_finish(const Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hipStream_t s, const WJobs& J,
+               int64_t n_red, unsigned* flag, const Skip& sk, int ntiles) {
+    const LCfg& c = p.c;
+    float* ws = bufs->workspace;
+    const int n_red_blocks = (int)((n_red + 255) / 256);
+    hipLaunchKernelGGL(mlg::wgrad_block_reduce_kernel<16>, dim3((unsigned)n_red_blocks), dim3(256), 0, s, J,
+                       ws + p.w.slab, ws + p.w.nrm);
+    const int64_t n_par = p.n_agent + p.n_mixer;
+    hipLaunchKernelGGL(finish_kernel, dim3((unsigned)((n_par + 1023) / 1024)), dim3(1024), 0, s, ws + p.w.part,
+                       p.w.n_mix_tiles, ws + p.w.msum + (c.mixer == 0 ? 2 : 0), bufs->params, bufs->grads, bufs->square_avg, n_par, cfg->lr,
+                       cfg->optim_alpha, cfg->optim_eps, cfg->grad_norm_clip, c.N, bufs->stats, ws + p.w.nrm,
+                       n_red_blocks, bufs->target_sync, bufs->trained_steps, sk, flag, ntiles, c.full);
+    return mlg::check_launch("qlearner_train");
 }
 
 template <int H>
@@ -2148,8 +2274,9 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     pj.p_tg = ws + p.w.p_tg;
     pj.wih = params + p.ao.wih;
     pj.wihT = ws + p.w.wihT;
-    pj.rows3 = 3 * c.H;
+    pj.rows3 = c.ff ? 0 : 3 * c.H;  // feed-forward: no W_ih^T
     pj.cols = c.H;
+    pj.ff = c.ff;
     pj.mp = p.mp;
     pj.mo = p.mo;
     pj.mix_src_on = params + p.n_agent;
@@ -2190,7 +2317,7 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
         for (int b = 0; b < c.B; ++b) pj.rows_in[b] = bufs->host_rows[b];
     }
     {
-        const int64_t work = 2 * p.L.total + 3 * (int64_t)c.H * c.H + (c.mixer == 2 ? 2 * p.mp.total : 0) + pj.n_d2 +
+        const int64_t work = 2 * p.L.total + (int64_t)pj.rows3 * c.H + (c.mixer == 2 ? 2 * p.mp.total : 0) + pj.n_d2 +
                              pj.n_dq + (pj.n_cmp + 3) / 4;
         const int blocks = 1 + (int)std::min<int64_t>((work + 1023) / 1024, 512);
         hipLaunchKernelGGL(prep_kernel, dim3(blocks), dim3(1024), 0, s, pj);
@@ -2217,9 +2344,15 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     }
     const int ntiles = (c.R + 15) / 16;
     HypOut hy{ws + p.w.hyp_on, ws + p.w.hyp_tg, ws + p.w.l1act, ws + p.w.srow, p.w.hyp_stride};
-    hipLaunchKernelGGL((agent_in_kernel<H>), dim3(ntiles, c.T, 2), dim3(threads), 0, s, c, bt, p.L, ws + p.w.p_on,
-                       ws + p.w.p_tg, ws + p.w.in, ws + p.w.x, ws + p.w.gi_on, ws + p.w.gi_tg, sk);
-    if (split_mix) {
+    if (c.ff)
+        hipLaunchKernelGGL((ff_hidden_kernel<H>), dim3(ntiles, c.T, 2), dim3(threads), 0, s, c, bt, p.L, ws + p.w.p_on,
+                           ws + p.w.p_tg, ws + p.w.in, ws + p.w.hs, ws + p.w.hs_tg, sk);
+    else
+        hipLaunchKernelGGL((agent_in_kernel<H>), dim3(ntiles, c.T, 2), dim3(threads), 0, s, c, bt, p.L, ws + p.w.p_on,
+                           ws + p.w.p_tg, ws + p.w.in, ws + p.w.x, ws + p.w.gi_on, ws + p.w.gi_tg, sk);
+    if (c.ff) {
+        // no recurrence: the hidden rows are complete
+    } else if (split_mix) {
         const int nrec = 2 * ((c.R + 3) / 4), per = dsp.per;
         hipLaunchKernelGGL((rec4_mixpre_kernel<H>), dim3(nrec + (p.w.n_mix_tiles + per - 1) / per), dim3(threads), 0, s,
                            c, p.L, ws + p.w.p_on, ws + p.w.p_tg, ws + p.w.gi_on, ws + p.w.gi_tg, ws + p.w.hs,
@@ -2275,6 +2408,14 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     int64_t slab_floats, n_red;
     int n_tasks;
     WJobs J = make_jobs(p, ws, bufs->grads, &slab_floats, &n_tasks, &n_red);
+    if (c.ff) {
+        // feed-forward: the fc1 delta rows, then every job in one launch and the one reduce
+        hipLaunchKernelGGL((ff_bwd_kernel<H>), dim3(ntiles, c.T), dim3(threads), 0, s, c, p.L, ws + p.w.p_on, ws + p.w.hs,
+                           ws + p.w.d2, ws + p.w.da, sk);
+        hipLaunchKernelGGL(mlg::wgrad_block_kernel<16>, dim3((unsigned)((n_tasks + 3) / 4)), dim3(256), 0, s, J,
+                           ws + p.w.slab);
+        return run_finish(p, cfg, bufs, s, J, n_red, pj.flag, sk, ntiles);
+    }
     int ta, tb;
     int64_t ra, rb;
     const WJobs JA = mlg::bjob_view(J, 3, J.n, &ta, &ra), JB = mlg::bjob_view(J, 0, 3, &tb, &rb);
@@ -2297,15 +2438,7 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     else
         hipLaunchKernelGGL(mlg::wgrad_block_kernel<16>, dim3((unsigned)((n_tasks + 3) / 4)), dim3(256), 0, s, J,
                            ws + p.w.slab);
-    const int n_red_blocks = (int)((n_red + 255) / 256);
-    hipLaunchKernelGGL(mlg::wgrad_block_reduce_kernel<16>, dim3((unsigned)n_red_blocks), dim3(256), 0, s, J,
-                       ws + p.w.slab, ws + p.w.nrm);
-    const int64_t n_par = p.n_agent + p.n_mixer;
-    hipLaunchKernelGGL(finish_kernel, dim3((unsigned)((n_par + 1023) / 1024)), dim3(1024), 0, s, ws + p.w.part,
-                       p.w.n_mix_tiles, ws + p.w.msum + (c.mixer == 0 ? 2 : 0), bufs->params, bufs->grads, bufs->square_avg, n_par, cfg->lr,
-                       cfg->optim_alpha, cfg->optim_eps, cfg->grad_norm_clip, c.N, bufs->stats, ws + p.w.nrm,
-                       n_red_blocks, bufs->target_sync, bufs->trained_steps, sk, pj.flag, ntiles, c.full);
-    return mlg::check_launch("qlearner_train");
+    return run_finish(p, cfg, bufs, s, J, n_red, pj.flag, sk, ntiles);
 }
 
 }  // namespace

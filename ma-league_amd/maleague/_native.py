@@ -56,6 +56,10 @@ class MlgAgentDims(ctypes.Structure):
                                               "obs_agent_id"]]
 
 
+class MlgFFParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ["fc1_w", "fc1_b", "fc2_w", "fc2_b"]]
+
+
 class MlgQMixParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ["hw1_0w", "hw1_0b", "hw1_2w", "hw1_2b", "hwf_0w", "hwf_0b", "hwf_2w",
                                               "hwf_2b", "hb1_w", "hb1_b", "v0_w", "v0_b", "v2_w", "v2_b"]] + \
@@ -66,7 +70,8 @@ class MlgQMixParams(ctypes.Structure):
 class MlgLearnerCfg(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ["B", "T", "N", "A", "d_obs", "H", "S", "E", "HE", "hypernet_layers",
                                               "mixer", "double_q", "obs_last_action", "obs_agent_id"]] + \
-               [(n, ctypes.c_float) for n in ["gamma", "lr", "optim_alpha", "optim_eps", "grad_norm_clip"]]
+               [(n, ctypes.c_float) for n in ["gamma", "lr", "optim_alpha", "optim_eps", "grad_norm_clip"]] + \
+               [("agent", ctypes.c_int32)]  # 0 DRQN, 1 feed-forward (dqn)
 
 
 class MlgLearnerBufs(ctypes.Structure):
@@ -195,6 +200,14 @@ SIGNATURES = {
     "mlg_coma_workspace_floats": (ctypes.c_int64, [_P]),
     "mlg_coma_critic_train": (ctypes.c_int, [_P, _P, _P]),
     "mlg_coma_target_update": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _I, _P]),
+    "mlg_ff_packed_size": (ctypes.c_int64, [_P]),
+    "mlg_ff_pack": (ctypes.c_int, [_P, _P, _P, _P]),
+    "mlg_ff_forward": (ctypes.c_int, [_P, _P, _P, _P, _I, _P]),
+    "mlg_ff_mac_forward": (ctypes.c_int, [_P, _P, _P, _I, _P, _P]),
+    "mlg_ff_backward_workspace_floats": (ctypes.c_int64, [_P, _I]),
+    "mlg_ff_backward": (ctypes.c_int, [_P] * 8 + [_I, _P]),
+    "mlg_rollout_ff": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
+    "mlg_rollout_ff_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
     "mlg_last_error": (ctypes.c_char_p, []),
     "mlg_version": (ctypes.c_char_p, []),
 }
@@ -254,6 +267,18 @@ def rollout_policy_describe(spec: MlgEnvSpec, dims: MlgAgentDims) -> tuple[str, 
     rc = lib.mlg_rollout_policy_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name), ctypes.byref(lds))
     if rc != 0:
         raise NativeError(f"mlg_rollout_policy_describe failed: {lib.mlg_last_error().decode()}")
+    return name.value.decode(), int(lds.value)
+
+
+def rollout_ff_describe(spec: MlgEnvSpec, dims: MlgAgentDims) -> tuple[str, int]:
+    """(instantiation name, dynamic LDS bytes) of the launch mlg_rollout_ff would make for this spec and agent dims
+    (mlg_rollout_ff_describe: host only, needs no GPU)."""
+    lib = load()
+    name = ctypes.create_string_buffer(32)
+    lds = ctypes.c_int64(0)
+    rc = lib.mlg_rollout_ff_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name), ctypes.byref(lds))
+    if rc != 0:
+        raise NativeError(f"mlg_rollout_ff_describe failed: {lib.mlg_last_error().decode()}")
     return name.value.decode(), int(lds.value)
 
 

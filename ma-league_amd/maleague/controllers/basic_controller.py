@@ -73,6 +73,14 @@ class BasicMAC(MultiAgentController):
     def _fused_forward(self, ep_batch, t):
         B, N, H = ep_batch.batch_size, self.n_agents, self.args.rnn_hidden_dim
         mb, keep = mlg_batch(ep_batch, required=("obs", "actions_onehot"))
+        if not getattr(self.agent, "recurrent", True):
+            # feed-forward agent (agent: dqn): no hidden state to read or to carry, hidden_states stays as it is
+            packed = self.agent.packed()
+            q = torch.empty(B, N, self.n_actions, device=packed.device)
+            _native.call("mlg_ff_mac_forward", _native.byref(self.agent.dims()), _native.ptr(packed),
+                         _native.byref(mb), int(t), _native.ptr(q), _native.stream_ptr())
+            del keep
+            return q
         h_in = self.hidden_states.reshape(B * N, H).float().contiguous()
         q = torch.empty(B, N, self.n_actions, device=h_in.device)
         h_out = torch.empty(B * N, H, device=h_in.device)

@@ -145,6 +145,10 @@ class CrossPlayEvaluator:
         if getattr(args, "agent_output_type", "q") != "q":
             raise NotImplementedError("cross-play evaluation plays greedy over Q values: agent_output_type="
                                       f"{args.agent_output_type!r} is not supported (COMA in the league is out of scope)")
+        if getattr(args, "agent", "rnn") != "rnn":
+            raise NotImplementedError("cross-play evaluation runs the recurrent agent (agent='rnn') only: "
+                                      f"agent={args.agent!r} is not supported (agent='dqn' and the other non-DRQN "
+                                      "agents in cross-play are out of scope)")
         self.E = int(episodes_per_launch or getattr(args, "league_eval_batch", 512))
         if self.E < 1:
             raise ValueError(f"episodes_per_launch={self.E}")

@@ -16,6 +16,7 @@ import torch
 
 from .. import _native
 from ..components.batch_view import mlg_batch
+from ..modules.agents import DQNAgentNetwork
 from ..modules.critics import COMACritic
 from ..modules.critics.coma import CRITIC_ORDER, HIDDEN
 from ..utils.checkpoint import save_module, save_optimizer
@@ -47,6 +48,9 @@ class COMALearner(Learner):
                 raise NotImplementedError(f"COMALearner supports {key}={want!r} only, got {key}={got!r}")
         if getattr(mac, "agent_output_type", "pi_logits") != "pi_logits":
             raise ValueError(f"COMALearner needs agent_output_type='pi_logits', got {mac.agent_output_type!r}")
+        if isinstance(getattr(mac, "agent", None), DQNAgentNetwork):
+            raise NotImplementedError("COMALearner trains the recurrent agent (agent='rnn') only: agent='dqn' with "
+                                      "agent_output_type='pi_logits' is not supported")
         self.critic = COMACritic(scheme, args)
         self.target_critic = copy.deepcopy(self.critic)
         self.device = torch.device(getattr(args, "device", "cuda"))

@@ -14,6 +14,7 @@ import torch
 
 from .. import _native
 from ..components.batch_view import mlg_batch
+from ..modules.agents import DQNAgentNetwork
 from ..modules.mixers import QMixer, VDNMixer
 from ..utils.checkpoint import save_module, save_optimizer
 
@@ -99,8 +100,9 @@ class QLearner(Learner):
 
     def _check_order(self):
         names = [n for n, _ in self.mac.agent.named_parameters()]
-        if names != AGENT_ORDER:
-            raise RuntimeError(f"agent parameter order {names} != kernel layout {AGENT_ORDER}")
+        order = list(getattr(self.mac.agent, "PARAM_ORDER", AGENT_ORDER))  # the feed-forward agent carries its own
+        if names != order:
+            raise RuntimeError(f"agent parameter order {names} != kernel layout {order}")
         if isinstance(self.mixer, QMixer):
             names = [n for n, _ in self.mixer.named_parameters()]
             order = QMIX1_ORDER if self.mixer.hypernet_layers == 1 else QMIX_ORDER
@@ -136,7 +138,8 @@ class QLearner(Learner):
                              mixer=mixer, double_q=int(bool(a.double_q)), obs_last_action=int(bool(a.obs_last_action)),
                              obs_agent_id=int(bool(a.obs_agent_id)), gamma=float(a.gamma), lr=float(a.lr),
                              optim_alpha=float(a.optim_alpha), optim_eps=float(a.optim_eps),
-                             grad_norm_clip=float(a.grad_norm_clip))
+                             grad_norm_clip=float(a.grad_norm_clip),
+                             agent=int(isinstance(self.mac.agent, DQNAgentNetwork)))
 
     def train(self, batch, t_env, episode_num: int):
         """q_learner.py:34-131. `t_env` may also be a zero-argument callable, resolved after the device work

@@ -17,6 +17,9 @@ raise on host tensors like every product path.
 | ``maleague::refil_agent_step``       | ``mlg_refil_agent_forward`` | EntityAttentionRNNAgent.forward, one step (entity_rnn_agent.py:32-65) |
 | ``maleague::drqn_forward``           | ``mlg_agent_forward``     | DRQNAgentNetwork.forward with the live parameters as inputs (differentiable) |
 | ``maleague::drqn_backward``          | ``mlg_agent_backward``    | its backward: one cell step (loss.backward(), q_learner.py:103) |
+| ``maleague::ff_forward``             | ``mlg_ff_forward``        | DQNAgentNetwork.forward (dqn_agent.py:34-37): fc2(relu(fc1(inputs))) |
+| ``maleague::dqn_forward``            | ``mlg_ff_forward``        | the same with the live parameters as inputs (differentiable) |
+| ``maleague::dqn_backward``           | ``mlg_ff_backward``       | its backward w.r.t. the inputs and the parameters   |
 | ``maleague::qmix_backward``          | ``mlg_qmix_backward``     | backward of ``qmix_forward`` w.r.t. agent_qs and the parameters |
 | ``maleague::refil_attention_backward`` | ``mlg_refil_attention_backward`` | backward of ``refil_attention`` w.r.t. x and the parameters |
 | ``maleague::flex_qmix_forward``      | ``mlg_refil_mixer_forward`` | FlexQMixer.forward with the live parameters as inputs (differentiable) |
@@ -28,7 +31,7 @@ raise on host tensors like every product path.
 | ``maleague::select_multinomial``     | ``mlg_select_multinomial`` | MultinomialActionSelector.select (action_selectors.py:11-32), counter RNG |
 | ``maleague::coma_policy_loss``       | ``mlg_coma_policy_loss``  | the COMA actor loss (coma_learner.py:75-96), forward and d pi in one launch |
 
-``drqn_forward``, ``qmix_forward``, ``refil_attention``, ``flex_qmix_forward`` and ``entity_agent_forward`` carry
+``drqn_forward``, ``dqn_forward``, ``qmix_forward``, ``refil_attention``, ``flex_qmix_forward`` and ``entity_agent_forward`` carry
 autograd formulas (``torch.library.register_autograd``) that call the backward ops; the backward ops have none, so
 double backward raises an error naming them. Gradients for ``packed``, ``dims``, the masks, the QMIX mixer's
 ``states`` and the REFIL ops' ``entities`` are ``None`` (states / entities that require grad are refused). The
@@ -286,6 +289,91 @@ def _drqn_backward(ctx, gq, gh_out):
 
 
 torch.library.register_autograd("maleague::drqn_forward", _drqn_backward, setup_context=_drqn_setup)
+
+
+# ---- DQNAgentNetwork.forward (feed-forward agent) ------------------------------------------------------------
+def _ff_forward(packed: Tensor, inputs: Tensor, dims: List[int]) -> Tensor:
+    d = _native.MlgAgentDims(*[int(v) for v in dims])
+    R = inputs.shape[0]
+    q = inputs.new_empty(R, d.n_actions)
+    _native.call("mlg_ff_forward", _native.byref(d), _native.ptr(packed), _native.ptr(inputs), _native.ptr(q), R,
+                 _stream(inputs))
+    return q
+
+
+@custom_op("maleague::ff_forward", mutates_args=())
+def ff_forward(packed: Tensor, inputs: Tensor, dims: List[int]) -> Tensor:
+    """dims = MlgAgentDims fields (hidden = the width of fc1); packed = the mlg_ff_pack() block;
+    inputs [R, d_in] -> q [R, A] = fc2(relu(fc1(inputs)))."""
+    return _ff_forward(packed, inputs, dims)
+
+
+@register_fake("maleague::ff_forward")
+def _ff_forward_fake(packed, inputs, dims):
+    return inputs.new_empty(inputs.shape[0], dims[1])
+
+
+def _ff_numels(dims: List[int]) -> List[int]:
+    """Sizes of the 4 feed-forward agent parameters in named_parameters() order (DQNAgentNetwork.PARAM_ORDER)."""
+    A, H, d_in = dims[1], dims[3], dims[4]
+    return [H * d_in, H, A * H, A]
+
+
+@custom_op("maleague::dqn_forward", mutates_args=())
+def dqn_forward(params: List[Tensor], packed: Tensor, inputs: Tensor, dims: List[int]) -> Tensor:
+    """``ff_forward`` with the 4 live parameters (fc1.weight, fc1.bias, fc2.weight, fc2.bias) as inputs autograd can
+    reach. The kernel reads ``packed``, which the caller guarantees is the pack of ``params``: values are
+    bit-identical to ``ff_forward``."""
+    return _ff_forward(packed, inputs, dims)
+
+
+@register_fake("maleague::dqn_forward")
+def _dqn_forward_fake(params, packed, inputs, dims):
+    return inputs.new_empty(inputs.shape[0], dims[1])
+
+
+@custom_op("maleague::dqn_backward", mutates_args=())
+def dqn_backward(params: List[Tensor], packed: Tensor, inputs: Tensor, gq: Optional[Tensor], dims: List[int]
+                 ) -> Tuple[Tensor, Tensor]:
+    """Backward of one ``dqn_forward`` call (``mlg_ff_backward``): gq [R, A] (None = zero) ->
+    (d_inputs [R, d_in], dflat: the 4 parameter gradients, flat, in named_parameters() order)."""
+    d = _native.MlgAgentDims(*[int(v) for v in dims])
+    R = inputs.shape[0]
+    keep = [p.contiguous() for p in params]
+    cparams = _native.MlgFFParams(*[_native.ptr(p) for p in keep])
+    inputs = inputs.contiguous()
+    gq = None if gq is None else gq.contiguous()
+    d_inputs = torch.empty_like(inputs)
+    dflat = inputs.new_empty(sum(_ff_numels(dims)))
+    ws = _workspace("mlg_ff_backward_workspace_floats", inputs, _native.byref(d), R)
+    _native.call("mlg_ff_backward", _native.byref(d), _native.byref(cparams), _native.ptr(packed),
+                 _native.ptr(inputs), _native.ptr(gq), _native.ptr(d_inputs), _native.ptr(dflat), _native.ptr(ws), R,
+                 _stream(inputs))
+    return d_inputs, dflat
+
+
+@register_fake("maleague::dqn_backward")
+def _dqn_backward_fake(params, packed, inputs, gq, dims):
+    return torch.empty_like(inputs), inputs.new_empty(sum(_ff_numels(dims)))
+
+
+def _dqn_setup(ctx, inputs, output):
+    params, packed, x, dims = inputs
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(*params, packed, x)
+    ctx.dims = [int(v) for v in dims]
+
+
+def _dqn_backward(ctx, gq):
+    *params, packed, x = ctx.saved_tensors
+    if gq is None:
+        return [None] * len(params), None, None, None
+    d_inputs, dflat = torch.ops.maleague.dqn_backward(list(params), packed, x, gq, ctx.dims)
+    need = ctx.needs_input_grad
+    return _split(dflat, list(params), need[0]), None, d_inputs if need[2] else None, None
+
+
+torch.library.register_autograd("maleague::dqn_forward", _dqn_backward, setup_context=_dqn_setup)
 
 
 @custom_op("maleague::qmix_backward", mutates_args=())

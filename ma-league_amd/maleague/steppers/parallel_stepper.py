@@ -22,6 +22,7 @@ from ..components.replay_buffer import RingEpisodeBatch
 from ..custom_logging import Collectibles, Originator
 from ..envs.teams_env import TeamsEnvSpec, VecEnvState
 from ..exceptions import MultiAgentControllerNotInitialized
+from ..modules.agents import DQNAgentNetwork
 
 
 def _same_device(a, b) -> bool:
@@ -174,7 +175,14 @@ class ParallelStepper(EnvStepper):
 
     def _rollout(self, mb, run_info, epsilon, test_mode):
         agent = self.home_mac.agent
+        if isinstance(agent, DQNAgentNetwork):
+            self._refuse_dqn_policy()
         st = self.envs.to_c()
+        if isinstance(agent, DQNAgentNetwork):
+            _native.call("mlg_rollout_ff", _native.byref(self._cspec), _native.byref(st), _native.byref(agent.dims()),
+                         _native.ptr(agent.packed()), _native.byref(mb), _native.byref(run_info), float(epsilon),
+                         int(bool(test_mode)), _native.stream_ptr(self.device))
+            return
         if getattr(self.home_mac, "agent_output_type", "q") == "pi_logits":
             # COMA: the softmax / epsilon-floor policy and the multinomial draw run inside the rollout kernel
             sel = self.home_mac.action_selector
@@ -190,11 +198,19 @@ class ParallelStepper(EnvStepper):
 
     _SELFPLAY = False  # which entry point run() calls: mlg_rollout / mlg_rollout_selfplay
 
+    def _refuse_dqn_policy(self):
+        if getattr(self.home_mac, "agent_output_type", "q") == "pi_logits":
+            raise NotImplementedError("agent='dqn' with agent_output_type='pi_logits' is not supported: the policy "
+                                      "rollout (mlg_rollout_policy) runs the recurrent agent (agent='rnn') only")
+
     def describe_rollout(self):
         """(kernel name, dynamic LDS bytes) of the launch the next run() makes with this env spec and the home MAC's
         agent under the current MLG_ROLLOUT_* environment (host only; the entry point decides by the same function)."""
         if self.home_mac is None:
             raise MultiAgentControllerNotInitialized()
+        if isinstance(self.home_mac.agent, DQNAgentNetwork):
+            self._refuse_dqn_policy()
+            return _native.rollout_ff_describe(self._cspec, self.home_mac.agent.dims())
         if getattr(self.home_mac, "agent_output_type", "q") == "pi_logits":
             return _native.rollout_policy_describe(self._cspec, self.home_mac.agent.dims())
         return _native.rollout_describe(self._cspec, self.home_mac.agent.dims(), self._SELFPLAY)

@@ -17,6 +17,7 @@ from .. import _native
 from ..components.batch_view import mlg_batch
 from ..components.replay_buffer import RingEpisodeBatch
 from ..exceptions import MultiAgentControllerNotInitialized
+from ..modules.agents import DRQNAgentNetwork
 from .parallel_stepper import LazyEnvInfos, ParallelStepper
 
 
@@ -41,6 +42,11 @@ class SelfPlayParallelStepper(ParallelStepper):
                 raise NotImplementedError(f"self-play rollouts select epsilon-greedy over Q values: the {side} MAC's "
                                           f"agent_output_type={mac.agent_output_type!r} is not supported (COMA in "
                                           "self-play is out of scope)")
+            agent = getattr(mac, "agent", None)
+            if agent is not None and not isinstance(agent, DRQNAgentNetwork):
+                raise NotImplementedError(f"self-play rollouts run the recurrent agent (agent='rnn') only: the {side} "
+                                          f"MAC's {type(agent).__name__} is not supported (agent='dqn' and the other "
+                                          "non-DRQN agents in self-play are out of scope)")
         ParallelStepper.initialize(self, scheme, groups, preprocess, home_mac)
         self.away_mac = away_mac
         self._away_buf = None
