@@ -45,10 +45,11 @@ def _clear_of_kinks(what, pre, x, w, b):
 
 
 # ---- agent step ----------------------------------------------------------------------------------------------
-def agent_case(R, H, A, seed, h_zero=False):
-    """Seeded parameters (state_dict names), inputs, hidden state and upstream gradients, float32 on the CPU."""
+def agent_case(R, H, A, seed, h_zero=False, d_in=None):
+    """Seeded parameters (state_dict names), inputs, hidden state and upstream gradients, float32 on the CPU.
+    d_in: the input width when it is not the fixture's [obs | last action | agent id] (tests/drqn_op_shapes.py)."""
     g = torch.Generator().manual_seed(seed)
-    d_in = D_OBS + A + N_AGENTS
+    d_in = D_OBS + A + N_AGENTS if d_in is None else d_in
     u = lambda *s, k=1.0: (torch.rand(*s, generator=g) * 2 - 1) * k  # noqa: E731
     p = {"fc1.weight": u(H, d_in, k=0.15), "fc1.bias": u(H, k=0.3), "gru.weight_ih": u(3 * H, H, k=0.25),
          "gru.weight_hh": u(3 * H, H, k=0.25), "gru.bias_ih": u(3 * H, k=0.3), "gru.bias_hh": u(3 * H, k=0.3),
@@ -161,7 +162,8 @@ def mixer_case(layers, N, R, seed):
     return mp, torch.randn(R, N, generator=g) * 1.5, torch.randn(R, S_DIM, generator=g), torch.randn(R, generator=g)
 
 
-def mixer_reference(mp, qs, st, g_out, layers, N, dtype, check=False):
+def mixer_reference(mp, qs, st, g_out, layers, N, dtype, check=False, S_DIM=S_DIM, E_DIM=E_DIM):
+    """S_DIM / E_DIM: the state and embedding widths when they are not the fixture's (tests/drqn_op_shapes.py)."""
     pp = {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in mp.items()}
     q, s = qs.detach().clone().to(dtype).requires_grad_(True), st.to(dtype)
     if check:
