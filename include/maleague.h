@@ -650,6 +650,35 @@ int mlg_rollout_ff(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgentDims *
 int mlg_rollout_ff_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, char *name, int32_t name_cap,
                             int64_t *lds_bytes);
 
+/* ---- Distinct per-agent networks (mac: distinct): agent slot i acts with network i, no parameter sharing --------
+ * DistinctMAC (src/marl/controllers/distinct_agents_controller.py). packed_pool [N][mlg_packed_agent_size(dims)]:
+ * row i is the mlg_pack_agent() block of network i (mlg_pack_agent_pool writes exactly this); N = dims->n_agents is
+ * the pool's row count; 16-byte aligned. dims->obs_agent_id must be 0 (the reference refuses agent ids for distinct
+ * networks). A 16-row MFMA tile is one agent across 16 batch rows / envs, its weight view selected by the tile's
+ * agent. No float atomics: the same inputs give the same bits. */
+
+/* DistinctMAC.forward(ep_batch, t): the contract of mlg_mac_forward (inputs built from the batch at t as
+ * [obs_t | onehot(a_{t-1})], batch->rows honoured, h_in NULL = zeros), q [B][N][A], h_in / h_out [B][N][H]. fc1 is
+ * summed in mlg_agent_forward's order over the concatenated row (the dense block), so row (b, i) has the bits of
+ * mlg_agent_forward with network i's block on that row: the MAC's differentiable path (maleague::drqn_forward per
+ * network) and this call agree bit for bit. */
+int mlg_mac_forward_distinct(const MlgAgentDims *dims, const float *packed_pool, const MlgBatch *batch, int32_t t,
+                             const float *h_in, float *q, float *h_out, void *stream);
+
+/* One full ParallelStepper.run with a DistinctMAC: mlg_rollout's arguments, run semantics, ring / full-write modes,
+ * slot_extent and MlgRunInfo and the counter RNG (the agent index is the epsilon stream index), on the generic fp32
+ * rollout kernel's structure with an agent-major agent phase: tile a = agent a of the workgroup's 16 envs, wave w owns
+ * tiles w, w + 8, ...; at most 4 tiles per wave, so more than 32 agents are refused (mlg_last_error names the tile
+ * count). Weights are read from global memory. A row's arithmetic is the generic kernel's (the column-gather fc1):
+ * with N equal networks a run stores the bits of mlg_rollout's generic fp32 kernel. One launch. */
+int mlg_rollout_distinct(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgentDims *dims, const float *packed_pool,
+                         MlgBatch *batch, MlgRunInfo *info, float epsilon, int32_t test_mode, void *stream);
+/* Host only, launches nothing (the contract of mlg_rollout_describe). Names: "dx-global/tpwK", K = 1..4 agent tiles
+ * per wave. mlg_rollout_distinct takes its decision from the same function. Nonzero (mlg_last_error) where it would
+ * refuse the spec or the dims. */
+int mlg_rollout_distinct_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, char *name, int32_t name_cap,
+                                  int64_t *lds_bytes);
+
 const char *mlg_last_error(void);
 const char *mlg_version(void);
 

@@ -208,6 +208,9 @@ SIGNATURES = {
     "mlg_ff_backward": (ctypes.c_int, [_P] * 8 + [_I, _P]),
     "mlg_rollout_ff": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
     "mlg_rollout_ff_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
+    "mlg_mac_forward_distinct": (ctypes.c_int, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "mlg_rollout_distinct": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
+    "mlg_rollout_distinct_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
     "mlg_last_error": (ctypes.c_char_p, []),
     "mlg_version": (ctypes.c_char_p, []),
 }
@@ -279,6 +282,18 @@ def rollout_ff_describe(spec: MlgEnvSpec, dims: MlgAgentDims) -> tuple[str, int]
     rc = lib.mlg_rollout_ff_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name), ctypes.byref(lds))
     if rc != 0:
         raise NativeError(f"mlg_rollout_ff_describe failed: {lib.mlg_last_error().decode()}")
+    return name.value.decode(), int(lds.value)
+
+
+def rollout_distinct_describe(spec: MlgEnvSpec, dims: MlgAgentDims) -> tuple[str, int]:
+    """(instantiation name, dynamic LDS bytes) of the launch mlg_rollout_distinct would make for this spec and agent
+    dims (mlg_rollout_distinct_describe: host only, needs no GPU)."""
+    lib = load()
+    name = ctypes.create_string_buffer(32)
+    lds = ctypes.c_int64(0)
+    rc = lib.mlg_rollout_distinct_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name), ctypes.byref(lds))
+    if rc != 0:
+        raise NativeError(f"mlg_rollout_distinct_describe failed: {lib.mlg_last_error().decode()}")
     return name.value.decode(), int(lds.value)
 
 

@@ -149,6 +149,9 @@ class CrossPlayEvaluator:
             raise NotImplementedError("cross-play evaluation runs the recurrent agent (agent='rnn') only: "
                                       f"agent={args.agent!r} is not supported (agent='dqn' and the other non-DRQN "
                                       "agents in cross-play are out of scope)")
+        if getattr(args, "mac", "basic") == "distinct":
+            raise NotImplementedError("cross-play evaluation packs one parameter-shared network per policy: "
+                                      "mac='distinct' is not supported (cross-play over distinct MACs is out of scope)")
         self.E = int(episodes_per_launch or getattr(args, "league_eval_batch", 512))
         if self.E < 1:
             raise ValueError(f"episodes_per_launch={self.E}")

@@ -37,6 +37,9 @@ class LeagueInstance:
         per player as CentralWorker assigns them, central_worker.py:84-93). Each match then puts this player's team
         against the opponent's (a historical snapshot plays its parent's team). None: every player plays the
         env config's own plan, mirrored."""
+        if getattr(args, "mac", "basic") == "distinct":
+            raise NotImplementedError("LeagueInstance shares one parameter-shared agent per player with the league: "
+                                      "mac='distinct' is not supported (a league over distinct MACs is out of scope)")
         self.args, self.logger, self.league = args, logger, league
         self.pid = league.player()
         self.mode = mode

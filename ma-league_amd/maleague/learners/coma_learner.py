@@ -16,6 +16,7 @@ import torch
 
 from .. import _native
 from ..components.batch_view import mlg_batch
+from ..controllers.distinct_controller import refuse_distinct
 from ..modules.agents import DQNAgentNetwork
 from ..modules.critics import COMACritic
 from ..modules.critics.coma import CRITIC_ORDER, HIDDEN
@@ -46,6 +47,7 @@ class COMALearner(Learner):
             got = getattr(args, key, want)
             if got != want:
                 raise NotImplementedError(f"COMALearner supports {key}={want!r} only, got {key}={got!r}")
+        refuse_distinct(mac, "COMALearner")
         if getattr(mac, "agent_output_type", "pi_logits") != "pi_logits":
             raise ValueError(f"COMALearner needs agent_output_type='pi_logits', got {mac.agent_output_type!r}")
         if isinstance(getattr(mac, "agent", None), DQNAgentNetwork):

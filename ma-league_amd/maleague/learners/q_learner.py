@@ -5,6 +5,10 @@ double-Q targets, mixer forward/backward, masked TD loss, all weight gradients, 
 RMSprop step. To make that possible the parameters of the MAC and mixer (and of their target copies)
 are re-homed into flat fp32 buffers; the nn.Module parameters become views into them, so state_dict()
 keys, checkpoint files and torch.optim.RMSprop.state_dict() stay compatible with the reference.
+
+With a DistinctMAC (mac: distinct, one network per agent slot) train() takes an unrolled branch instead
+(_train_distinct): the MAC's differentiable forward per step, the mixer op with its HIP backward, torch's
+clip_grad_norm_ and RMSprop; the fused pipeline holds one shared agent and is not extended.
 """
 from __future__ import annotations
 
@@ -14,6 +18,7 @@ import torch
 
 from .. import _native
 from ..components.batch_view import mlg_batch
+from ..controllers.distinct_controller import DistinctMAC
 from ..modules.agents import DQNAgentNetwork
 from ..modules.mixers import QMixer, VDNMixer
 from ..utils.checkpoint import save_module, save_optimizer
@@ -89,6 +94,12 @@ class QLearner(Learner):
         self._last_stats = None
         self._stats_fresh = False
         self.train_calls = 0
+        # one network per agent slot: the unrolled branch (_train_distinct); mlg_qlearner_train holds one shared agent
+        self._distinct = isinstance(mac, DistinctMAC)
+        if self._distinct:
+            mac.enable_autograd()
+            if isinstance(self.mixer, QMixer):
+                self.mixer.enable_autograd()
 
     def parameters(self):
         # the reference's precedence slip (q_learner.py:30-32) returns [] for IQL; VDN/QMIX are unaffected
@@ -99,6 +110,8 @@ class QLearner(Learner):
                                                      if self.mixer is not None else [])
 
     def _check_order(self):
+        if self._distinct:
+            return  # torch autograd and torch.optim.RMSprop: no flat kernel layout to match
         names = [n for n, _ in self.mac.agent.named_parameters()]
         order = list(getattr(self.mac.agent, "PARAM_ORDER", AGENT_ORDER))  # the feed-forward agent carries its own
         if names != order:
@@ -111,6 +124,8 @@ class QLearner(Learner):
 
     def build_optimizer(self):
         self._check_order()
+        if self._distinct:
+            return self._build_optimizer_distinct()
         for m in [self.mac.agent, self.target_mac.agent] + ([self.mixer, self.target_mixer] if self.mixer else []):
             m.to(self.device)
         params = self.parameters()
@@ -146,6 +161,8 @@ class QLearner(Learner):
         is queued (lets the caller avoid a host sync before the launch)."""
         if self.optimiser is None:
             raise RuntimeError("call build_optimizer() before train()")
+        if self._distinct:
+            return self._train_distinct(batch, t_env, episode_num)
         lib = _native.load(require_gpu=True)
         cfg = self._cfg(batch.batch_size, batch.max_seq_length)
         need = lib.mlg_qlearner_workspace_floats(_native.byref(cfg))
@@ -187,6 +204,98 @@ class QLearner(Learner):
                 self.logger.log_stat(self.name + k, v, t_env)
             self.log_stats_t = t_env
 
+    # ---- mac: distinct -- the unrolled branch (the pattern COMALearner uses for its actor) -------------------------
+    def _build_optimizer_distinct(self):
+        """Parameters of the N networks (and the mixer) re-homed back to back into one flat buffer, as the fused
+        learner's: the MAC's pool then packs in one mlg_pack_agent_pool launch and the target update is one copy.
+        Gradients are autograd's, the step torch.optim.RMSprop's."""
+        mods = [self.mac.agents, self.target_mac.agents] + ([self.mixer, self.target_mixer] if self.mixer else [])
+        for m in mods:
+            m.to(self.device)
+        params = self.parameters()
+        self._flat = FlatParams(params, self.device)
+        self._tflat = FlatParams(self._target_parameters(), self.device)
+        a = self.args
+        self.optimiser = torch.optim.RMSprop(params=params, lr=a.lr, alpha=a.optim_alpha, eps=a.optim_eps)
+        self._stats = torch.zeros(8, dtype=torch.float32, device=self.device)
+        self.mac.mark_dirty()
+        self.target_mac.mark_dirty()
+
+    def _train_distinct(self, batch, t_env, episode_num):
+        """q_learner.py:34-131 with torch ops over the MAC unrolls: the online MAC differentiably
+        (maleague::drqn_forward per network and step, HIP backward), the target MAC under no_grad through the fused
+        mlg_mac_forward_distinct; QMIX through maleague::qmix_forward (HIP backward), VDN's sum, or none."""
+        a = self.args
+        rewards = batch["reward"][:, :-1]
+        actions = batch["actions"][:, :-1]
+        terminated = batch["terminated"][:, :-1].float()
+        mask = batch["filled"][:, :-1].float()
+        mask[:, 1:] = mask[:, 1:] * (1 - terminated[:, :-1])
+        avail = batch["avail_actions"]
+        T = batch.max_seq_length
+        # the reference trains on the sample truncated to max_t_filled (ma_experiment.py:235-239): transitions from
+        # max_t_filled - 1 on are masked out, on the device (no host sync), as the fused learner does
+        te = batch["filled"][:, :, 0].sum(dim=1).max().clamp(min=2)
+        mask = mask * (torch.arange(T - 1, device=mask.device) < te - 1).view(1, T - 1, 1).float()
+        self.mac.init_hidden(batch.batch_size)
+        mac_out = torch.stack([self.mac.forward(batch, t=t) for t in range(T)], dim=1)
+        chosen = torch.gather(mac_out[:, :-1], dim=3, index=actions).squeeze(3)
+        # A slot that is dead in every stored step (nothing but the no-op, action 0, was ever available to it) took no
+        # decision in this batch. Its chosen Q keeps its value in the mix, the loss and the statistics, but passes no
+        # gradient: the slot's own network gets exactly zero and is not moved (DESIGN.md §7; with shared parameters
+        # the question does not arise). The other slots' gradients do not change.
+        stored = (batch["filled"][:, :, 0] != 0).unsqueeze(2)
+        alive = ((avail[..., 1:] != 0).any(dim=3) & stored).flatten(0, 1).any(dim=0)  # [N]
+        chosen = torch.where(alive.view(1, 1, -1), chosen, chosen.detach())
+        with torch.no_grad():
+            self.target_mac.init_hidden(batch.batch_size)
+            tmac = torch.stack([self.target_mac.forward(batch, t=t) for t in range(T)][1:], dim=1)
+            tmac[avail[:, 1:] == 0] = -9999999
+            if a.double_q:
+                md = mac_out.detach().clone()
+                md[avail == 0] = -9999999
+                cur_max = md[:, 1:].max(dim=3, keepdim=True)[1]
+                target_max = torch.gather(tmac, 3, cur_max).squeeze(3)
+            else:
+                target_max = tmac.max(dim=3)[0]
+        if self.mixer is not None:
+            chosen = self.mixer(chosen, batch["state"][:, :-1])
+            with torch.no_grad():
+                target_max = self.target_mixer(target_max, batch["state"][:, 1:])
+        targets = rewards + a.gamma * (1 - terminated) * target_max
+        td = chosen - targets.detach()
+        mask = mask.expand_as(td)
+        mtd = td * mask
+        n = mask.sum()
+        loss = (mtd ** 2).sum() / n
+        self.optimiser.zero_grad()
+        loss.backward()
+        params = self.parameters()
+        grad_norm = torch.nn.utils.clip_grad_norm_(params, a.grad_norm_clip)
+        self.optimiser.step()
+        self.mac.mark_dirty()
+        self.train_calls += 1
+        if (episode_num - self.last_target_update_episode) / a.target_update_interval >= 1.0:
+            self.update_targets()
+            self.last_target_update_episode = episode_num
+        with torch.no_grad():
+            steps = torch.count_nonzero(mask)
+            for ag in self.mac.agents:  # no host sync: trained steps accumulate on the device (Agent.trained_steps)
+                ag.add_trained_steps(steps)
+            self._stats[:7] = torch.stack([loss.detach(), grad_norm.detach().reshape(()), mtd.abs().sum() / n,
+                                           (chosen * mask).sum() / (n * a.n_agents),
+                                           (targets * mask).sum() / (n * a.n_agents), n, steps.float()])
+        self._stats_fresh = True
+        if callable(t_env):
+            up = getattr(t_env, "upper", None)
+            if up is not None and up() - self.log_stats_t < a.learner_log_interval:
+                return
+            t_env = t_env()
+        if t_env - self.log_stats_t >= a.learner_log_interval:
+            for k, v in self.last_stats.items():
+                self.logger.log_stat(self.name + k, v, t_env)
+            self.log_stats_t = t_env
+
     @property
     def last_stats(self):
         """Stats of the latest train() (q_learner.py:115-124 values); reading them syncs the stream."""
@@ -200,7 +309,7 @@ class QLearner(Learner):
 
     def update_targets(self):
         self._tflat.flat.copy_(self._flat.flat)
-        self.target_mac.agent.mark_dirty()
+        (self.target_mac if self._distinct else self.target_mac.agent).mark_dirty()
         self.logger.info(f"Updated {self.name}target network.")
 
     def cuda(self):
@@ -220,6 +329,11 @@ class QLearner(Learner):
             self.mixer.load_state_dict(sd)
         opt = torch.load(f"{path}/{self.name}opt.th", map_location=lambda s, loc: s, weights_only=True)
         self.optimiser.load_state_dict(opt)
+        if self._distinct:  # torch's own RMSprop state: nothing to re-home
+            self._tflat.flat.copy_(self._flat.flat)
+            self.mac.mark_dirty()
+            self.target_mac.mark_dirty()
+            return
         for p, off, k in self._flat.views:  # re-home the loaded RMSprop state into the flat buffer
             st = self.optimiser.state.get(p, {})
             if "square_avg" in st:

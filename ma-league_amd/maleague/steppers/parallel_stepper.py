@@ -19,6 +19,7 @@ from .. import _native
 from ..components.batch_view import mlg_batch
 from ..components.episode_batch import EpisodeBatch
 from ..components.replay_buffer import RingEpisodeBatch
+from ..controllers.distinct_controller import DistinctMAC
 from ..custom_logging import Collectibles, Originator
 from ..envs.teams_env import TeamsEnvSpec, VecEnvState
 from ..exceptions import MultiAgentControllerNotInitialized
@@ -174,6 +175,13 @@ class ParallelStepper(EnvStepper):
         return mlg_batch(batch)
 
     def _rollout(self, mb, run_info, epsilon, test_mode):
+        if isinstance(self.home_mac, DistinctMAC):
+            # one network per agent slot: the agent-major rollout kernel over the MAC's packed pool
+            mac = self.home_mac
+            _native.call("mlg_rollout_distinct", _native.byref(self._cspec), _native.byref(self.envs.to_c()),
+                         _native.byref(mac.dims()), _native.ptr(mac.packed()), _native.byref(mb),
+                         _native.byref(run_info), float(epsilon), int(bool(test_mode)), _native.stream_ptr(self.device))
+            return
         agent = self.home_mac.agent
         if isinstance(agent, DQNAgentNetwork):
             self._refuse_dqn_policy()
@@ -208,6 +216,8 @@ class ParallelStepper(EnvStepper):
         agent under the current MLG_ROLLOUT_* environment (host only; the entry point decides by the same function)."""
         if self.home_mac is None:
             raise MultiAgentControllerNotInitialized()
+        if isinstance(self.home_mac, DistinctMAC):
+            return _native.rollout_distinct_describe(self._cspec, self.home_mac.dims())
         if isinstance(self.home_mac.agent, DQNAgentNetwork):
             self._refuse_dqn_policy()
             return _native.rollout_ff_describe(self._cspec, self.home_mac.agent.dims())
@@ -417,7 +427,8 @@ class ParallelStepper(EnvStepper):
 
     def _launch_mb(self, mb, epsilon: float, test_mode: bool):
         run_info = self._run_info()
-        self.home_mac.agent.packed()  # a re-pack (parameters changed) runs before the timed window
+        # a re-pack (parameters changed) runs before the timed window
+        (self.home_mac if isinstance(self.home_mac, DistinctMAC) else self.home_mac.agent).packed()
         ev = None
         if self._timed_launch():
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))

@@ -16,6 +16,7 @@ import torch
 from .. import _native
 from ..components.batch_view import mlg_batch
 from ..components.replay_buffer import RingEpisodeBatch
+from ..controllers.distinct_controller import refuse_distinct
 from ..exceptions import MultiAgentControllerNotInitialized
 from ..modules.agents import DRQNAgentNetwork
 from .parallel_stepper import LazyEnvInfos, ParallelStepper
@@ -38,6 +39,7 @@ class SelfPlayParallelStepper(ParallelStepper):
         if away_mac is None:
             raise ValueError("self-play needs an away MAC (initialize(..., home_mac, away_mac))")
         for side, mac in (("home", home_mac), ("away", away_mac)):
+            refuse_distinct(mac, f"self-play rollouts ({side} MAC)")
             if getattr(mac, "agent_output_type", "q") != "q":
                 raise NotImplementedError(f"self-play rollouts select epsilon-greedy over Q values: the {side} MAC's "
                                           f"agent_output_type={mac.agent_output_type!r} is not supported (COMA in "
