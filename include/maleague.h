@@ -245,13 +245,28 @@ int mlg_qmix_backward(const MlgQMixParams *p, const float *agent_qs, const float
  * relu(fc1) of every live (16-row tile, t) block for the online and the target network, one backward kernel turns the
  * mixer's deltas into the fc1 delta rows, and the workspace holds no GRU buffers. Mask scan, skip rules, mixers, the
  * weight-gradient reduce, clip, RMSprop, target_sync, trained_steps and stats are those of agent = 0; the supported
- * ranges too. A zero-initialised cfg keeps today's meaning. */
+ * ranges too. A zero-initialised cfg keeps today's meaning.
+ * distinct = 1 (one DRQN per agent slot, DistinctMAC): params, grads, square_avg, target_params and target_sync are
+ * [agent 0 | agent 1 | ... | agent N-1 | mixer], each agent block in the agent order above with d_in = d_obs (+ A with
+ * obs_last_action); mlg_qlearner_param_counts returns n_agent = N x one block. Network n reads the obs / last-action
+ * rows of slot n and receives the gradient of slot n's rows only. The agent kernels run N instances of the N = 1, R = B
+ * problem selected by a grid coordinate (per-agent strides on the packed weights, the workspace tensors and the
+ * gradient output; the weight-gradient jobs repeat per network): the launches per call do not depend on N. Mask scan,
+ * skip rules under MLG_LEARNER_FULL, the target pass only when the target differs bitwise, mixers 0 / 1 / 2 at every
+ * supported width, double-Q, TD error, stats, the clip over the whole vector, RMSprop, target_sync, host_rows and
+ * batch.rows are those of distinct = 0; stats[7] counts the blocks of all N instances, and trained_steps points at N
+ * doubles (one per network), each += count_nonzero(mask). Dead-slot rule, decided on the device: a slot to which, in
+ * every stored step of the batch (filled != 0), no action other than action 0 is available keeps its chosen Q in the
+ * mix, the loss and the statistics, but its network receives an exactly zero gradient in every tensor, is left
+ * bit-unchanged by the step, and grad_norm is the norm without its share; a slot alive in any stored step trains on
+ * all its rows. Refused by name: agent = 1 with distinct = 1, obs_agent_id = 1, N > 32; H stays in {32, 64, 128}. */
 typedef struct {
     int32_t B, T, N, A, d_obs, H, S, E, HE, hypernet_layers;
     int32_t mixer; /* 0 none (IQL), 1 vdn, 2 qmix */
     int32_t double_q, obs_last_action, obs_agent_id;
     float gamma, lr, optim_alpha, optim_eps, grad_norm_clip;
     int32_t agent; /* 0 DRQN (rnn: everything above), 1 feed-forward (dqn): see above */
+    int32_t distinct; /* 0 one shared agent, 1 one DRQN per agent slot (mac: distinct): see above */
 } MlgLearnerCfg;
 
 typedef struct {
@@ -270,7 +285,8 @@ typedef struct {
     /* optional (NULL = off), folded into the same launches instead of separate copies / adds: */
     float *target_sync;          /* [n_agent + n_mixer] receives the updated parameters (the target update
                                     q_learner.py:127-128 when it is due after this step; usually target_params) */
-    double *trained_steps;       /* [1] += count_nonzero(mask) (Agent.trained_steps, q_learner.py:104) */
+    double *trained_steps;       /* [1] += count_nonzero(mask) (Agent.trained_steps, q_learner.py:104); distinct = 1:
+                                    [N], one per network, each += the same count */
     const int32_t *host_rows;    /* HOST copy of the slot map (B <= 64): travels as a kernel argument,
                                     batch.rows is then ignored */
 } MlgLearnerBufs;
@@ -288,7 +304,11 @@ int mlg_qlearner_train(const MlgLearnerCfg *c, const MlgLearnerBufs *b, void *st
  * tiles of agent_q_kernel). Mixer part: iql, vdn-fast / vdn and qmix-split / qmix-generic (default widths E = 32,
  * HE = 64: the prefetching forms up to N = 8, A = 16, S = 64 / the generic mix_td_kernel<64, 32>), qmix1-e{E} (one
  * hypernet layer), qmix-he{HE}-e{E} (the other widths). With agent = 1 the agent part is ff-h32 | ff-h64 | ff-h128 followed by /q1..q6,
- * and QMIX at the default widths runs qmix-generic (no recurrence launch carries the split form). Nonzero
+ * and QMIX at the default widths runs qmix-generic (no recurrence launch carries the split form). With distinct = 1
+ * the agent part is dx-h32 | dx-h64 | dx-h128 followed by /bwd-split/q1..q6 (the <H, true> forms of the agent kernels,
+ * prep_kernel<true> and the repeating weight-gradient kernels; the H = 64 fused backward is not carried over), e.g.
+ * "dx-h64/bwd-split/q1 + qmix-generic"; the mixer part is iql, vdn-fast / vdn, qmix-generic, qmix1-e{E} or
+ * qmix-he{HE}-e{E} (no qmix-split: the hypernet tiles ride in the shared agent's recurrence launch only). Nonzero
  * (mlg_last_error) where mlg_qlearner_train would refuse the cfg. */
 int mlg_qlearner_describe(const MlgLearnerCfg *c, char *name, int32_t name_cap);
 

@@ -155,6 +155,8 @@ struct Gru4Bwd {
     float *dgi, *dgh;              // [T][R][3H]
     int Tz = -1;                   // deltas of steps Te <= t < Tz are zeroed (< 0: up to T). The QMIX learner's weight
                                    // gradients skip the rows past a tile's steps, so it zeroes none (Tz = 0)
+    int dq_ld = 1;                 // dQ of row r at step t: dq[(t R + r) dq_ld] (distinct networks: the agents of an
+                                   // episode lie side by side in the mixer's rows, dq_ld = N, dq based at the agent)
 };
 
 // One 4-row tile of the reverse-time backward over Te steps (rows past Te zeroed up to Gru4Bwd::Tz: wgrad rows). Wave w owns
@@ -186,7 +188,7 @@ __device__ __forceinline__ void gru4_bwd(const Gru4Bwd& a, int tile, int Te, int
     const __amdgpu_buffer_rsrc_t rs_r = mlg_rsrc(a.gr), rs_z = mlg_rsrc(a.gz), rs_n = mlg_rsrc(a.gn),
                                  rs_hn = mlg_rsrc(a.ghn), rs_hs = mlg_rsrc(a.hs), rs_dq = mlg_rsrc(a.dq),
                                  rs_act = mlg_rsrc(reinterpret_cast<const float*>(a.actions));
-    const int vo_g = (rr * H + f) * 4, vo_dq = rr * 4, vo_act = (int)(abase * 8);
+    const int vo_g = (rr * H + f) * 4, vo_dq = rr * a.dq_ld * 4, vo_act = (int)(abase * 8);
     auto load_raw = [&](int t, Raw& s) {
         const int so = t * R * H * 4;
         s.rg = ld1_rs(rs_r, vo_g, so);
@@ -195,7 +197,7 @@ __device__ __forceinline__ void gru4_bwd(const Gru4Bwd& a, int tile, int Te, int
         s.ghn = ld1_rs(rs_hn, vo_g, so);
         s.hp = ld1_rs(rs_hs, vo_g, so);  // HS[t] = h_{t-1}
         const int tq = t < a.T - 1 ? t : a.T - 2;
-        s.dq = ld1_rs(rs_dq, vo_dq, tq * R * 4);
+        s.dq = ld1_rs(rs_dq, vo_dq, tq * R * a.dq_ld * 4);
         // 32-bit load of the action's low word (little-endian int64), unconditional: no branch around it, and no
         // dead high half whose pending load would block the reuse of its register
         const int act = __float_as_int(ld1_rs(rs_act, vo_act, tq * N * 8));

@@ -17,6 +17,8 @@
 // rows past the episode's last unmasked transition, and the whole target pass while the target parameters are a
 // bit copy of the online ones. MLG_LEARNER_FULL=1 (read per call) runs every row to max_t_filled and both nets.
 // Tensors saved for backward are t-major: [T][R][F] with R = B * N agent rows (r = b * N + n).
+// MlgLearnerCfg.distinct = 1 (one DRQN per agent slot): the agent kernels' <H, true> forms run N instances of the
+// N = 1, R = B problem by a grid coordinate (Distinct networks, below); the mixer side is unchanged.
 //
 // Mixers (MlgLearnerCfg.mixer / hypernet_layers; everything else is refused by check_cfg):
 //   0 none (IQL)   iql_td: td[b,t,n] = Q_chosen[b,t,n] - (r[b,t] + gamma (1 - term[b,t]) target[b,t+1,n]), the target
@@ -145,7 +147,28 @@ struct LCfg {
     float gamma;
     int full;  // MLG_LEARNER_FULL: no skipping
     int ff;    // MlgLearnerCfg.agent = 1: the feed-forward agent (no recurrence kernels, no GRU buffers)
+    int dx;    // MlgLearnerCfg.distinct = 1: one network per agent slot (Distinct networks, below)
 };
+
+// ---- Distinct networks (cfg.distinct = 1) ---------------------------------------------------------
+// The agent part of a call is N instances of the shared-agent problem with N = 1 and R = B rows: instance `ag` (a grid
+// coordinate of every agent kernel's <H, true> form) runs network ag on the rows of agent slot ag. Its packed weights,
+// W_ih^T and every agent-side workspace tensor ([T][B][F], rows r = b) lie at ag times a per-agent stride, all
+// multiples of four floats; the Skip tables and the agent row bitmap are those of one instance (l16 per tile of 16
+// episodes) and shared by all. The mixer side keeps its layout, rows r = b N + n: the instances meet it where they
+// read the batch (obs / last action of slot ag), where agent_q stores Q into mac / tmac, and where the reverse
+// recurrence and fc2's weight-gradient job read dq / d2 (row stride N). The mixer and TD kernels run unchanged.
+struct DxView {
+    int ag;                                  // network = agent slot
+    int64_t p, in, h, hs, g3;                // float offsets of instance ag: packed block, [T][B][d_in], [T][B][H],
+                                             // [T + 1][B][H], [T][B][3H] (agent_dx_kernel, which has no layout
+                                             // argument, forms its own: W_ih^T blocks are 3 H H apart)
+};
+__host__ __device__ inline int64_t dx_in_stride(const LCfg& c) { return mlg_align4((int64_t)c.T * c.B * c.d_in); }
+__device__ __forceinline__ DxView dx_view(const LCfg& c, const AgentLayout& L, int ag) {
+    const int64_t TB = (int64_t)c.T * c.B;
+    return DxView{ag, (int64_t)ag * L.gsp, ag * dx_in_stride(c), ag * TB * c.H, ag * (TB + c.B) * c.H, ag * TB * 3 * c.H};
+}
 
 // What a call skips, from prep_kernel (workspace; every kernel after it reads the same three):
 //   mlen[b]   1 + the last t < t_eff - 1 with mask(b, t) != 0: transition (b, t) is live iff t < mlen[b]; the dead
@@ -172,7 +195,7 @@ struct WsLayout {
     int64_t p_on, p_tg, wihT, mix_on, mix_tg;
     int64_t in, x, hs, hs_tg, gi_on, gi_tg, gr, gz, gn, ghn, mac, tmac, dq, d2, dgi, dgh, da;
     int64_t srow, l1act, d1, da2, df2, dv2, hyp_on, hyp_tg;
-    int64_t part, msum, rows, mlen, l16, flag, abits, mbits, nrm, slab, total;
+    int64_t part, msum, rows, mlen, l16, flag, alive, abits, mbits, nrm, slab, total;
     int n_mix_tiles, n_tasks, hyp_stride;
 };
 
@@ -259,6 +282,11 @@ struct PrepJob {
     int n_rows_in;          // > 0: the slot map travels here (host_rows); block 0 stores it to rows_dst
     int32_t* rows_dst;
     int32_t rows_in[MLG_INLINE_ROWS];
+    // distinct networks (prep_kernel<true>): nag networks of ao_total flat floats each, packed at strides of L.gsp
+    // (W_ih^T: 3 H H); R = B and N = 1 above (the tables of one instance); blocks 1 .. nag store alive[ag]
+    int nag, nslots, A;     // nslots = the batch's agents per episode
+    int64_t ao_total;
+    unsigned* alive;
 };
 static_assert(sizeof(PrepJob) <= 3072, "PrepJob must fit the kernel-argument segment");
 
@@ -267,7 +295,38 @@ __device__ __forceinline__ float prep_pack_agent(const PrepJob& J, const MlgAgen
     return pack_agent_elem(J.L, ap, k);
 }
 
+__device__ __forceinline__ MlgAgentParams shift_agent(const MlgAgentParams& p, int64_t o) {
+    return MlgAgentParams{p.fc1_w + o, p.fc1_b + o, p.w_ih + o, p.b_ih + o, p.w_hh + o, p.b_hh + o, p.fc2_w + o, p.fc2_b + o};
+}
+
+// DX: the distinct-network form. Dead-slot rule: slot ag is alive iff some stored step of the batch
+// (filled != 0, t < T) offers it an action other than action 0; block 1 + ag scans the slot's avail rows and stores
+// alive[ag] (every call, so the word needs no initial value). The weight-gradient reduce reads it.
+template <bool DX>
 __global__ void __launch_bounds__(1024) prep_kernel(PrepJob J) {
+    if constexpr (DX) {
+        if (blockIdx.x >= 1 && (int)blockIdx.x <= J.nag) {
+            __shared__ int32_t arows[MLG_INLINE_ROWS];
+            MlgBatch b2 = J.bt;
+            if (J.n_rows_in > 0) {
+                if (threadIdx.x < J.n_rows_in) arows[threadIdx.x] = J.rows_in[threadIdx.x];
+                __syncthreads();
+                b2.rows = arows;
+            }
+            const int ag = (int)blockIdx.x - 1;
+            int any = 0;
+            for (int i = threadIdx.x; i < J.B * J.T; i += blockDim.x) {
+                const int b = i / J.T, t = i - b * J.T;
+                const int64_t st = bslot(b2, b) * b2.T1 + t;
+                if (b2.filled[st] == 0) continue;
+                const int32_t* av = b2.avail + (st * J.nslots + ag) * J.A;
+                for (int a = 1; a < J.A; ++a) any |= av[a] != 0;
+            }
+            any = __syncthreads_or(any);
+            if (threadIdx.x == 0) J.alive[ag] = any ? 1u : 0u;
+            return;
+        }
+    }
     if (blockIdx.x == 0) {
         __shared__ int32_t srows[MLG_INLINE_ROWS];
         __shared__ mlg::MaskStatsLds ms;
@@ -333,20 +392,42 @@ __global__ void __launch_bounds__(1024) prep_kernel(PrepJob J) {
     }
     const int64_t na = J.ff ? J.L.total : J.L.gsp,  // the learner reads no pre-split rollout sections (gsp, w1s)
                    nt = (int64_t)J.rows3 * J.cols, nm = J.mixer == 2 ? J.mp.total : 0;
-    const int64_t total = 2 * na + nt + 2 * nm + J.n_d2 + J.n_dq + (J.n_cmp + 3) / 4;
-    for (int64_t i = (int64_t)(blockIdx.x - 1) * blockDim.x + threadIdx.x; i < total;
-         i += (int64_t)(gridDim.x - 1) * blockDim.x) {
+    const int nag = DX ? J.nag : 1, first = DX ? 1 + J.nag : 1;  // DX: blocks 1 .. nag scan the slots (above)
+    const int64_t total = 2 * na * nag + nt * nag + 2 * nm + J.n_d2 + J.n_dq + (J.n_cmp + 3) / 4;
+    for (int64_t i = (int64_t)(blockIdx.x - first) * blockDim.x + threadIdx.x; i < total;
+         i += (int64_t)(gridDim.x - first) * blockDim.x) {
         int64_t k = i;
-        if (k < na) { J.p_on[k] = prep_pack_agent(J, J.ap_on, k); continue; }
-        k -= na;
-        if (k < na) { J.p_tg[k] = prep_pack_agent(J, J.ap_tg, k); continue; }
-        k -= na;
-        if (k < nt) {  // wihT[c][r] = wih[r][c]
-            const int r = (int)(k / J.cols), c = (int)(k % J.cols);
-            J.wihT[(int64_t)c * J.rows3 + r] = J.wih[k];
-            continue;
+        if constexpr (DX) {  // network ag's blocks: element by element what the shared agent's block holds
+            if (k < 2 * na * nag) {
+                const bool on = k < na * nag;
+                if (!on) k -= na * nag;
+                const int ag = (int)(k / na);
+                k -= ag * na;
+                const MlgAgentParams ap = shift_agent(on ? J.ap_on : J.ap_tg, ag * J.ao_total);
+                (on ? J.p_on : J.p_tg)[ag * na + k] = pack_agent_elem(J.L, ap, k);
+                continue;
+            }
+            k -= 2 * na * nag;
+            if (k < nt * nag) {
+                const int ag = (int)(k / nt);
+                k -= ag * nt;
+                const int r = (int)(k / J.cols), c = (int)(k % J.cols);
+                J.wihT[ag * nt + (int64_t)c * J.rows3 + r] = J.wih[ag * J.ao_total + k];
+                continue;
+            }
+            k -= nt * nag;
+        } else {
+            if (k < na) { J.p_on[k] = prep_pack_agent(J, J.ap_on, k); continue; }
+            k -= na;
+            if (k < na) { J.p_tg[k] = prep_pack_agent(J, J.ap_tg, k); continue; }
+            k -= na;
+            if (k < nt) {  // wihT[c][r] = wih[r][c]
+                const int r = (int)(k / J.cols), c = (int)(k % J.cols);
+                J.wihT[(int64_t)c * J.rows3 + r] = J.wih[k];
+                continue;
+            }
+            k -= nt;
         }
-        k -= nt;
         if (k < nm) { J.mix_on[k] = pack_mixer_elem(J.mp, J.mo, J.mix_src_on, k, J.S, J.E, J.HE); continue; }
         k -= nm;
         if (k < nm) { J.mix_tg[k] = pack_mixer_elem(J.mp, J.mo, J.mix_src_tg, k, J.S, J.E, J.HE); continue; }
@@ -426,7 +507,8 @@ __device__ __forceinline__ floatx4 tile_mm_lds(const float* __restrict__ W, int6
 //   agent_q_kernel   (t, tile, net): q = fc2(h_t)
 // The accumulation order per output is the one of the fused unroll (bias, W_ih x chunks, W_hh h chunks).
 // grid (ntiles, T, 2), HC waves: wave w computes x chunk w, then GI chunks w, w + HC, w + 2 HC.
-template <int H>
+// DX (distinct networks): grid (ntiles, T, 2 N), z = 2 ag + net; instance ag's rows r = b are agent slot ag's.
+template <int H, bool DX = false>
 __global__ void __launch_bounds__(512) agent_in_kernel(LCfg c, MlgBatch bt, AgentLayout L, const float* __restrict__ Pon,
                                                        const float* __restrict__ Ptg, float* __restrict__ ws_in,
                                                        float* __restrict__ ws_x, float* __restrict__ gi_on,
@@ -436,16 +518,21 @@ __global__ void __launch_bounds__(512) agent_in_kernel(LCfg c, MlgBatch bt, Agen
     __shared__ __attribute__((aligned(16))) float xs[16 * LDA];
     const int tile = blockIdx.x, t = blockIdx.y;
     if (t >= tile_steps(sk, tile)) return;
-    const bool online = blockIdx.z == 0;
+    const bool online = DX ? (blockIdx.z & 1) == 0 : blockIdx.z == 0;
     if (!online && !target_runs(c, sk)) return;
+    const int ag = DX ? (int)(blockIdx.z >> 1) : 0;
+    if constexpr (DX) {
+        const DxView v = dx_view(c, L, ag);
+        Pon += v.p, Ptg += v.p, ws_in += v.in, ws_x += v.h, gi_on += v.g3, gi_tg += v.g3;
+    }
     const float* P = online ? Pon : Ptg;
     float* gi = online ? gi_on : gi_tg;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int col = lane & 15, g = lane >> 4;
-    const int N = c.N, A = c.A, R = c.R;
+    const int N = c.N, A = c.A, R = DX ? c.B : c.R;
     const int r = tile * 16 + col;
     const bool valid = r < R;
-    const int b = valid ? r / N : 0, n = valid ? r % N : 0;
+    const int b = valid ? (DX ? r : r / N) : 0, n = DX ? ag : (valid ? r % N : 0);
     const int64_t boff = (bslot(bt, b) * bt.T1 + t) * N + n;
     {
         floatx4 acc = ld4(P + L.b1 + w * 16 + 4 * g);
@@ -473,7 +560,7 @@ __global__ void __launch_bounds__(512) agent_in_kernel(LCfg c, MlgBatch bt, Agen
         for (int i = tid >> 4; i < 16; i += blockDim.x >> 4) {
             const int rr = tile * 16 + i;
             if (rr >= R) break;
-            const int bb = rr / N, nn = rr - bb * N;
+            const int bb = DX ? rr : rr / N, nn = DX ? ag : rr - bb * N;
             const int64_t bo = (bslot(bt, bb) * bt.T1 + t) * N + nn;
             float* dst = ws_in + ((int64_t)t * R + rr) * c.d_in;
             const float* src = bt.obs + bo * c.d_obs;
@@ -506,32 +593,40 @@ __device__ __forceinline__ void agent_rec4_body(const LCfg& c, const AgentLayout
                                                 const float* __restrict__ gi_tg, float* __restrict__ hs_on,
                                                 float* __restrict__ hs_tg, float* __restrict__ ws_gr,
                                                 float* __restrict__ ws_gz, float* __restrict__ ws_gn,
-                                                float* __restrict__ ws_ghn, const Skip& sk, int bid) {
-    const int nt4 = (c.R + 3) / 4;
+                                                float* __restrict__ ws_ghn, const Skip& sk, int bid, int R) {
+    const int nt4 = (R + 3) / 4;
     const bool online = bid < nt4;
     if (!online && !target_runs(c, sk)) return;
     LStamps lst;
     lst.init();
     const float* P = online ? Pon : Ptg;
-    const mlg::Gru4Fwd a{c.R, P + L.whh, P + L.bhh, online ? gi_on : gi_tg, online ? hs_on : hs_tg,
+    const mlg::Gru4Fwd a{R, P + L.whh, P + L.bhh, online ? gi_on : gi_tg, online ? hs_on : hs_tg,
                          ws_gr, ws_gz, ws_gn, ws_ghn, online};
     const int tile4 = online ? bid : bid - nt4;
     mlg::gru4_fwd<H>(a, tile4, tile_steps(sk, tile4 >> 2), lst);
     lst.flush(0);
 }
 
-template <int H>
+// DX (distinct networks): grid (2 * ntiles4 of one instance, N), y = ag.
+template <int H, bool DX = false>
 __global__ void __launch_bounds__(512) agent_rec4_kernel(LCfg c, AgentLayout L, const float* __restrict__ Pon,
                                                          const float* __restrict__ Ptg, const float* __restrict__ gi_on,
                                                          const float* __restrict__ gi_tg, float* __restrict__ hs_on,
                                                          float* __restrict__ hs_tg, float* __restrict__ ws_gr,
                                                          float* __restrict__ ws_gz, float* __restrict__ ws_gn,
                                                          float* __restrict__ ws_ghn, Skip sk) {
-    agent_rec4_body<H>(c, L, Pon, Ptg, gi_on, gi_tg, hs_on, hs_tg, ws_gr, ws_gz, ws_gn, ws_ghn, sk, blockIdx.x);
+    if constexpr (DX) {
+        const DxView v = dx_view(c, L, blockIdx.y);
+        agent_rec4_body<H>(c, L, Pon + v.p, Ptg + v.p, gi_on + v.g3, gi_tg + v.g3, hs_on + v.hs, hs_tg + v.hs,
+                           ws_gr + v.h, ws_gz + v.h, ws_gn + v.h, ws_ghn + v.h, sk, blockIdx.x, c.B);
+    } else {
+        agent_rec4_body<H>(c, L, Pon, Ptg, gi_on, gi_tg, hs_on, hs_tg, ws_gr, ws_gz, ws_gn, ws_ghn, sk, blockIdx.x, c.R);
+    }
 }
 
 // grid (ntiles, T, 2), Ap/16 waves: wave = action tile. q = b2 + W2 . h_t (h_t = HS[t + 1]).
-template <int H>
+// DX (distinct networks): grid (ntiles, T, 2 N), z = 2 ag + net; instance row r = b stores to the mixer's row b N + ag.
+template <int H, bool DX = false>
 __global__ void __launch_bounds__(512) agent_q_kernel(LCfg c, AgentLayout L, const float* __restrict__ Pon,
                                                       const float* __restrict__ Ptg, const float* __restrict__ hs_on,
                                                       const float* __restrict__ hs_tg, float* __restrict__ mac,
@@ -539,25 +634,32 @@ __global__ void __launch_bounds__(512) agent_q_kernel(LCfg c, AgentLayout L, con
     constexpr int HC = H / 16;
     const int tile = blockIdx.x, t = blockIdx.y;
     if (t >= tile_steps(sk, tile)) return;
-    const bool online = blockIdx.z == 0;
+    const bool online = DX ? (blockIdx.z & 1) == 0 : blockIdx.z == 0;
     if (!online && !target_runs(c, sk)) return;
+    const int ag = DX ? (int)(blockIdx.z >> 1) : 0;
+    if constexpr (DX) {
+        const DxView v = dx_view(c, L, ag);
+        Pon += v.p, Ptg += v.p, hs_on += v.hs, hs_tg += v.hs;
+    }
+    const int R = DX ? c.B : c.R;
     const float* P = online ? Pon : Ptg;
-    const float* hsg = (online ? hs_on : hs_tg) + (int64_t)(t + 1) * c.R * H;
+    const float* hsg = (online ? hs_on : hs_tg) + (int64_t)(t + 1) * R * H;
     float* qout = online ? mac : tmac;
     const int lane = threadIdx.x & 63, at = threadIdx.x >> 6;
     const int col = lane & 15, g = lane >> 4;
     const int r = tile * 16 + col;
-    const bool valid = r < c.R;
+    const bool valid = r < R;
     const float* hrow = hsg + (int64_t)(valid ? r : 0) * H + 4 * g;
     const float* wrow = P + L.w2 + (int64_t)(at * 16 + col) * H + 4 * g;
     floatx4 q = ld4(P + L.b2 + at * 16 + 4 * g);
 #pragma unroll
     for (int kc = 0; kc < HC; ++kc) q = mfma_chunk(ld4(wrow + kc * 16), ld4(hrow + kc * 16), q);
     if (valid) {
+        const int64_t qrow = DX ? (int64_t)t * c.R + r * c.N + ag : (int64_t)t * c.R + r;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int a = at * 16 + 4 * g + k;
-            if (a < c.A) qout[((int64_t)t * c.R + r) * c.A + a] = q[k];
+            if (a < c.A) qout[qrow * c.A + a] = q[k];
         }
     }
 }
@@ -1637,7 +1739,7 @@ __global__ void __launch_bounds__(512) rec4_mixpre_kernel(LCfg c, AgentLayout L,
                                                           MlgBatch bt, MixPtrs Mon, MixPtrs Mtg, MixPack mp, HypOut o) {
     const int nrec = 2 * ((c.R + 3) / 4);
     if ((int)blockIdx.x < nrec) {
-        agent_rec4_body<H>(c, L, Pon, Ptg, gi_on, gi_tg, hs_on, hs_tg, ws_gr, ws_gz, ws_gn, ws_ghn, sk, blockIdx.x);
+        agent_rec4_body<H>(c, L, Pon, Ptg, gi_on, gi_tg, hs_on, hs_tg, ws_gr, ws_gz, ws_gn, ws_ghn, sk, blockIdx.x, c.R);
         return;
     }
     const int w = threadIdx.x >> 6, per = blockDim.x / 128;
@@ -1861,7 +1963,8 @@ __global__ void __launch_bounds__(128) mix_td2_kernel(LCfg c, MlgBatch bt, MixPt
 // 16-lane rows with a transposing reduction (rows_sum_transpose4): lane (row kq, fg, j) ends up owning feature
 // 16w + 4fg + kq of row j, so all 64 lanes run the elementwise GRU backward, one (feature, row) each.
 // grid (ntiles4), H/16 waves.
-template <int H>
+// DX (distinct networks): grid (ntiles4 of one instance, N), y = ag; dQ of instance row r = b is the mixer's row b N + ag.
+template <int H, bool DX = false>
 __global__ void __launch_bounds__(512) agent_bwd4_kernel(LCfg c, MlgBatch bt, AgentLayout L, const float* __restrict__ P,
                                                          const float* __restrict__ ws_hs, const float* __restrict__ ws_gr,
                                                          const float* __restrict__ ws_gz, const float* __restrict__ ws_gn,
@@ -1869,13 +1972,25 @@ __global__ void __launch_bounds__(512) agent_bwd4_kernel(LCfg c, MlgBatch bt, Ag
                                                          float* __restrict__ dgi, float* __restrict__ dgh, Skip sk) {
     LStamps lst;
     lst.init();
-    const int r = blockIdx.x * 4 + ((threadIdx.x & 63) & 3);
-    const bool valid = r < c.R;
-    const int b = valid ? r / c.N : 0, n = valid ? r % c.N : 0;
-    const mlg::Gru4Bwd a{c.R, c.T, c.A, c.N, P + L.whh, P + L.w2, ws_hs, ws_gr, ws_gz, ws_gn, ws_ghn, dqv,
-                         bt.actions, dgi, dgh, 0};  // no zeroed tail: the weight gradients skip those rows
-    mlg::gru4_bwd<H>(a, blockIdx.x, tile_steps(sk, blockIdx.x >> 2), bslot(bt, b) * bt.T1 * c.N + n, lst);
-    lst.flush(1);
+    if constexpr (DX) {
+        const int ag = blockIdx.y;
+        const DxView v = dx_view(c, L, ag);
+        P += v.p;
+        const int r = blockIdx.x * 4 + ((threadIdx.x & 63) & 3);
+        const int b = r < c.B ? r : 0;
+        const mlg::Gru4Bwd a{c.B, c.T, c.A, c.N, P + L.whh, P + L.w2, ws_hs + v.hs, ws_gr + v.h, ws_gz + v.h, ws_gn + v.h,
+                             ws_ghn + v.h, dqv + ag, bt.actions, dgi + v.g3, dgh + v.g3, 0, c.N};
+        mlg::gru4_bwd<H>(a, blockIdx.x, tile_steps(sk, blockIdx.x >> 2), bslot(bt, b) * bt.T1 * c.N + ag, lst);
+        lst.flush(1);
+    } else {
+        const int r = blockIdx.x * 4 + ((threadIdx.x & 63) & 3);
+        const bool valid = r < c.R;
+        const int b = valid ? r / c.N : 0, n = valid ? r % c.N : 0;
+        const mlg::Gru4Bwd a{c.R, c.T, c.A, c.N, P + L.whh, P + L.w2, ws_hs, ws_gr, ws_gz, ws_gn, ws_ghn, dqv,
+                             bt.actions, dgi, dgh, 0};  // no zeroed tail: the weight gradients skip those rows
+        mlg::gru4_bwd<H>(a, blockIdx.x, tile_steps(sk, blockIdx.x >> 2), bslot(bt, b) * bt.T1 * c.N + n, lst);
+        lst.flush(1);
+    }
 }
 
 // The reverse recurrence (blocks < nbwd, H = 64: 4 waves each) and, as the launch's remaining workgroups, the weight
@@ -1906,17 +2021,23 @@ __global__ void __launch_bounds__(256, 2) bwd4_wgrad_kernel(LCfg c, MlgBatch bt,
 }
 
 // dA = (W_ih^T dGI) * (x > 0) for every (t, row): grid (ntiles, T), HC waves (wave = feature chunk).
-template <int H>
+// DX (distinct networks): grid (ntiles, T, N), z = ag.
+template <int H, bool DX = false>
 __global__ void __launch_bounds__(512) agent_dx_kernel(LCfg c, const float* __restrict__ wihT,
                                                        const float* __restrict__ ws_x, const float* __restrict__ dgi,
                                                        float* __restrict__ da, Skip sk) {
     const int tile = blockIdx.x, t = blockIdx.y;
     if (t >= tile_steps(sk, tile)) return;  // the fc1 weight gradient skips the block's rows
+    if constexpr (DX) {
+        const int64_t TB = (int64_t)c.T * c.B, ag = blockIdx.z;
+        wihT += ag * 3 * H * H, ws_x += ag * TB * H, dgi += ag * TB * 3 * H, da += ag * TB * H;
+    }
+    const int R = DX ? c.B : c.R;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int col = lane & 15, g = lane >> 4;
     const int r = tile * 16 + col;
-    const bool valid = r < c.R;
-    const int64_t row = (int64_t)t * c.R + (valid ? r : 0);
+    const bool valid = r < R;
+    const int64_t row = (int64_t)t * R + (valid ? r : 0);
     const float* wrow = wihT + (int64_t)(w * 16 + col) * 3 * H + 4 * g;
     const float* grow = dgi + row * 3 * H + 4 * g;
     const int64_t o = row * H + w * 16 + 4 * g;
@@ -1941,7 +2062,9 @@ __global__ void __launch_bounds__(1024) finish_kernel(const float* __restrict__ 
                                                       float lr, float alpha, float eps, float max_norm, int N,
                                                       float* __restrict__ stats, const float* __restrict__ nrm_part,
                                                       int n_nrm, float* __restrict__ tsync, double* __restrict__ trained,
-                                                      Skip sk, unsigned* __restrict__ flag, int ntiles, int full) {
+                                                      Skip sk, unsigned* __restrict__ flag, int ntiles, int full,
+                                                      int nets) {  // distinct networks: N instances ran the tiles, and
+                                                                   // trained[0 .. N - 1] count (1 otherwise)
     __shared__ float red[1024];
     const int tid = threadIdx.x;
     // the planned forward blocks (stats[7]: exact integers, any order) and the flag, requested ahead of the step
@@ -1975,9 +2098,11 @@ __global__ void __launch_bounds__(1024) finish_kernel(const float* __restrict__ 
         stats[1] = norm;
         stats[5] = ms;
         stats[6] = ms;
+        blocks *= (float)nets;
         stats[7] = (full || fl == 1u) ? 2.f * blocks : blocks;  // forward (16-row tile, t, net) blocks of this call
         *flag = 0u;  // the next call's prep_kernel stores 1 where its target differs
-        if (trained) trained[0] += (double)ms;  // Agent.trained_steps (q_learner.py:104)
+        if (trained)
+            for (int k = 0; k < nets; ++k) trained[k] += (double)ms;  // Agent.trained_steps (q_learner.py:104)
     }
 }
 
@@ -2005,6 +2130,14 @@ int check_cfg(const MlgLearnerCfg* c) {
                 (long long)c->T * c->B * c->N * 3 * c->H);
     MLG_REQUIRE(c->mixer >= 0 && c->mixer <= 2, "learner: mixer=%d unsupported (0 none, 1 vdn, 2 qmix)", c->mixer);
     MLG_REQUIRE(c->agent == 0 || c->agent == 1, "learner: agent=%d unsupported (0 rnn: DRQN, 1 dqn: feed-forward)", c->agent);
+    MLG_REQUIRE(c->distinct == 0 || c->distinct == 1, "learner: distinct=%d unsupported (0 shared agent, 1 one DRQN per slot)",
+                c->distinct);
+    if (c->distinct) {
+        MLG_REQUIRE(c->agent == 0, "learner: agent=%d with distinct=1 unsupported (distinct networks are DRQNs, agent=0)",
+                    c->agent);
+        MLG_REQUIRE(!c->obs_agent_id, "learner: obs_agent_id=%d with distinct=1 unsupported (a slot's network is its id)",
+                    c->obs_agent_id);
+    }
     if (c->mixer == 2) {
         MLG_REQUIRE(c->hypernet_layers == 1 || c->hypernet_layers == 2, "learner: qmix hypernet_layers=%d unsupported (1, 2)",
                     c->hypernet_layers);
@@ -2040,13 +2173,14 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
     c.gamma = cfg->gamma;
     c.full = getenv("MLG_LEARNER_FULL") != nullptr;  // read per call, so a test can set it
     c.ff = cfg->agent == 1;
+    c.dx = cfg->distinct == 1;
     p.layers = cfg->mixer == 2 ? cfg->hypernet_layers : 2;
     MlgAgentDims d{cfg->d_obs, cfg->A, cfg->N, cfg->H, c.d_in, cfg->obs_last_action, cfg->obs_agent_id};
     p.L = c.ff ? make_ff_layout(d) : make_agent_layout(d);
     p.ao = c.ff ? ff_offs(c.H, c.d_in, c.A) : agent_offs(c.H, c.d_in, c.A);
     p.mo = mix_offs(c.N, c.S, c.E, c.HE, p.layers);
     p.mp = mix_pack(c.N, c.S, c.E, c.HE, p.layers);
-    p.n_agent = p.ao.total;
+    p.n_agent = c.dx ? c.N * p.ao.total : p.ao.total;  // distinct: [agent 0 | ... | agent N - 1], then the mixer
     p.n_mixer = c.mixer == 2 ? p.mo.total : 0;
     WsLayout& w = p.w;
     const int64_t T = c.T, R = c.R, H = c.H, RM = c.RM;
@@ -2054,13 +2188,15 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
     const int L1 = one ? 2 * c.E : 2 * c.HE + 2 * c.E;
     int64_t o = 0;
     auto take = [&](int64_t n) { int64_t r = o; o += a4(n); return r; };
-    w.p_on = take(p.L.total);
-    w.p_tg = take(p.L.total);
+    // distinct networks: N blocks at DxView's strides. The [T][R][F] tensors below hold N instances of [T][B][F]
+    // back to back, which is their size with R = B N
+    w.p_on = take(c.dx ? (int64_t)c.N * p.L.gsp : p.L.total);
+    w.p_tg = take(c.dx ? (int64_t)c.N * p.L.gsp : p.L.total);
     const int64_t G = c.ff ? 0 : 1;  // the feed-forward layout has no W_ih^T, gate, GI or gate-delta buffers
-    w.wihT = take(G * 3 * H * H);
+    w.wihT = take(G * 3 * H * H * (c.dx ? c.N : 1));
     w.mix_on = take(p.mp.total);
     w.mix_tg = take(p.mp.total);
-    w.in = take(T * R * c.d_in);
+    w.in = take(c.dx ? c.N * dx_in_stride(c) : T * R * c.d_in);
     w.x = take(G * T * R * H);
     // feed-forward: row block t + 1 holds relu(fc1) of step t (what agent_q_kernel reads); block 0 is never touched
     w.hs = take((T + 1) * R * H);
@@ -2094,6 +2230,7 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
     w.mlen = take(c.B);
     w.l16 = take((R + 15) / 16);
     w.flag = take(4);
+    w.alive = take(c.dx ? c.N : 0);  // distinct networks: a word per slot (prep_kernel<true>)
     w.abits = take((T * R + 31) / 32);
     w.mbits = take((RM + 31) / 32);
     w.nrm = 0;  // placed after the slab (size known once the jobs are built)
@@ -2104,13 +2241,18 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
 
 
 // builds the job list; with ws == nullptr only sizes are computed (pointers are offsets from 0)
-WJobs make_jobs(Plan& p, float* ws, float* grads, int64_t* slab_floats, int* n_tasks, int64_t* n_red) {
+// distinct networks (rp != nullptr, filled here): the four agent jobs are those of one instance (T B rows, network 0's
+// operands and gradient tensors) and repeat N times at the instances' strides (mlg::BRepeat); fc2's deltas are the
+// mixer's d2 rows of the slot, N A floats apart
+WJobs make_jobs(Plan& p, float* ws, float* grads, int64_t* slab_floats, int* n_tasks, int64_t* n_red,
+                mlg::BRepeat* rp) {
     const LCfg& c = p.c;
     float* W = ws ? ws : nullptr;
     auto at = [&](int64_t off) { return W ? W + off : (float*)nullptr; };
     float* G = grads;
     auto gp = [&](int64_t off) { return G ? G + off : (float*)nullptr; };
-    const int TR = c.T * c.R, H = c.H, L1 = 2 * c.HE + 2 * c.E, RM = c.RM;
+    const int TR = c.T * (c.dx ? c.B : c.R), H = c.H, L1 = 2 * c.HE + 2 * c.E, RM = c.RM;
+    const int Ra = c.dx ? c.B : c.R;  // agent rows per step of an instance
     WJobs J;
     J.n = 0;
     const AgentOffs& a = p.ao;
@@ -2119,9 +2261,27 @@ WJobs make_jobs(Plan& p, float* ws, float* grads, int64_t* slab_floats, int* n_t
         J.j[J.n++] = mlg::bjob(at(p.w.dgi), 3 * H, at(p.w.x), H, gp(a.wih), gp(a.bih), 3 * H, H, TR);
         J.j[J.n++] = mlg::bjob(at(p.w.dgh), 3 * H, at(p.w.hs), H, gp(a.whh), gp(a.bhh), 3 * H, H, TR);
     }
-    J.j[J.n++] = mlg::bjob(at(p.w.d2), c.A, at(p.w.hs) ? at(p.w.hs) + (int64_t)c.R * H : nullptr, H, gp(a.fc2w), gp(a.fc2b),
-                     c.A, H, TR);
+    J.j[J.n++] = mlg::bjob(at(p.w.d2), c.dx ? (int64_t)c.N * c.A : c.A,
+                           at(p.w.hs) ? at(p.w.hs) + (int64_t)Ra * H : nullptr, H, gp(a.fc2w), gp(a.fc2b), c.A, H, TR);
     const int n_agent_jobs = J.n;
+    if (c.dx) {
+        static_assert(mlg::MLG_BREP_JOBS >= 4, "the four agent jobs repeat");
+        const int64_t TB = (int64_t)c.T * c.B;
+        rp->rep = c.N;
+        rp->nj = n_agent_jobs;
+        rp->sg = a.total;
+        rp->alive = reinterpret_cast<const unsigned*>(at(p.w.alive));
+        const int64_t sd[4] = {TB * H, TB * 3 * H, TB * 3 * H, c.A};  // dA, dGI, dGH, d2 of the next slot
+        const int64_t sx[4] = {dx_in_stride(c), TB * H, (TB + c.B) * H, (TB + c.B) * H};  // inputs, x, HS, HS[1..]
+        for (int q = 0; q < 4; ++q) {
+            rp->sd[q] = sd[q];
+            rp->sx[q] = sx[q];
+            J.j[q].va = J.j[q].va && sd[q] % 4 == 0;  // every repeat's rows readable as 16-byte vectors
+            J.j[q].vb = J.j[q].vb && sx[q] % 4 == 0;
+        }
+        // a 16-byte load of fc2's delta columns past A would read the next slot's: element loads, guarded by M
+        if (c.N > 1) J.j[3].va = 0;
+    }
     if (c.mixer == 2 && p.layers == 1) {  // every delta against the state row; V.2 against V's hidden activations
         const MixOffs& m = p.mo;
         const int64_t G0 = p.n_agent;
@@ -2156,7 +2316,7 @@ WJobs make_jobs(Plan& p, float* ws, float* grads, int64_t* slab_floats, int* n_t
         J.j[q] = mlg::bjob_row_bits(J.j[q], reinterpret_cast<const uint32_t*>(bits));
     }
     int64_t slab_part;
-    *slab_floats = mlg::layout_bjobs(J, n_tasks, n_red, &slab_part);  // slab partials + per-block norm partials
+    *slab_floats = mlg::layout_bjobs(J, n_tasks, n_red, &slab_part, c.dx ? rp : nullptr);  // slab + per-block norm partials
     p.w.nrm = p.w.slab + slab_part;
     return J;
 }
@@ -2193,11 +2353,15 @@ int make_dispatch(const Plan& p, Dispatch* out) {
     d.fast_mix = d.dflt_mix && p.mp.Sp <= 64 && c.N <= MIXPF_N && c.A <= MIXPF_A && !getenv("MLG_MIX_GENERIC");
     // feed-forward: no recurrence launch for the hypernet forward to ride in, so QMIX runs its one-kernel generic form
     if (c.ff && c.mixer == 2) d.fast_mix = false;
+    // distinct networks: the split form's hypernet tiles ride in the shared agent's recurrence launch and the fused
+    // backward carries the shared agent's job views; neither is carried over (QMIX runs its one-kernel generic form,
+    // the weight gradients one launch after agent_dx). The mixer kernels themselves are the shared agent's.
+    if (c.dx && c.mixer == 2) d.fast_mix = false;
     d.threads = (c.H / 16) * 64;
     d.split_mix = c.mixer == 2 && d.fast_mix && d.threads % 128 == 0;
     d.per = d.threads / 128;
     d.q_tiles = c.Ap / 16;
-    d.fused = !c.ff && Dispatch::fused_for(c.H);
+    d.fused = !c.ff && !c.dx && Dispatch::fused_for(c.H);
     if (c.mixer == 0) {
         d.mix = MIX_IQL;
     } else if (d.split_mix) {
@@ -2231,22 +2395,27 @@ void dispatch_name(const LCfg& c, const Dispatch& d, char* name, size_t cap) {
         case MIX_QMIX_WIDTHS: snprintf(mix, sizeof mix, "qmix-he%d-e%d", c.HE, c.E); break;
     }
     if (c.ff) snprintf(name, cap, "ff-h%d/q%d + %s", c.H, d.q_tiles, mix);
+    else if (c.dx) snprintf(name, cap, "dx-h%d/bwd-split/q%d + %s", c.H, d.q_tiles, mix);
     else snprintf(name, cap, "h%d/%s/q%d + %s", c.H, d.fused ? "bwd-fused" : "bwd-split", d.q_tiles, mix);
 }
 
 // the one reduce over the job table, then clip + RMSprop + statistics (both agents end a call the same way)
 int run_finish(const Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hipStream_t s, const WJobs& J,
-               int64_t n_red, unsigned* flag, const Skip& sk, int ntiles) {
+               int64_t n_red, unsigned* flag, const Skip& sk, int ntiles, const mlg::BRepeat* rp = nullptr) {
     const LCfg& c = p.c;
     float* ws = bufs->workspace;
     const int n_red_blocks = (int)((n_red + 255) / 256);
-    hipLaunchKernelGGL(mlg::wgrad_block_reduce_kernel<16>, dim3((unsigned)n_red_blocks), dim3(256), 0, s, J,
-                       ws + p.w.slab, ws + p.w.nrm);
+    if (rp)
+        hipLaunchKernelGGL(mlg::wgrad_block_reduce_rep_kernel<16>, dim3((unsigned)n_red_blocks), dim3(256), 0, s, J, *rp,
+                           ws + p.w.slab, ws + p.w.nrm);
+    else
+        hipLaunchKernelGGL(mlg::wgrad_block_reduce_kernel<16>, dim3((unsigned)n_red_blocks), dim3(256), 0, s, J,
+                           ws + p.w.slab, ws + p.w.nrm);
     const int64_t n_par = p.n_agent + p.n_mixer;
     hipLaunchKernelGGL(finish_kernel, dim3((unsigned)((n_par + 1023) / 1024)), dim3(1024), 0, s, ws + p.w.part,
                        p.w.n_mix_tiles, ws + p.w.msum + (c.mixer == 0 ? 2 : 0), bufs->params, bufs->grads, bufs->square_avg, n_par, cfg->lr,
                        cfg->optim_alpha, cfg->optim_eps, cfg->grad_norm_clip, c.N, bufs->stats, ws + p.w.nrm,
-                       n_red_blocks, bufs->target_sync, bufs->trained_steps, sk, flag, ntiles, c.full);
+                       n_red_blocks, bufs->target_sync, bufs->trained_steps, sk, flag, ntiles, c.full, c.dx ? c.N : 1);
     return mlg::check_launch("qlearner_train");
 }
 
@@ -2283,7 +2452,12 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     pj.mix_src_tg = tparams + p.n_agent;
     pj.mix_on = ws + p.w.mix_on;
     pj.mix_tg = ws + p.w.mix_tg;
-    pj.N = c.N;
+    pj.N = c.dx ? 1 : c.N;  // distinct networks: the Skip tables of one instance (R = B rows, one agent each)
+    pj.nag = c.dx ? c.N : 1;
+    pj.nslots = c.N;
+    pj.A = c.A;
+    pj.ao_total = p.ao.total;
+    pj.alive = reinterpret_cast<unsigned*>(ws + p.w.alive);
     pj.S = c.S;
     pj.E = c.E;
     pj.HE = c.HE;
@@ -2307,7 +2481,7 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     pj.cmp_tg = tparams;
     pj.n_cmp = p.n_agent + p.n_mixer;
     pj.cmp_vec = ((uintptr_t)params % 16 == 0) && ((uintptr_t)tparams % 16 == 0);
-    pj.R = c.R;
+    pj.R = c.dx ? c.B : c.R;
     pj.full = c.full;
     const Skip sk{pj.mlen, pj.l16, pj.flag};
     pj.n_rows_in = 0;
@@ -2316,11 +2490,16 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
         pj.n_rows_in = c.B;
         for (int b = 0; b < c.B; ++b) pj.rows_in[b] = bufs->host_rows[b];
     }
-    {
+    if (c.dx) {  // block 0 the tables, blocks 1 .. N the slots' liveness, the others the N networks' packs and the rest
+        const int64_t work = c.N * (2 * (int64_t)p.L.gsp + (int64_t)pj.rows3 * c.H) + (c.mixer == 2 ? 2 * p.mp.total : 0) +
+                             pj.n_d2 + pj.n_dq + (pj.n_cmp + 3) / 4;
+        const int blocks = 1 + c.N + (int)std::min<int64_t>((work + 1023) / 1024, 512);
+        hipLaunchKernelGGL(prep_kernel<true>, dim3(blocks), dim3(1024), 0, s, pj);
+    } else {
         const int64_t work = 2 * p.L.total + (int64_t)pj.rows3 * c.H + (c.mixer == 2 ? 2 * p.mp.total : 0) + pj.n_d2 +
                              pj.n_dq + (pj.n_cmp + 3) / 4;
         const int blocks = 1 + (int)std::min<int64_t>((work + 1023) / 1024, 512);
-        hipLaunchKernelGGL(prep_kernel, dim3(blocks), dim3(1024), 0, s, pj);
+        hipLaunchKernelGGL(prep_kernel<false>, dim3(blocks), dim3(1024), 0, s, pj);
     }
     MixPtrs Mon{}, Mtg{};
     if (c.mixer == 2) {
@@ -2342,16 +2521,25 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
         Mon = ptrs(params, ws + p.w.mix_on);
         Mtg = ptrs(tparams, ws + p.w.mix_tg);
     }
-    const int ntiles = (c.R + 15) / 16;
+    const int Ra = c.dx ? c.B : c.R;  // agent rows of an instance (distinct networks: N instances, a grid coordinate)
+    const int ntiles = (Ra + 15) / 16;
     HypOut hy{ws + p.w.hyp_on, ws + p.w.hyp_tg, ws + p.w.l1act, ws + p.w.srow, p.w.hyp_stride};
-    if (c.ff)
+    if (c.dx) {
+        hipLaunchKernelGGL((agent_in_kernel<H, true>), dim3(ntiles, c.T, 2 * c.N), dim3(threads), 0, s, c, bt, p.L,
+                           ws + p.w.p_on, ws + p.w.p_tg, ws + p.w.in, ws + p.w.x, ws + p.w.gi_on, ws + p.w.gi_tg, sk);
+        hipLaunchKernelGGL((agent_rec4_kernel<H, true>), dim3(2 * ((Ra + 3) / 4), c.N), dim3(threads), 0, s, c, p.L,
+                           ws + p.w.p_on, ws + p.w.p_tg, ws + p.w.gi_on, ws + p.w.gi_tg, ws + p.w.hs, ws + p.w.hs_tg,
+                           ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, sk);
+        hipLaunchKernelGGL((agent_q_kernel<H, true>), dim3(ntiles, c.T, 2 * c.N), dim3(64 * dsp.q_tiles), 0, s, c, p.L,
+                           ws + p.w.p_on, ws + p.w.p_tg, ws + p.w.hs, ws + p.w.hs_tg, ws + p.w.mac, ws + p.w.tmac, sk);
+    } else if (c.ff)
         hipLaunchKernelGGL((ff_hidden_kernel<H>), dim3(ntiles, c.T, 2), dim3(threads), 0, s, c, bt, p.L, ws + p.w.p_on,
                            ws + p.w.p_tg, ws + p.w.in, ws + p.w.hs, ws + p.w.hs_tg, sk);
     else
         hipLaunchKernelGGL((agent_in_kernel<H>), dim3(ntiles, c.T, 2), dim3(threads), 0, s, c, bt, p.L, ws + p.w.p_on,
                            ws + p.w.p_tg, ws + p.w.in, ws + p.w.x, ws + p.w.gi_on, ws + p.w.gi_tg, sk);
-    if (c.ff) {
-        // no recurrence: the hidden rows are complete
+    if (c.ff || c.dx) {
+        // feed-forward: no recurrence, the hidden rows are complete; distinct networks: launched above
     } else if (split_mix) {
         const int nrec = 2 * ((c.R + 3) / 4), per = dsp.per;
         hipLaunchKernelGGL((rec4_mixpre_kernel<H>), dim3(nrec + (p.w.n_mix_tiles + per - 1) / per), dim3(threads), 0, s,
@@ -2362,8 +2550,9 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
         hipLaunchKernelGGL((agent_rec4_kernel<H>), dim3(2 * ((c.R + 3) / 4)), dim3(threads), 0, s, c, p.L,
                            ws + p.w.p_on, ws + p.w.p_tg, ws + p.w.gi_on, ws + p.w.gi_tg, ws + p.w.hs, ws + p.w.hs_tg,
                            ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, sk);
-    hipLaunchKernelGGL((agent_q_kernel<H>), dim3(ntiles, c.T, 2), dim3(64 * dsp.q_tiles), 0, s, c, p.L, ws + p.w.p_on,
-                       ws + p.w.p_tg, ws + p.w.hs, ws + p.w.hs_tg, ws + p.w.mac, ws + p.w.tmac, sk);
+    if (!c.dx)
+        hipLaunchKernelGGL((agent_q_kernel<H>), dim3(ntiles, c.T, 2), dim3(64 * dsp.q_tiles), 0, s, c, p.L, ws + p.w.p_on,
+                           ws + p.w.p_tg, ws + p.w.hs, ws + p.w.hs_tg, ws + p.w.mac, ws + p.w.tmac, sk);
     MixOut mo{ws + p.w.srow, ws + p.w.l1act, ws + p.w.d1, ws + p.w.da2, ws + p.w.df2, ws + p.w.dv2,
               ws + p.w.dq, ws + p.w.d2, ws + p.w.part};
 #define MLG_MIX_LAUNCH(K)                                                                                       \
@@ -2407,7 +2596,20 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
     // agent_dx; one reduce over the whole table
     int64_t slab_floats, n_red;
     int n_tasks;
-    WJobs J = make_jobs(p, ws, bufs->grads, &slab_floats, &n_tasks, &n_red);
+    mlg::BRepeat rp{};
+    WJobs J = make_jobs(p, ws, bufs->grads, &slab_floats, &n_tasks, &n_red, &rp);
+    if (c.dx) {
+        // distinct networks: the N reverse recurrences and dX passes by grid coordinate, then every job in one launch
+        // (the agent jobs repeat per network) and the one reduce, which zeroes a dead slot's network
+        hipLaunchKernelGGL((agent_bwd4_kernel<H, true>), dim3((Ra + 3) / 4, c.N), dim3(threads), 0, s, c, bt, p.L,
+                           ws + p.w.p_on, ws + p.w.hs, ws + p.w.gr, ws + p.w.gz, ws + p.w.gn, ws + p.w.ghn, ws + p.w.dq,
+                           ws + p.w.dgi, ws + p.w.dgh, sk);
+        hipLaunchKernelGGL((agent_dx_kernel<H, true>), dim3(ntiles, c.T, c.N), dim3(threads), 0, s, c, ws + p.w.wihT,
+                           ws + p.w.x, ws + p.w.dgi, ws + p.w.da, sk);
+        hipLaunchKernelGGL(mlg::wgrad_block_rep_kernel<16>, dim3((unsigned)((n_tasks + 3) / 4)), dim3(256), 0, s, J, rp,
+                           ws + p.w.slab);
+        return run_finish(p, cfg, bufs, s, J, n_red, pj.flag, sk, ntiles, &rp);
+    }
     if (c.ff) {
         // feed-forward: the fc1 delta rows, then every job in one launch and the one reduce
         hipLaunchKernelGGL((ff_bwd_kernel<H>), dim3(ntiles, c.T), dim3(threads), 0, s, c, p.L, ws + p.w.p_on, ws + p.w.hs,
@@ -2469,7 +2671,8 @@ extern "C" int64_t mlg_qlearner_workspace_floats(const MlgLearnerCfg* c) {
     Plan p = make_plan(c, c->T);
     int64_t slab, n_red;
     int tasks;
-    make_jobs(p, nullptr, nullptr, &slab, &tasks, &n_red);
+    mlg::BRepeat rp{};
+    make_jobs(p, nullptr, nullptr, &slab, &tasks, &n_red, &rp);
     return p.w.total + slab;
 }
 

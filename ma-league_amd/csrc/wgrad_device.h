@@ -65,6 +65,19 @@ struct BJobsT {
     int n;
 };
 
+// Repeated jobs (the QMIX learner with distinct per-agent networks): jobs [0, nj) of a table run `rep` times, repeat a
+// on operands shifted by a sd[q] (delta) and a sx[q] (x) floats, into dw / db shifted by a sg; the other jobs run once.
+// A repeat is a job of its own in every respect (tasks, slab partials, chunk order: each sum is the one the job would
+// give alone on the shifted operands), so a table of 16 jobs covers any number of networks. alive (nullptr = all): a
+// repeat with alive[a] == 0 stores exact zeros for dw / db and adds nothing to the norm (reduce pass). A separate
+// kernel argument of the *_rep kernels: tables without repeats travel and run as before.
+constexpr int MLG_BREP_JOBS = 4;
+struct BRepeat {
+    int rep, nj;
+    int64_t sd[MLG_BREP_JOBS], sx[MLG_BREP_JOBS], sg;
+    const unsigned* alive;
+};
+
 inline BJob bjob(const float* delta, int64_t ldd, const float* x, int64_t ldx, float* dw, float* db, int M, int K,
                  int rows) {
     BJob j;
@@ -189,8 +202,9 @@ __device__ __forceinline__ void wgrad_mfma_step(const float (&a)[8][4], const fl
 
 // the work of workgroup `bid` (4 waves = 4 consecutive tasks) of a wgrad launch; a __device__ function so that
 // a learner can run it as extra workgroups of another launch (learner.hip bwd4_wgrad_kernel). 256 threads.
-template <int MJ, bool GLDS = false>
-__device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __restrict__ slab, int bid) {
+template <int MJ, bool GLDS = false, bool REP = false>
+__device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __restrict__ slab, int bid,
+                                                 const BRepeat* rp = nullptr) {
     // partials of the 4 waves summed pairwise in LDS, (c0 + c2) + (c1 + c3), before the one slab store per workgroup
     // (two 16 KB slots: with the reverse recurrence's LDS, bwd4_wgrad_kernel still fits two workgroups per CU). GLDS:
     // 16 KB of row staging per wave, the slots in waves 2 and 3's staging (their loops are over when they fill them)
@@ -201,9 +215,21 @@ __device__ __forceinline__ void wgrad_block_body(const BJobsT<MJ>& J, float* __r
     const int task = bid * 4 + w;
     const BJob& last = J.j[J.n - 1];
     // job task counts are multiples of 4: the test (and the job) is the same for the whole workgroup
-    if (bid * 4 >= last.task0 + bjob_wgs(last) * 4) return;
-    const BJob jb = J.j[find_bjob(J, task)];
-    const int wg = (task - jb.task0) >> 2;
+    int last_rep = 1;
+    if constexpr (REP) last_rep = J.n - 1 < rp->nj ? rp->rep : 1;
+    if (bid * 4 >= last.task0 + bjob_wgs(last) * 4 * last_rep) return;
+    const int jq = find_bjob(J, task);
+    BJob jb = J.j[jq];
+    int wg = (task - jb.task0) >> 2;
+    if constexpr (REP) {  // repeat a of the job: a job of its own on shifted operands (workgroup-uniform)
+        if (jq < rp->nj) {
+            const int per = bjob_wgs(jb), a = wg / per;
+            wg -= a * per;
+            jb.delta += a * rp->sd[jq];
+            jb.x += a * rp->sx[jq];
+            jb.slab0 += (int64_t)a * jb.mb * jb.nb * bjob_groups(jb) * BSLAB;
+        }
+    }
     // the 4 waves of a workgroup take the row chunks 4 cg .. 4 cg + 3 of one 64 x 64 output block and add their
     // partials in LDS, so the slab holds one partial per chunk group. Jobs with several output blocks (M = 192:
     // in_trans, W_ih, W_hh; K > 64) take the groups in stripes of 8: workgroup wg of a stripe has group
@@ -409,22 +435,42 @@ __global__ void __launch_bounds__(256, 2) wgrad_block_kernel(BJobsT<MJ> J, float
 }
 
 template <int MJ>
-__global__ void __launch_bounds__(256) wgrad_block_reduce_kernel(BJobsT<MJ> J, const float* __restrict__ slab,
-                                                                 float* __restrict__ nrm_part) {
+__global__ void __launch_bounds__(256, 2) wgrad_block_rep_kernel(BJobsT<MJ> J, BRepeat rp, float* __restrict__ slab) {
+    wgrad_block_body<MJ, true, true>(J, slab, (int)blockIdx.x, &rp);
+}
+
+template <int MJ, bool REP = false>
+__device__ __forceinline__ void wgrad_block_reduce_body(const BJobsT<MJ>& J, const float* __restrict__ slab,
+                                                        float* __restrict__ nrm_part, const BRepeat* rp = nullptr) {
     __shared__ float red[256];
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t acc = 0;
     float sq = 0.f;
     for (int q = 0; q < J.n; ++q) {
         const BJob& jb = J.j[q];
-        const int64_t n_el = (int64_t)jb.mb * jb.nb * BSLAB;
+        const int64_t n_one = (int64_t)jb.mb * jb.nb * BSLAB;
+        int64_t n_el = n_one;
+        if constexpr (REP) n_el = q < rp->nj ? n_one * rp->rep : n_one;
         if (i >= acc && i < acc + n_el) {
-            const int64_t loc = i - acc;
+            int64_t loc = i - acc;
+            const int ng = bjob_groups(jb);
+            const float* sl = slab + jb.slab0;
+            float *dw = jb.dw, *db = jb.db;
+            bool dead = false;
+            if constexpr (REP) {  // repeat a: its own slab range, its own dw / db
+                if (q < rp->nj) {
+                    const int a = (int)(loc / n_one);
+                    loc -= a * n_one;
+                    sl += (int64_t)a * jb.mb * jb.nb * ng * BSLAB;
+                    dw += a * rp->sg;
+                    if (db) db += a * rp->sg;
+                    dead = rp->alive && rp->alive[a] == 0u;
+                }
+            }
             const int blk = (int)(loc / BSLAB), e = (int)(loc % BSLAB);
             const int mbi = blk / jb.nb, nbi = blk % jb.nb;
             float s = 0.f;
-            const int ng = bjob_groups(jb);
-            const float* base = slab + jb.slab0 + (int64_t)blk * ng * BSLAB + e;
+            const float* base = sl + (int64_t)blk * ng * BSLAB + e;
             int ch = 0;
             // MLG_WRED_DEPTH loads in flight (the slab partials were just written by other CUs: each round trip is an
             // L2 / MALL miss), summed in group order
@@ -443,16 +489,17 @@ __global__ void __launch_bounds__(256) wgrad_block_reduce_kernel(BJobsT<MJ> J, c
                 for (int u = 0; u < 8; ++u) s += v[u];
             }
             for (; ch < ng; ++ch) s += base[(int64_t)ch * BSLAB];
+            if constexpr (REP) s = dead ? 0.f : s;
             if (e < 4096) {
                 const int m = mbi * 64 + e / 64, k = nbi * 64 + e % 64;
                 if (m < jb.M && k < jb.K) {
-                    jb.dw[(int64_t)m * jb.K + k] = s;
+                    dw[(int64_t)m * jb.K + k] = s;
                     sq = s * s;
                 }
-            } else if (nbi == 0 && jb.db) {
+            } else if (nbi == 0 && db) {
                 const int m = mbi * 64 + (e - 4096);
                 if (m < jb.M) {
-                    jb.db[m] = s;
+                    db[m] = s;
                     sq = s * s;
                 }
             }
@@ -465,15 +512,30 @@ __global__ void __launch_bounds__(256) wgrad_block_reduce_kernel(BJobsT<MJ> J, c
 }
 
 template <int MJ>
-inline int64_t layout_bjobs(BJobsT<MJ>& J, int* n_tasks, int64_t* n_red, int64_t* slab_part) {
+__global__ void __launch_bounds__(256) wgrad_block_reduce_kernel(BJobsT<MJ> J, const float* __restrict__ slab,
+                                                                 float* __restrict__ nrm_part) {
+    wgrad_block_reduce_body<MJ>(J, slab, nrm_part);
+}
+
+template <int MJ>
+__global__ void __launch_bounds__(256) wgrad_block_reduce_rep_kernel(BJobsT<MJ> J, BRepeat rp,
+                                                                     const float* __restrict__ slab,
+                                                                     float* __restrict__ nrm_part) {
+    wgrad_block_reduce_body<MJ, true>(J, slab, nrm_part, &rp);
+}
+
+template <int MJ>
+inline int64_t layout_bjobs(BJobsT<MJ>& J, int* n_tasks, int64_t* n_red, int64_t* slab_part,
+                            const BRepeat* rp = nullptr) {
     int tasks = 0;
     int64_t slab = 0, red = 0;
     for (int q = 0; q < J.n; ++q) {
+        const int rep = rp && q < rp->nj ? rp->rep : 1;  // a repeated job's tasks, partials and outputs, repeat-major
         J.j[q].task0 = tasks;
         J.j[q].slab0 = slab;
-        tasks += bjob_wgs(J.j[q]) * 4;
-        slab += (int64_t)J.j[q].mb * J.j[q].nb * bjob_groups(J.j[q]) * BSLAB;
-        red += (int64_t)J.j[q].mb * J.j[q].nb * BSLAB;
+        tasks += bjob_wgs(J.j[q]) * 4 * rep;
+        slab += (int64_t)J.j[q].mb * J.j[q].nb * bjob_groups(J.j[q]) * BSLAB * rep;
+        red += (int64_t)J.j[q].mb * J.j[q].nb * BSLAB * rep;
     }
     *n_tasks = tasks;
     *n_red = red;

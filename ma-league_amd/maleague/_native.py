@@ -71,7 +71,8 @@ class MlgLearnerCfg(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ["B", "T", "N", "A", "d_obs", "H", "S", "E", "HE", "hypernet_layers",
                                               "mixer", "double_q", "obs_last_action", "obs_agent_id"]] + \
                [(n, ctypes.c_float) for n in ["gamma", "lr", "optim_alpha", "optim_eps", "grad_norm_clip"]] + \
-               [("agent", ctypes.c_int32)]  # 0 DRQN, 1 feed-forward (dqn)
+               [("agent", ctypes.c_int32),  # 0 DRQN, 1 feed-forward (dqn)
+                ("distinct", ctypes.c_int32)]  # 1: one DRQN per agent slot (mac: distinct), vectors [agent 0 | .. | mixer]
 
 
 class MlgLearnerBufs(ctypes.Structure):

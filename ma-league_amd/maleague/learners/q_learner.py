@@ -6,13 +6,17 @@ RMSprop step. To make that possible the parameters of the MAC and mixer (and of 
 are re-homed into flat fp32 buffers; the nn.Module parameters become views into them, so state_dict()
 keys, checkpoint files and torch.optim.RMSprop.state_dict() stay compatible with the reference.
 
-With a DistinctMAC (mac: distinct, one network per agent slot) train() takes an unrolled branch instead
-(_train_distinct): the MAC's differentiable forward per step, the mixer op with its HIP backward, torch's
-clip_grad_norm_ and RMSprop; the fused pipeline holds one shared agent and is not extended.
+With a DistinctMAC (mac: distinct, one network per agent slot) train() is the same call with cfg.distinct = 1: the flat
+vectors are [agent 0 | ... | agent N-1 | mixer] and the agent kernels run the N networks by a grid coordinate
+(DESIGN.md §4j). MLG_DISTINCT_LEARNER=unrolled in the environment (read per call) takes the unrolled branch instead
+(_train_distinct): the MAC's differentiable forward per step, the mixer op with its HIP backward,
+torch's clip_grad_norm_ and RMSprop. Both work on the same flat parameters, gradients and RMSprop state, so a learner
+may switch between them from one call to the next.
 """
 from __future__ import annotations
 
 import copy
+import os
 
 import torch
 
@@ -94,8 +98,11 @@ class QLearner(Learner):
         self._last_stats = None
         self._stats_fresh = False
         self.train_calls = 0
-        # one network per agent slot: the unrolled branch (_train_distinct); mlg_qlearner_train holds one shared agent
+        # one network per agent slot: mlg_qlearner_train with cfg.distinct = 1; autograd stays enabled for the unrolled
+        # branch (MLG_DISTINCT_LEARNER=unrolled), which the fused call never enters (it runs no torch graph)
         self._distinct = isinstance(mac, DistinctMAC)
+        self._tcount = None  # distinct: the N networks' trained-steps counters as one float64 vector
+        self._tviews = None
         if self._distinct:
             mac.enable_autograd()
             if isinstance(self.mixer, QMixer):
@@ -110,12 +117,11 @@ class QLearner(Learner):
                                                      if self.mixer is not None else [])
 
     def _check_order(self):
-        if self._distinct:
-            return  # torch autograd and torch.optim.RMSprop: no flat kernel layout to match
-        names = [n for n, _ in self.mac.agent.named_parameters()]
-        order = list(getattr(self.mac.agent, "PARAM_ORDER", AGENT_ORDER))  # the feed-forward agent carries its own
-        if names != order:
-            raise RuntimeError(f"agent parameter order {names} != kernel layout {order}")
+        for agent in (self.mac.agents if self._distinct else [self.mac.agent]):
+            names = [n for n, _ in agent.named_parameters()]
+            order = list(getattr(agent, "PARAM_ORDER", AGENT_ORDER))  # the feed-forward agent carries its own
+            if names != order:
+                raise RuntimeError(f"agent parameter order {names} != kernel layout {order}")
         if isinstance(self.mixer, QMixer):
             names = [n for n, _ in self.mixer.named_parameters()]
             order = QMIX1_ORDER if self.mixer.hypernet_layers == 1 else QMIX_ORDER
@@ -123,10 +129,12 @@ class QLearner(Learner):
                 raise RuntimeError(f"mixer parameter order {names} != kernel layout {order}")
 
     def build_optimizer(self):
+        """Parameters re-homed into one flat buffer (a DistinctMAC's N networks back to back, then the mixer: the MAC's
+        pool then packs in one mlg_pack_agent_pool launch and the target update is one copy), the gradient and RMSprop
+        square_avg vectors beside it; torch.optim.RMSprop carries the state dict."""
         self._check_order()
-        if self._distinct:
-            return self._build_optimizer_distinct()
-        for m in [self.mac.agent, self.target_mac.agent] + ([self.mixer, self.target_mixer] if self.mixer else []):
+        nets = [self.mac.agents, self.target_mac.agents] if self._distinct else [self.mac.agent, self.target_mac.agent]
+        for m in nets + ([self.mixer, self.target_mixer] if self.mixer else []):
             m.to(self.device)
         params = self.parameters()
         self._flat = FlatParams(params, self.device)
@@ -140,12 +148,28 @@ class QLearner(Learner):
         for p, off, k in self._flat.views:
             self.optimiser.state[p] = {"step": self._step, "square_avg": self._sq[off:off + k].view_as(p)}
         self._stats = torch.zeros(8, dtype=torch.float32, device=self.device)
-        self.mac.agent.mark_dirty()
-        self.target_mac.agent.mark_dirty()
+        self._online().mark_dirty()
+        self._target().mark_dirty()
+
+    def _online(self):
+        """What holds the online networks' packed weights: the DistinctMAC itself (a pool), else the shared agent."""
+        return self.mac if self._distinct else self.mac.agent
+
+    def _target(self):
+        return self.target_mac if self._distinct else self.target_mac.agent
+
+    def _trained_counters(self):
+        """distinct: the networks' device-side trained-steps counts as one float64 vector [N] (element i seated as
+        network i's count), so the optimizer launch adds to all of them. Re-seated when a count was set from outside."""
+        agents = self.mac.agents
+        if self._tcount is None or not all(a.trained_counter_is(v) for a, v in zip(agents, self._tviews)):
+            self._tcount = torch.stack([a.trained_counter(self.device) for a in agents])
+            self._tviews = [a.seat_trained_counter(self._tcount[i]) for i, a in enumerate(agents)]
+        return self._tcount
 
     def _cfg(self, B, T):
         a = self.args
-        d = self.mac.agent.dims()
+        d = self._online().dims()
         mixer = 2 if isinstance(self.mixer, QMixer) else (1 if isinstance(self.mixer, VDNMixer) else 0)
         return _native.MlgLearnerCfg(B=B, T=T, N=a.n_agents, A=a.n_actions, d_obs=d.d_obs, H=a.rnn_hidden_dim,
                              S=int(a.state_shape), E=int(getattr(a, "mixing_embed_dim", 32)),
@@ -154,7 +178,8 @@ class QLearner(Learner):
                              obs_agent_id=int(bool(a.obs_agent_id)), gamma=float(a.gamma), lr=float(a.lr),
                              optim_alpha=float(a.optim_alpha), optim_eps=float(a.optim_eps),
                              grad_norm_clip=float(a.grad_norm_clip),
-                             agent=int(isinstance(self.mac.agent, DQNAgentNetwork)))
+                             agent=int(not self._distinct and isinstance(self.mac.agent, DQNAgentNetwork)),
+                             distinct=int(self._distinct))
 
     def train(self, batch, t_env, episode_num: int):
         """q_learner.py:34-131. `t_env` may also be a zero-argument callable, resolved after the device work
@@ -162,7 +187,11 @@ class QLearner(Learner):
         if self.optimiser is None:
             raise RuntimeError("call build_optimizer() before train()")
         if self._distinct:
-            return self._train_distinct(batch, t_env, episode_num)
+            which = os.environ.get("MLG_DISTINCT_LEARNER", "fused")  # read per call, as MLG_LEARNER_FULL
+            if which == "unrolled":
+                return self._train_distinct(batch, t_env, episode_num)
+            if which != "fused":
+                raise ValueError(f"MLG_DISTINCT_LEARNER={which!r} not recognised (fused, unrolled)")
         lib = _native.load(require_gpu=True)
         cfg = self._cfg(batch.batch_size, batch.max_seq_length)
         need = lib.mlg_qlearner_workspace_floats(_native.byref(cfg))
@@ -179,7 +208,7 @@ class QLearner(Learner):
         # the target update due after this step (q_learner.py:127-128) is written by the optimizer launch itself
         sync = (episode_num - self.last_target_update_episode) / self.args.target_update_interval >= 1.0
         # no host sync per train step: trained steps accumulate on the device (Agent.trained_steps)
-        counter = self.mac.agent.trained_counter(self.device)
+        counter = self._trained_counters() if self._distinct else self.mac.agent.trained_counter(self.device)
         bufs = _native.MlgLearnerBufs(mb, self._flat.flat.data_ptr(), self._grads.data_ptr(), self._sq.data_ptr(),
                                       self._tflat.flat.data_ptr(), self._ws.data_ptr(), self._stats.data_ptr(),
                                       self._tflat.flat.data_ptr() if sync else None, counter.data_ptr(),
@@ -187,10 +216,10 @@ class QLearner(Learner):
         _native.call("mlg_qlearner_train", _native.byref(cfg), _native.byref(bufs), _native.stream_ptr(self.device))
         del keep
         self._step += 1
-        self.mac.agent.mark_dirty()
+        self._online().mark_dirty()
         self.train_calls += 1
         if sync:
-            self.target_mac.agent.mark_dirty()
+            self._target().mark_dirty()
             self.logger.info(f"Updated {self.name}target network.")
             self.last_target_update_episode = episode_num
         self._stats_fresh = True
@@ -204,27 +233,14 @@ class QLearner(Learner):
                 self.logger.log_stat(self.name + k, v, t_env)
             self.log_stats_t = t_env
 
-    # ---- mac: distinct -- the unrolled branch (the pattern COMALearner uses for its actor) -------------------------
-    def _build_optimizer_distinct(self):
-        """Parameters of the N networks (and the mixer) re-homed back to back into one flat buffer, as the fused
-        learner's: the MAC's pool then packs in one mlg_pack_agent_pool launch and the target update is one copy.
-        Gradients are autograd's, the step torch.optim.RMSprop's."""
-        mods = [self.mac.agents, self.target_mac.agents] + ([self.mixer, self.target_mixer] if self.mixer else [])
-        for m in mods:
-            m.to(self.device)
-        params = self.parameters()
-        self._flat = FlatParams(params, self.device)
-        self._tflat = FlatParams(self._target_parameters(), self.device)
-        a = self.args
-        self.optimiser = torch.optim.RMSprop(params=params, lr=a.lr, alpha=a.optim_alpha, eps=a.optim_eps)
-        self._stats = torch.zeros(8, dtype=torch.float32, device=self.device)
-        self.mac.mark_dirty()
-        self.target_mac.mark_dirty()
-
+    # ---- mac: distinct -- the unrolled branch (MLG_DISTINCT_LEARNER=unrolled; the pattern COMALearner uses for its
+    # actor), the same-commit comparator of the fused call ------------------------------------------------------------
     def _train_distinct(self, batch, t_env, episode_num):
         """q_learner.py:34-131 with torch ops over the MAC unrolls: the online MAC differentiably
         (maleague::drqn_forward per network and step, HIP backward), the target MAC under no_grad through the fused
-        mlg_mac_forward_distinct; QMIX through maleague::qmix_forward (HIP backward), VDN's sum, or none."""
+        mlg_mac_forward_distinct; QMIX through maleague::qmix_forward (HIP backward), VDN's sum, or none. Gradients
+        are autograd's, accumulated into the fused learner's gradient vector (every .grad is a view of it); the step is
+        torch.optim.RMSprop's on the fused learner's square_avg vector, so the next call may be either branch's."""
         a = self.args
         rewards = batch["reward"][:, :-1]
         actions = batch["actions"][:, :-1]
@@ -268,11 +284,14 @@ class QLearner(Learner):
         mtd = td * mask
         n = mask.sum()
         loss = (mtd ** 2).sum() / n
-        self.optimiser.zero_grad()
+        self._grads.zero_()
+        self._flat.attach_grads(self._grads)  # autograd then accumulates in place
         loss.backward()
         params = self.parameters()
         grad_norm = torch.nn.utils.clip_grad_norm_(params, a.grad_norm_clip)
+        steps_done = float(self._step)
         self.optimiser.step()
+        self._step.fill_(steps_done + 1)  # the one step tensor is every parameter's: torch counted it once for each
         self.mac.mark_dirty()
         self.train_calls += 1
         if (episode_num - self.last_target_update_episode) / a.target_update_interval >= 1.0:
@@ -329,11 +348,10 @@ class QLearner(Learner):
             self.mixer.load_state_dict(sd)
         opt = torch.load(f"{path}/{self.name}opt.th", map_location=lambda s, loc: s, weights_only=True)
         self.optimiser.load_state_dict(opt)
-        if self._distinct:  # torch's own RMSprop state: nothing to re-home
+        if self._distinct:
+            # the target networks and mixer restart as copies of the online ones (as the branch did before it had a
+            # fused form; an opt.th it wrote then holds torch's own per-parameter state and re-homes like any other)
             self._tflat.flat.copy_(self._flat.flat)
-            self.mac.mark_dirty()
-            self.target_mac.mark_dirty()
-            return
         for p, off, k in self._flat.views:  # re-home the loaded RMSprop state into the flat buffer
             st = self.optimiser.state.get(p, {})
             if "square_avg" in st:
@@ -341,5 +359,5 @@ class QLearner(Learner):
             if "step" in st:  # one shared step counter (RMSprop steps every parameter together)
                 self._step.fill_(float(st["step"]))
             self.optimiser.state[p] = {"step": self._step, "square_avg": self._sq[off:off + k].view_as(p)}
-        self.mac.agent.mark_dirty()
-        self.target_mac.agent.mark_dirty()
+        self._online().mark_dirty()
+        self._target().mark_dirty()

@@ -43,6 +43,15 @@ class AgentNetwork(nn.Module):
             self._trained_dev = torch.full((), extra, dtype=torch.float64, device=device)
         return self._trained_dev
 
+    def seat_trained_counter(self, view: torch.Tensor):
+        """Makes ``view`` (a 0-dim float64 element of a learner's counter vector, holding this network's count so far)
+        the device-side count, so that one kernel adds to the counts of several networks; returns it."""
+        self._trained_dev = view
+        return view
+
+    def trained_counter_is(self, view) -> bool:
+        return self._trained_dev is view
+
     def add_trained_steps(self, update):
         if torch.is_tensor(update):
             if self._trained_dev is None:

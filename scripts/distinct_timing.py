@@ -5,11 +5,20 @@
             4096 envs (the medium_1h_4t plan, episode limit 100, train mode at t_env 30000), next to mlg_rollout under
             MLG_ROLLOUT_KERNEL=v1 (BasicMAC, obs_agent_id off: the like-for-like generic fp32 kernel) at the same
             shape. The two alternate; median and spread over the repetitions after the warm-up runs.
-  learner   one QLearner.train call (qmix) with mac=distinct at 32 episodes x 5 agents on a rollout's own batch, next
-            to the fused learner's (mlg_qlearner_train, BasicMAC) on a batch of the same shape: HIP events around the
-            call, median and spread.
+  learner   one QLearner.train call (qmix) with mac=distinct at 32 episodes x 5 agents on a rollout's own batch, through
+            both learner paths in one run -- the fused call (mlg_qlearner_train with cfg.distinct = 1, the default) and
+            the unrolled branch (MLG_DISTINCT_LEARNER=unrolled), on learners of their own with equal weights, the calls
+            alternating -- next to the shared-agent fused learner's (BasicMAC) on a batch of the same shape: HIP
+            events around the call, median and spread.
 
     python scripts/distinct_timing.py [--envs 4096] [--reps 10] [--warmup 3] [--out FILE.json]
+
+  launches  kernel launches per train call, by difference: the same process run twice under a kernel trace with K = 1
+            and K = 3 train calls after the set-up; (count(3) - count(1)) / 2 is one call's launches, whatever the
+            set-up and the rollout launched. --plan small is 3 agents, medium_1h_4t is 5.
+
+    rocprofv3 --kernel-trace --output-format csv -d OUT -- \
+        python scripts/distinct_timing.py --launch-probe K [--path fused|unrolled] [--plan medium_1h_4t]
 """
 import argparse
 import json
@@ -26,13 +35,13 @@ for p in ("ma-league_amd", "oracle", "tests"):
 from helpers import qmix_args, scheme_for  # noqa: E402
 
 
-def build(mac_name, B, device, **kw):
+def build(mac_name, B, device, plan="medium_1h_4t", **kw):
     from maleague.components.episode_batch import EpisodeBatch
     from maleague.controllers import REGISTRY
     from maleague.custom_logging import MainLogger
     from maleague.steppers import ParallelStepper
     args = qmix_args(batch_size_run=B, seed=1, obs_agent_id=False, mac=mac_name, learner_log_interval=10 ** 12,
-                     env_args={"match_build_plan": "medium_1h_4t", "grid_size": 20, "stochastic_spawns": True,
+                     env_args={"match_build_plan": plan, "grid_size": 20, "stochastic_spawns": True,
                                "episode_limit": 100}, **kw)
     stepper = ParallelStepper(args, MainLogger(log_interval=10 ** 12))
     info = stepper.get_env_info()
@@ -78,30 +87,61 @@ def time_rollouts(envs, reps, warmup, device):
     return out
 
 
-def time_learners(reps, warmup, device):
+def learner_on_rollout(mac_name, device, plan="medium_1h_4t"):
+    """A learner on a 32-episode train-mode rollout of its own MAC, truncated to max_t_filled."""
     from maleague.custom_logging import MainLogger
     from maleague.learners import QLearner
+    stepper, mac, args, proto = build(mac_name, 32, device, plan=plan)
+    learner = QLearner(mac, proto.scheme, MainLogger(log_interval=10 ** 12), args, name="home")
+    learner.build_optimizer()
+    stepper.t_env = 30000
+    batch, _ = stepper.run(test_mode=False)
+    stepper.flush()
+    T = int(batch.max_t_filled())
+    return learner, batch[:, :T], T, args
+
+
+def timed_call(learner, sample, it, path=None):
+    if path == "unrolled":
+        os.environ["MLG_DISTINCT_LEARNER"] = "unrolled"
+    else:
+        os.environ.pop("MLG_DISTINCT_LEARNER", None)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    learner.train(sample, 30000, it)
+    b.record()
+    torch.cuda.synchronize()
+    os.environ.pop("MLG_DISTINCT_LEARNER", None)
+    return a.elapsed_time(b)
+
+
+def time_learners(reps, warmup, device):
     out = {}
-    for name, mac_name in (("QLearner.train mac=distinct", "distinct"), ("QLearner.train fused (mac=basic)", "basic")):
-        stepper, mac, args, proto = build(mac_name, 32, device)
-        learner = QLearner(mac, proto.scheme, MainLogger(log_interval=10 ** 12), args, name="home")
-        learner.build_optimizer()
-        stepper.t_env = 30000
-        batch, _ = stepper.run(test_mode=False)
-        stepper.flush()
-        T = int(batch.max_t_filled())
-        sample = batch[:, :T]
-        ms = []
-        for it in range(warmup + reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            learner.train(sample, 30000, it)
-            b.record()
-            torch.cuda.synchronize()
+    # the two distinct paths: equal weights (the same seed builds both MACs), the same rollout, calls alternating
+    legs = {}
+    for name, path in (("QLearner.train mac=distinct fused", "fused"), ("QLearner.train mac=distinct unrolled", "unrolled")):
+        legs[name] = learner_on_rollout("distinct", device) + (path,)
+    times = {k: [] for k in legs}
+    for it in range(warmup + reps):
+        for name, (learner, sample, T, args, path) in legs.items():
+            ms = timed_call(learner, sample, it, path)
             if it >= warmup:
-                ms.append(a.elapsed_time(b))
-        out[name] = dict(summary(ms), episodes=32, T=T, agents=args.n_agents)
+                times[name].append(ms)
+    for name, (learner, sample, T, args, path) in legs.items():
+        out[name] = dict(summary(times[name]), episodes=32, T=T, agents=args.n_agents)
+    learner, sample, T, args = learner_on_rollout("basic", device)
+    ms = [timed_call(learner, sample, it) for it in range(warmup + reps)][warmup:]
+    out["QLearner.train fused (mac=basic)"] = dict(summary(ms), episodes=32, T=T, agents=args.n_agents)
     return out
+
+
+def launch_probe(calls, path, plan, device, mac="distinct"):
+    """Set-up, then `calls` train calls and nothing else: for a kernel trace (see the module docstring)."""
+    learner, sample, T, args = learner_on_rollout(mac, device, plan=plan)
+    torch.cuda.synchronize()
+    for it in range(calls):
+        timed_call(learner, sample, it, path)
+    print(json.dumps({"launch_probe": calls, "path": path, "agents": args.n_agents, "T": T}))
 
 
 def main():
@@ -110,9 +150,17 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--learner-only", action="store_true", help="skip the rollout legs")
+    ap.add_argument("--launch-probe", type=int, default=0, metavar="K", help="run K train calls and exit (kernel trace)")
+    ap.add_argument("--path", choices=("fused", "unrolled"), default="fused")
+    ap.add_argument("--plan", default="medium_1h_4t")
+    ap.add_argument("--mac", choices=("distinct", "basic"), default="distinct", help="the probe's MAC")
     a = ap.parse_args()
     device = torch.device("cuda:0")
-    res = {"rollout": time_rollouts(a.envs, a.reps, a.warmup, device), "learner": time_learners(a.reps, a.warmup, device)}
+    if a.launch_probe:
+        return launch_probe(a.launch_probe, a.path, a.plan, device, a.mac)
+    res = {} if a.learner_only else {"rollout": time_rollouts(a.envs, a.reps, a.warmup, device)}
+    res["learner"] = time_learners(a.reps, a.warmup, device)
     print(json.dumps(res, indent=1))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
