@@ -30,6 +30,8 @@
  *                      (src/marl/learners/q_learner.py:47-52,103 with any loss)
  *   mlg_crossplay_rollout  JointPolicyCorrelationEvaluationRun.evaluate_instances (all pairs in one launch)
  *                      src/runs/evaluation/jpc_eval_run.py:62-89
+ *   mlg_rollout_selfplay_mix  mlg_rollout_selfplay with one away policy and roster per 16 envs (a league match against
+ *                      an opponent mixture; no reference counterpart: its matches are single-env episodes)
  *   mlg_refil_*      REFIL (config 5): see the REFIL section below
  *   mlg_policy_probs   MultiAgentController._softmax src/marl/controllers/multi_agent_controller.py:78-99
  *   mlg_select_multinomial MultinomialActionSelector.select src/marl/components/action_selectors.py:11-32
@@ -533,6 +535,57 @@ int mlg_crossplay_rollout(const MlgAgentDims *dims, const MlgCrossplay *c, void 
  * [P][mlg_packed_agent_size(dims)]; each row equals mlg_pack_agent() of the same parameters. One launch. */
 int mlg_pack_agent_pool(const MlgAgentDims *dims, const float *flat, int64_t row_stride, int32_t P,
                         float *packed_pool, void *stream);
+
+/* ---- Self-play against an opponent mixture (league matches): one away policy and roster per 16 envs -------------
+ * Env b belongs to group g = b / 16; n_groups = ceil(B / 16). Group g plays the home policy against away policy
+ * packed_pool[groups[g].away] (a row written by mlg_pack_agent_pool) under the roster specs[groups[g].spec]. Env b
+ * runs EXACTLY as env b of mlg_rollout_selfplay from the same MlgEnvState with that away block and that spec: the same
+ * home weights and epsilons (one away epsilon for every opponent), RNG key mlg_env_key(seed, b), counters and stream
+ * index (the global agent index), ring / full-write / slot_extent modes. Its rows of both batches and its run info
+ * are bit-identical to that plain launch on the same arm family (a row of an MFMA tile depends on its own inputs only).
+ * Host copies are validated before anything is launched and are never launched themselves; the kernels read the device
+ * copies and guard the indices they read: a group whose device row is out of range plays nothing (ep_len -1, returns
+ * 0, won / draw 0, no batch row written). */
+typedef struct {
+    int32_t away; /* row of packed_pool */
+    int32_t spec; /* index into specs */
+} MlgMixGroup;
+
+typedef struct {
+    const float *packed_pool;      /* device [n_pool][mlg_packed_agent_size(dims)], 16-byte aligned */
+    int32_t n_pool;
+    int32_t n_groups;              /* ceil(B / 16) */
+    const MlgMixGroup *groups;     /* device [n_groups]: what the launch reads */
+    const MlgMixGroup *host_groups; /* HOST copy: validated (indices in range), never launched */
+    const MlgEnvSpec *specs;       /* device [n_specs]: what the launch reads */
+    const MlgEnvSpec *host_specs;  /* HOST copy: valid two-policy-team specs that agree with each other and with spec0 on
+                                      U, n_agents, n_actions, grid, episode_limit, stochastic, policy_team and seed
+                                      (team / role / melee / agent_unit may differ: composed rosters); agents 0..nh-1
+                                      are the home team in each */
+    int32_t n_specs;
+} MlgOpponentMix;
+
+/* mlg_rollout_selfplay's arguments with the away policy and the roster taken per group from `mix`; spec0 gives the
+ * shape every spec shares (host_specs[k] must agree with it). Two arms: "sp8-mix" exactly when mlg_rollout_selfplay
+ * would launch "sp8" for the shape (static 5v5 / 3v3 plans at H = 64; one group per sp8 workgroup), else "v1-mix/tpwK",
+ * the generic fp32 self-play kernel with global-memory weights (MLG_ROLLOUT_KERNEL=v1 | sp2 | sp7 and
+ * MLG_ROLLOUT_GENERIC included: sp7 / sp2 have no mixture form). One launch. */
+int mlg_rollout_selfplay_mix(const MlgEnvSpec *spec0, MlgEnvState *st, const MlgAgentDims *dims,
+                             const float *home_packed, const MlgOpponentMix *mix, MlgBatch *home, MlgBatch *away,
+                             MlgRunInfo *info, float eps_home, float eps_away, int32_t test_mode, void *stream);
+/* Host only, launches nothing (the contract of mlg_rollout_describe): the arm mlg_rollout_selfplay_mix would launch for
+ * this shape under the current MLG_ROLLOUT_* environment and its dynamic LDS bytes. */
+int mlg_rollout_selfplay_mix_describe(const MlgEnvSpec *spec0, const MlgAgentDims *dims, char *name, int32_t name_cap,
+                                      int64_t *lds_bytes);
+
+/* mlg_league_record_runs per opponent: env b books into row + group_col[b / 16] * entry_stride (a payoff entry
+ * [GAMES, WIN, LOSS, DRAW, ...]) by the same win / loss / draw rule; GAMES += the column's envs when count_games.
+ * group_col: device [ceil(B / 16)], each in [0, n_cols) (a group whose column is out of range books nothing); equal
+ * columns add up. Integer counts, reduced in a fixed order (wave w of the one workgroup owns the columns w, w + 16,
+ * ...; lane l counts the envs l, l + 64, ... of every group of the column in ascending order, then the 64 lane counts
+ * are added by an integer butterfly), no float atomics. One launch. */
+int mlg_league_record_runs_mix(const int32_t *won, const int32_t *draw, int32_t B, const int32_t *group_col,
+                               int32_t n_cols, float *row, int64_t entry_stride, int32_t count_games, void *stream);
 
 /* ---- COMA (algs/coma.yaml): policy output, multinomial selection, critic training, actor loss ------------- */
 /* MultiAgentController._softmax (multi_agent_controller.py:78-99) over R rows of logits [R][A] with avail [R][A]:

@@ -70,7 +70,67 @@ __global__ void __launch_bounds__(kRecThreads) league_record_kernel(const int32_
     }
 }
 
+// The mixture form: env b books into column group_col[b / 16]. One block of 16 waves; wave w owns the columns w,
+// w + 16, ... and nobody else touches their entries. Per column the wave scans the group table 64 entries at a time
+// and reads the 16 envs of up to four matching groups at once (one quarter-wave per group: the run summary may live
+// in pinned host memory, so a wave's loads of one pass are issued together). Counts are integers; the 64 lane counts
+// are added by a butterfly and lane 0 adds each total into the entry once.
+__global__ void __launch_bounds__(kRecThreads) league_record_mix_kernel(const int32_t* __restrict__ won,
+                                                                        const int32_t* __restrict__ draw, int B, int G,
+                                                                        const int32_t* __restrict__ group_col,
+                                                                        int n_cols, float* __restrict__ row,
+                                                                        int64_t entry_stride, int count_games) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, le = lane & 15;
+    for (int c = wave; c < n_cols; c += kRecThreads / 64) {
+        int w = 0, l = 0, d = 0, n = 0;
+        for (int g0 = 0; g0 < G; g0 += 64) {
+            const int g = g0 + lane;
+            unsigned long long m = __ballot(g < G && group_col[g] == c);
+            while (m) {  // wave-uniform: up to four matching groups per pass, quarter q takes the q-th
+                unsigned long long mq = m;
+                for (int k = 0; k < q; ++k) mq &= mq - 1;
+                const int b = mq ? (g0 + __ffsll((long long)mq) - 1) * 16 + le : B;
+                if (b < B) {
+                    const bool w0 = won[2 * b] != 0, w1 = won[2 * b + 1] != 0;
+                    const bool dr = draw[b] != 0 || w0 == w1;
+                    w += !dr && w0;
+                    l += !dr && !w0;
+                    d += dr;
+                    n += 1;
+                }
+                for (int k = 0; k < 4 && m; ++k) m &= m - 1;
+            }
+        }
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) {
+            w += __shfl_xor(w, s);
+            l += __shfl_xor(l, s);
+            d += __shfl_xor(d, s);
+            n += __shfl_xor(n, s);
+        }
+        if (lane == 0) {
+            float* entry = row + (int64_t)c * entry_stride;
+            if (count_games) entry[0] += (float)n;
+            entry[1] += (float)w;
+            entry[2] += (float)l;
+            entry[3] += (float)d;
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int mlg_league_record_runs_mix(const int32_t* won, const int32_t* draw, int32_t B, const int32_t* group_col,
+                                          int32_t n_cols, float* row, int64_t entry_stride, int32_t count_games,
+                                          void* stream) {
+    MLG_REQUIRE(won && draw && group_col && row, "league_record_runs_mix: null pointer");
+    MLG_REQUIRE(B >= 1 && n_cols >= 1, "league_record_runs_mix: B=%d n_cols=%d must be >= 1", B, n_cols);
+    MLG_REQUIRE(entry_stride >= 4, "league_record_runs_mix: entry_stride=%lld < 4 (GAMES, WIN, LOSS, DRAW)",
+                (long long)entry_stride);
+    hipLaunchKernelGGL(league_record_mix_kernel, dim3(1), dim3(kRecThreads), 0, (hipStream_t)stream, won, draw, B,
+                       (B + 15) / 16, group_col, n_cols, row, entry_stride, count_games);
+    return mlg::check_launch("league_record_runs_mix");
+}
 
 extern "C" int mlg_league_record_runs(const int32_t* won, const int32_t* draw, int32_t B, float* entry,
                                       int32_t count_games, void* stream) {

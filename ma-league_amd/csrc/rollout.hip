@@ -18,7 +18,8 @@
 // The per-workgroup env machinery (spec tables, env LDS carve, sides, observe / reset / env step / zeroing / summary,
 // action recording) is rollout_env_device.h and the argument checks rollout_host.h, both shared with
 // rollout_policy.hip and crossplay.hip. This file holds the diagnostic phase stamps, the kernels (v1, v2 / v7, the
-// self-play ones, the standalone env kernels), the dispatch and the entry points.
+// self-play ones, the standalone env kernels), the dispatch and the entry points. rollout_mix.hip (self-play against an
+// opponent mixture) takes sp8's dispatch decision and the sp8-mix launch from the two functions at the end.
 #include <cstring>
 
 #include "agent_device.h"
@@ -1625,6 +1626,7 @@ __global__ void __launch_bounds__(512, 2) rollout_v2_kernel(MlgEnvSpec spec, Mlg
 
 #include "rollout_sp.inc"
 #include "rollout_sp8.inc"
+#include "rollout_sp8_mix.inc"
 
 __global__ void env_reset_kernel(MlgEnvSpec spec, MlgEnvState st) {
     __shared__ SpecShared SS;
@@ -2085,4 +2087,34 @@ extern "C" int mlg_rollout_selfplay(const MlgEnvSpec* spec, MlgEnvState* st, con
         return mlg::check_launch("rollout_sp_kernel");
     }
     return launch_rollout_v1(s, *spec, *st, L, sd, *info, test_mode, plan);
+}
+
+// ---- for rollout_mix.hip (mlg_rollout_selfplay_mix): sp8's decision and the sp8-mix launch ----------------------
+// The agents per env (10 / 6) of the sp8 instantiation mlg_rollout_selfplay would launch for this shape under the
+// current MLG_ROLLOUT_* environment, 0 when it would launch anything else; *lds_bytes = that launch's dynamic LDS.
+int rollout_selfplay_sp8_shape(const MlgEnvSpec* spec, const MlgAgentDims* dims, int64_t* lds_bytes) {
+    RolloutPlan plan;
+    if (plan_rollout(make_agent_layout(*dims), *spec, true, &plan) || plan.arm != Arm::SP8) return 0;
+    *lds_bytes = (int64_t)plan.lds_bytes;
+    return plan.sn;
+}
+
+// Arguments validated by the caller; eps already zeroed in test mode.
+int launch_rollout_sp8_mix(int sn, const MlgEnvSpec* spec0, const MlgEnvState* st, const MlgAgentDims* dims,
+                           const float* home_packed, const MlgOpponentMix* mix, const MlgBatch* home,
+                           const MlgBatch* away, const MlgRunInfo* info, float eps0, float eps1, int32_t test_mode,
+                           void* stream) {
+    const size_t bytes = (size_t)(sn == 10 ? StaticShapeSP8<10, 10>::lay.total : StaticShapeSP8<6, 6>::lay.total) * 4;
+    SP8Mix m;
+    m.pool = mix->packed_pool;
+    m.pool_stride = make_agent_layout(*dims).total;
+    m.groups = mix->groups;
+    m.specs = mix->specs;
+    m.n_pool = mix->n_pool;
+    m.n_specs = mix->n_specs;
+    auto kern = sn == 10 ? rollout_sp8_mix_kernel<10, 10> : rollout_sp8_mix_kernel<6, 6>;
+    if (int rc = allow_lds(kern, bytes, "rollout_selfplay_mix")) return rc;
+    hipLaunchKernelGGL(kern, dim3((st->B + RS8 - 1) / RS8), dim3(512), bytes, (hipStream_t)stream, *spec0, *st,
+                       home_packed, m, *home, *away, *info, eps0, eps1, test_mode);
+    return mlg::check_launch("rollout_sp8_mix_kernel");
 }

@@ -127,6 +127,16 @@ class MlgCrossplay(ctypes.Structure):
                 ("won", ctypes.c_void_p), ("draw", ctypes.c_void_p), ("summary", ctypes.c_void_p)]
 
 
+class MlgMixGroup(ctypes.Structure):
+    _fields_ = [("away", ctypes.c_int32), ("spec", ctypes.c_int32)]
+
+
+class MlgOpponentMix(ctypes.Structure):
+    _fields_ = [("packed_pool", ctypes.c_void_p), ("n_pool", ctypes.c_int32), ("n_groups", ctypes.c_int32),
+                ("groups", ctypes.c_void_p), ("host_groups", ctypes.c_void_p), ("specs", ctypes.c_void_p),
+                ("host_specs", ctypes.c_void_p), ("n_specs", ctypes.c_int32)]
+
+
 class MlgComaCfg(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ["B", "T", "N", "A", "d_obs", "S", "hidden"]] + \
                [(n, ctypes.c_float) for n in ["lr", "optim_eps", "grad_norm_clip"]] + \
@@ -212,6 +222,9 @@ SIGNATURES = {
     "mlg_mac_forward_distinct": (ctypes.c_int, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "mlg_rollout_distinct": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
     "mlg_rollout_distinct_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
+    "mlg_rollout_selfplay_mix": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _I, _P]),
+    "mlg_rollout_selfplay_mix_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
+    "mlg_league_record_runs_mix": (ctypes.c_int, [_P, _P, _I, _P, _I, _P, ctypes.c_int64, _I, _P]),
     "mlg_last_error": (ctypes.c_char_p, []),
     "mlg_version": (ctypes.c_char_p, []),
 }
@@ -259,6 +272,19 @@ def rollout_describe(spec: MlgEnvSpec, dims: MlgAgentDims, selfplay: bool = Fals
                                   ctypes.byref(lds))
     if rc != 0:
         raise NativeError(f"mlg_rollout_describe failed: {lib.mlg_last_error().decode()}")
+    return name.value.decode(), int(lds.value)
+
+
+def rollout_selfplay_mix_describe(spec: MlgEnvSpec, dims: MlgAgentDims) -> tuple[str, int]:
+    """(arm name, dynamic LDS bytes) of the launch mlg_rollout_selfplay_mix would make for this shape under the current
+    MLG_ROLLOUT_* environment: "sp8-mix" or "v1-mix/tpwK" (mlg_rollout_selfplay_mix_describe: host only)."""
+    lib = load()
+    name = ctypes.create_string_buffer(32)
+    lds = ctypes.c_int64(0)
+    rc = lib.mlg_rollout_selfplay_mix_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name),
+                                               ctypes.byref(lds))
+    if rc != 0:
+        raise NativeError(f"mlg_rollout_selfplay_mix_describe failed: {lib.mlg_last_error().decode()}")
     return name.value.decode(), int(lds.value)
 
 

@@ -113,6 +113,43 @@ class DistributedLeague:
         if not self.payoff.reference_compat:
             self._delta[home, away, PayoffEntry.GAMES] += won.shape[0]
 
+    def record_runs_mix(self, home: int, cols, group_col, won: torch.Tensor, draw: torch.Tensor):
+        """record_runs for a run against an opponent mixture: env b belongs to group b // 16 and books into payoff
+        column ``cols[group_col[b // 16]]`` (``cols``: the opponent pid of every draw, equal draws share a column;
+        ``group_col``: ceil(B / 16) indices into ``cols``). Device tensors: one mlg_league_record_runs_mix launch over
+        this player's row of the local delta (the device copy of the column table is kept until the table changes);
+        host tensors: the same reduction in torch, per column."""
+        B = int(won.shape[0])
+        G = (B + 15) // 16
+        cols = [int(c) for c in cols]
+        table = [int(k) for k in group_col]
+        if len(table) != G or any(k < 0 or k >= len(cols) for k in table):
+            raise ValueError(f"record_runs_mix: group_col must hold {G} indices into the {len(cols)} columns")
+        if any(c < 0 or c >= self.capacity for c in cols):
+            raise ValueError(f"record_runs_mix: columns {cols} outside the payoff table [0, {self.capacity})")
+        gcol = [cols[k] for k in table]
+        if self._delta.is_cuda:
+            from .. import _native
+            reach = lambda x: x.is_cuda or (x.device.type == "cpu" and x.is_pinned())  # noqa: E731
+            if won.dtype != torch.int32 or draw.dtype != torch.int32 or tuple(won.shape) != (B, 2) or \
+                    tuple(draw.shape) != (B,) or not reach(won) or not reach(draw):
+                raise ValueError(f"record_runs_mix: won must be int32 [B, 2] and draw int32 [B] on the device or pinned, "
+                                 f"got {won.dtype} {tuple(won.shape)} / {draw.dtype} {tuple(draw.shape)}")
+            cache = getattr(self, "_gcol", None)
+            if cache is None or cache[0] != gcol:
+                cache = (gcol, torch.tensor(gcol, dtype=torch.int32).to(self.device))
+                self._gcol = cache
+            row = self._delta[home]
+            dptr = lambda x: _native.ptr(x) if x.is_cuda else x.data_ptr()  # noqa: E731  (pinned: device-accessible)
+            _native.call("mlg_league_record_runs_mix", dptr(won.contiguous()), dptr(draw.contiguous()), B,
+                         cache[1].data_ptr(), self.capacity, row.data_ptr(), int(row.stride(0)),
+                         int(not self.payoff.reference_compat), _native.stream_ptr(self.device))
+            return
+        env_col = torch.tensor(gcol, dtype=torch.int64).repeat_interleave(16)[:B]
+        for c in sorted(set(gcol)):
+            sel = env_col == c
+            self.record_runs(home, c, won[sel], draw[sel])
+
     def _host_staged(self) -> bool:
         """gloo (CPU tests, single-GPU rehearsals) reduces host tensors; RCCL reduces device tensors in place."""
         return self.device.type == "cuda" and dist.get_backend() == "gloo"

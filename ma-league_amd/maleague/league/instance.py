@@ -6,6 +6,9 @@ role_based_league_instance.py:21-53 (with LeagueExperimentInstance, league_exper
   2. share the home agent's parameters with the league                          (:26)
   3. per league iteration: get a match (matchmaker or league role), load the adversary's parameters, play
      ``iterations_per_match`` self-play training iterations recording every episode's result, share.
+With ``opponents_per_match = K > 1`` a match draws K opponents and every rollout launch plays all of them, one per
+contiguous block of 16-env groups (an opponent mixture, SelfPlayParallelStepper.set_opponent_mix): PFSP and the role
+branch mixes are realised inside a match, the results land in K payoff cells and the replay buffer holds K opponents.
 Processes, queues and the coordinator are replaced by one rank per GPU and DistributedLeague collectives.
 The self-play experiment is built once per instance and its adversary swapped between matches (the
 reference rebuilds LeagueExperiment -- replay buffer, optimizer state -- for every match).
@@ -27,16 +30,37 @@ from .roles import ROLES, Historical, LeagueView, alphastar_roles
 from .teams import match_plan
 
 
+def group_count(batch_size: int) -> int:
+    """16-env groups of a rollout launch (one workgroup, one opponent of a mixture each)."""
+    return (int(batch_size) + 15) // 16
+
+
+def group_assignment(K: int, G: int) -> list:
+    """The draw of every group: draw j of K (clipped to G) gets the contiguous groups [floor(j G / K),
+    floor((j + 1) G / K)), so every draw gets at least one group and the block sizes differ by at most one."""
+    K = max(1, min(int(K), int(G)))
+    out = []
+    for j in range(K):
+        out.extend([j] * ((j + 1) * G // K - j * G // K))
+    return out
+
+
 class LeagueInstance:
     """``mode``: "matchmaking" (args.matchmaking in pfsp/uniform/random/fsp/adversaries, every player a
     learner) or "rolebased" (``role`` in simple/main/main_exploiter/league_exploiter)."""
 
     def __init__(self, args, logger, league: DistributedLeague, mode="matchmaking", role=None, seed=0,
-                 experiment=None, teams=None):
+                 experiment=None, teams=None, opponents_per_match: int = 1):
         """``teams``: the league's Team of every player (index = pid; league.teams.compose_league_teams, one team
         per player as CentralWorker assigns them, central_worker.py:84-93). Each match then puts this player's team
         against the opponent's (a historical snapshot plays its parent's team). None: every player plays the
-        env config's own plan, mirrored."""
+        env config's own plan, mirrored. ``opponents_per_match``: opponents drawn per sync() (clipped to the number
+        of 16-env groups of a launch); 1 is the single-adversary match."""
+        if int(opponents_per_match) < 1:
+            raise ValueError(f"opponents_per_match={opponents_per_match} must be >= 1")
+        self.opponents_per_match = int(opponents_per_match)
+        self.opponents = []      # the draws of the current match (pids; equal draws repeat)
+        self.group_draw = None   # mixture match: the draw (index into opponents) of every 16-env group
         if getattr(args, "mac", "basic") == "distinct":
             raise NotImplementedError("LeagueInstance shares one parameter-shared agent per player with the league: "
                                       "mac='distinct' is not supported (a league over distinct MACs is out of scope)")
@@ -133,6 +157,10 @@ class LeagueInstance:
             self.me.checkpoint()  # only when the snapshot exists (max_historical > 0): otherwise it asks again
         self.league.barrier()
         view = self.view()
+        K = 1 if self.opponents_per_match == 1 else \
+            min(self.opponents_per_match, group_count(self.experiment.stepper.batch_size))
+        if K > 1:
+            return self._sync_mix(view, K)
         if self.matchmaker is not None:
             opp, hist = self.matchmaker.get_match(self.pid, view), False
         else:
@@ -142,6 +170,7 @@ class LeagueInstance:
         if self._any(opp is None):
             return None
         self.opponent = int(opp)
+        self.opponents, self.group_draw = [self.opponent], None
         self.experiment.load_adversary_vector(self.league.params_of(self.opponent))
         if self.teams is not None:  # the adversary's roster (matchmaking_league_instance.py:52, :61-62)
             self.away_team = self.team_of(self.opponent)
@@ -149,6 +178,40 @@ class LeagueInstance:
             self.experiment.configure_match(self.home_team, self.away_team)
         self.history.append((len(self.history), self.opponent, bool(hist)))
         return self.opponent, hist
+
+    def _sync_mix(self, view, K: int):
+        """The match of sync() with K > 1 draws: K calls of the matchmaker (or of the role's get_match), one
+        record_match per draw, draw j on the contiguous groups [floor(j G / K), floor((j + 1) G / K)). Equal draws
+        share a payoff column. With teams every opponent plays ``team_of(pid)``'s roster."""
+        draws = []
+        for _ in range(K):
+            if self.matchmaker is not None:
+                opp, hist = self.matchmaker.get_match(self.pid, view), False
+            else:
+                opp, hist = self.me.get_match(view)
+                if opp is not None:
+                    self.league.record_match(self.pid, opp)
+            draws.append((opp, bool(hist)))
+        # the league ends for everybody once one player has no match left (keeps the collectives aligned)
+        if self._any(any(opp is None for opp, _ in draws)):
+            return None
+        self.opponents = [int(opp) for opp, _ in draws]
+        self.opponent = self.opponents[0]
+        self.group_draw = group_assignment(K, group_count(self.experiment.stepper.batch_size))
+        # the away MAC keeps a real opponent (architecture check, away epsilon); the launches read the pool rows
+        self.experiment.load_adversary_vector(self.league.params_of(self.opponent))
+        rows = torch.stack([self.league.params_of(o) for o in self.opponents])
+        if self.teams is not None:
+            aways = [self.team_of(o) for o in self.opponents]
+            self.away_team = aways[0]
+            self.away_teams.extend(t.codes() for t in aways)
+            self.experiment.configure_match(self.home_team, self.away_team)
+            self.experiment.load_adversary_mix(rows, self.group_draw, teams=aways, home=self.home_team)
+        else:
+            self.experiment.load_adversary_mix(rows, self.group_draw)
+        for opp, hist in draws:
+            self.history.append((len(self.history), int(opp), hist))
+        return self.opponent, draws[0][1]
 
     def _any(self, flag: bool) -> bool:
         if not self.league._dist:
@@ -166,7 +229,11 @@ class LeagueInstance:
         for _ in range(iterations):
             exp._train_episode(self.episode)
             info = st.last_run_info() if hasattr(st, "last_run_info") else st._info
-            self.league.record_runs(self.pid, self.opponent, info[B:3 * B].view(B, 2), info[3 * B:4 * B])
+            if self.group_draw is not None:  # mixture match: every env books into its group's opponent
+                self.league.record_runs_mix(self.pid, self.opponents, self.group_draw, info[B:3 * B].view(B, 2),
+                                            info[3 * B:4 * B])
+            else:
+                self.league.record_runs(self.pid, self.opponent, info[B:3 * B].view(B, 2), info[3 * B:4 * B])
             self.episode += B
 
     def play_for(self, seconds: float, max_iterations: int = None) -> int:

@@ -30,6 +30,11 @@ Evaluation: ``--league_eval_episodes=N`` (a config key, default 0 = off) runs ``
 after the last league iteration: every player and stored snapshot against every other, greedy, N games per pair in
 one launch per rank (league.evaluation); the tables land in the summary's ``league_eval``.
 
+Opponent mixture: ``--league_opponents_per_match=K`` (a config key, default 1 = one adversary per match) lets every
+sync draw K opponents and every rollout launch play all of them, one per contiguous block of 16-env groups
+(``LeagueInstance(opponents_per_match=K)``; K is clipped to the launch's ceil(batch_size_run / 16) groups). A match
+entry of the summary then lists ``opponents``.
+
 Output: rank 0 writes ``<local_results_path>/league_<token>/league_config.json`` (arguments + every player's team,
 role and device) and ``payoff.json`` and prints the payoff per team like ``CentralWorker._print_payoff``
 (``central_worker.py:123-131``); the last stdout line is a JSON summary.
@@ -223,7 +228,8 @@ def main(argv=None) -> dict:
         from maleague.custom_logging import MainLogger
         logger = MainLogger(args=args)
         inst = LeagueInstance(args, logger, lg, mode="matchmaking" if roles[0] is None else "rolebased",
-                              role=None if roles[0] is None else roles, seed=seed, teams=player_teams)
+                              role=None if roles[0] is None else roles, seed=seed, teams=player_teams,
+                              opponents_per_match=int(cfg.get("league_opponents_per_match", 1) or 1))
         play_s = float(cfg.get("play_time_mins", 1.0)) * 60.0
         runtime_s = float(cfg.get("league_runtime_hours", 0.0)) * 3600.0
         if a.pretrain_iterations is not None:
@@ -240,7 +246,8 @@ def main(argv=None) -> dict:
             if inst.sync() is None:  # no match left for some player: the league ends for everybody
                 break
             n = inst.play_for(play_s if a.match_iterations is None else float("inf"), a.match_iterations)
-            matches.append({"opponent": inst.opponent, "historical": bool(inst.history[-1][2]), "iterations": n,
+            matches.append({"opponent": inst.opponent, "opponents": list(inst.opponents),
+                            "historical": bool(inst.history[-len(inst.opponents)][2]), "iterations": n,
                             "away_team": inst.away_team.tid if inst.away_team is not None else None,
                             "away_codes": inst.away_team.codes() if inst.away_team is not None else None})
             iters += 1

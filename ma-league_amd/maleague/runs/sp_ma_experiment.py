@@ -116,6 +116,24 @@ class LeagueExperiment(SelfPlayMultiAgentExperiment):
         self.home_mac.load_state_dict(agent=agent)
         del agent
 
+    def load_adversary_mix(self, rows, group_opponent, teams=None, home=None):
+        """A match against a mixture of frozen opponents, one per group of 16 envs (SelfPlayParallelStepper
+        .set_opponent_mix): ``rows`` float32 [K, n_params] flat agent parameters on the device (the league's pool rows
+        of the draws), ``group_opponent`` the row of every group. ``teams``: the K opponents' league Teams (or
+        match_build_plan unit lists); opponent k then plays its own roster against ``home`` (this player's team).
+        ``rows = None`` returns to the single adversary of load_adversary_vector."""
+        from ..steppers.self_play_stepper import OpponentMix
+        if rows is None:
+            self.stepper.set_opponent_mix(None)
+            return
+        plans = None
+        if teams is not None:
+            from ..league.teams import match_plan
+            if home is None:
+                raise ValueError("load_adversary_mix: opponent teams need the home team (home=...)")
+            plans = [match_plan(home, t) for t in teams]
+        self.stepper.set_opponent_mix(OpponentMix(rows, group_opponent, plans))
+
     def configure_match(self, home, away=None):
         """LeagueExperimentInstance._configure_experiment(home, away, ai=False) (league_experiment_process.py:57-62):
         plan team 0 = the home team's roster, team 1 = the adversary's (the home roster mirrored when ``away`` is

@@ -2,7 +2,7 @@
 same keys resolve to the entity-env steppers (see build_stepper)."""
 from .entity_stepper import EntityEpisodeStepper, EntityParallelStepper
 from .parallel_stepper import EnvStepper, EpisodeStepper, ParallelStepper
-from .self_play_stepper import SelfPlayParallelStepper, SelfPlayStepper
+from .self_play_stepper import OpponentMix, SelfPlayParallelStepper, SelfPlayStepper
 
 REGISTRY = {"episode": EpisodeStepper, "parallel": ParallelStepper}
 SELF_REGISTRY = {"episode": SelfPlayStepper, "parallel": SelfPlayParallelStepper}
@@ -14,6 +14,6 @@ def build_stepper(args, logger, log_start_t=0):
     return reg[args.runner](args=args, logger=logger, log_start_t=log_start_t)
 
 
-__all__ = ["EnvStepper", "EpisodeStepper", "ParallelStepper", "SelfPlayParallelStepper", "SelfPlayStepper",
+__all__ = ["EnvStepper", "OpponentMix", "EpisodeStepper", "ParallelStepper", "SelfPlayParallelStepper", "SelfPlayStepper",
            "EntityParallelStepper", "EntityEpisodeStepper", "REGISTRY", "SELF_REGISTRY", "ENTITY_REGISTRY",
            "build_stepper"]

@@ -156,6 +156,15 @@ class ParallelStepper(EnvStepper):
         plan must keep the env's shape (units, agents, actions, policy team) -- the batches, replay buffer and MACs
         stay valid; the roles / attack types of every unit follow the plan. The spec travels by value as a kernel
         argument, so runs already queued keep the rosters they were launched with."""
+        env_args, spec = self._spec_of_plan(plan)
+        self.args.env_args = env_args
+        self.spec = spec
+        self.envs.spec = spec
+        self._cspec = spec.to_c()
+
+    def _spec_of_plan(self, plan):
+        """(env_args, spec) of this env with ``plan`` as its match_build_plan; refuses a plan that changes the env's
+        shape (the rule of set_match_build_plan)."""
         env_args = dict(self.args.env_args)
         env_args["match_build_plan"] = plan
         env_args.setdefault("seed", getattr(self.args, "seed", 0))
@@ -166,10 +175,7 @@ class ParallelStepper(EnvStepper):
             raise ValueError(f"match_build_plan changes the env shape (U {old.U} -> {spec.U}, agents {old.n_agents} -> "
                              f"{spec.n_agents}, policy teams {old.n_policy_teams} -> {spec.n_policy_teams}): a "
                              "roster swap keeps the team sizes")
-        self.args.env_args = env_args
-        self.spec = spec
-        self.envs.spec = spec
-        self._cspec = spec.to_c()
+        return env_args, spec
 
     def _to_mlg(self, batch):
         return mlg_batch(batch)

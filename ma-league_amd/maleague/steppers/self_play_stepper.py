@@ -8,8 +8,16 @@ episode with both policies: each side's agents use their own weights and epsilon
 their own EpisodeBatch (obs / avail of that side's agents, the shared global state, ``reward[0]`` for
 home and ``reward[1]`` for away; stepper_utils.build_pre_transition_data, stepper_utils.py:4-24).
 ``run()`` returns ``(home_batch, away_batch, env_infos)`` like the reference.
+
+Opponent mixture (``set_opponent_mix``): one launch of ``mlg_rollout_selfplay_mix`` plays the home policy against one
+away policy -- and one roster -- per group of 16 envs; env b runs exactly as in the plain launch against its group's
+opponent.
 """
 from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+from typing import Optional, Sequence
 
 import torch
 
@@ -20,6 +28,24 @@ from ..controllers.distinct_controller import refuse_distinct
 from ..exceptions import MultiAgentControllerNotInitialized
 from ..modules.agents import DRQNAgentNetwork
 from .parallel_stepper import LazyEnvInfos, ParallelStepper
+
+
+GROUP_ENVS = 16  # envs per mixture group (one rollout workgroup)
+
+
+@dataclass
+class OpponentMix:
+    """The away side of a mixture launch. ``rows``: float32 [K, n_params] device tensor of flat agent parameters
+    (named_parameters() order, any row stride; read when the mix is set). ``group_opponent``: int [G] row of ``rows``
+    for each group of 16 envs, G = ceil(B / 16). ``plans``: optionally one match_build_plan per opponent (K of them):
+    group g then plays under ``plans[group_opponent[g]]``; None: every group plays the stepper's current plan."""
+    rows: torch.Tensor
+    group_opponent: Sequence[int]
+    plans: Optional[Sequence] = None
+
+
+def n_groups(batch_size: int) -> int:
+    return (int(batch_size) + GROUP_ENVS - 1) // GROUP_ENVS
 
 
 class SelfPlayParallelStepper(ParallelStepper):
@@ -34,6 +60,67 @@ class SelfPlayParallelStepper(ParallelStepper):
                              "two-team scenario. Ensure the Self-Play scenario has two teams set to is_scripted=False")
         self.away_batch = None
         self._away_buf = None
+        self._mix = None  # set_opponent_mix: the packed pool and the group / spec tables of the mixture launches
+
+    def set_opponent_mix(self, mix: Optional[OpponentMix]):
+        """Play the next runs against a mixture of frozen opponents, one per group of 16 envs (None: back to the away
+        MAC's own parameters and the plain launch). The rows are packed here (mlg_pack_agent_pool), so later changes
+        of ``mix.rows`` do not reach the launches. The away MAC still gives the architecture and the away epsilon."""
+        if mix is None:
+            self._mix = None
+            return
+        if self.home_mac is None or self.away_mac is None:
+            raise MultiAgentControllerNotInitialized()
+        rows = mix.rows
+        if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_cuda or \
+                (rows.shape[0] > 1 and rows.stride(1) != 1) or rows.shape[0] < 1:
+            raise ValueError("set_opponent_mix: rows must be float32 [K >= 1, n_params] on the device with contiguous "
+                             f"rows, got {rows.dtype} {tuple(rows.shape)} on {rows.device}")
+        K, G = int(rows.shape[0]), n_groups(self.batch_size)
+        table = [int(k) for k in mix.group_opponent]
+        if len(table) != G:
+            raise ValueError(f"set_opponent_mix: group_opponent has {len(table)} entries, {self.batch_size} envs are "
+                             f"{G} groups of {GROUP_ENVS}")
+        if any(k < 0 or k >= K for k in table):
+            raise ValueError(f"set_opponent_mix: group_opponent entries must be rows of the [{K}, n_params] pool")
+        dims = self.away_mac.agent.dims()
+        n_params = sum(p.numel() for p in self.away_mac.agent.parameters())
+        if int(rows.shape[1]) != n_params:
+            raise ValueError(f"set_opponent_mix: rows of {int(rows.shape[1])} floats for an agent of {n_params}")
+        plans = list(mix.plans) if mix.plans is not None else None
+        if plans is not None and len(plans) != K:
+            raise ValueError(f"set_opponent_mix: {len(plans)} plans for {K} opponents (one per opponent)")
+        lib = _native.load(require_gpu=True)
+        psize = int(lib.mlg_packed_agent_size(_native.byref(dims)))
+        if psize < 0:
+            raise _native.NativeError(lib.mlg_last_error().decode())
+        packed = torch.empty(K * psize, dtype=torch.float32, device=self.device)
+        _native.call("mlg_pack_agent_pool", _native.byref(dims), rows.data_ptr(), int(rows.stride(0)), K,
+                     packed.data_ptr(), _native.stream_ptr(self.device))
+        groups = (_native.MlgMixGroup * G)(*[_native.MlgMixGroup(k, k if plans is not None else 0) for k in table])
+        m = {"packed": packed, "K": K, "G": G, "groups": groups, "table": table,
+             "dev_groups": torch.frombuffer(bytearray(bytes(groups)), dtype=torch.uint8).to(self.device),
+             "specs": [self._spec_of_plan(p)[1] for p in plans] if plans is not None else None}
+        self._mix = m
+        self._mix_specs()
+
+    def _mix_specs(self):
+        """The spec array of the mixture (host + device copy): the opponents' plans, else the stepper's current spec
+        (rebuilt when set_match_build_plan swapped it since)."""
+        m = self._mix
+        if m.get("cspecs") is not None and (m["specs"] is not None or m["spec_src"] is self._cspec):
+            return
+        cs = [s.to_c() for s in m["specs"]] if m["specs"] is not None else [self._cspec]
+        m["cspecs"] = (_native.MlgEnvSpec * len(cs))(*cs)
+        m["dev_specs"] = torch.frombuffer(bytearray(bytes(m["cspecs"])), dtype=torch.uint8).to(self.device)
+        m["spec_src"] = self._cspec
+
+    def describe_rollout(self):
+        if self._mix is not None:
+            if self.home_mac is None:
+                raise MultiAgentControllerNotInitialized()
+            return _native.rollout_selfplay_mix_describe(self._cspec, self.home_mac.agent.dims())
+        return super().describe_rollout()
 
     def initialize(self, scheme, groups, preprocess, home_mac, away_mac=None):
         if away_mac is None:
@@ -117,10 +204,21 @@ class SelfPlayParallelStepper(ParallelStepper):
         if self._timed_launch():
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-        _native.call("mlg_rollout_selfplay", _native.byref(self._cspec), _native.byref(st), _native.byref(d),
-                     _native.ptr(p_h), _native.ptr(p_a), _native.byref(mb_h),
-                     _native.byref(mb_a), _native.byref(run_info), float(eps_h), float(eps_a),
-                     int(bool(test_mode)), _native.stream_ptr(self.device))
+        if self._mix is not None:
+            m = self._mix
+            self._mix_specs()
+            cmix = _native.MlgOpponentMix(m["packed"].data_ptr(), m["K"], m["G"], m["dev_groups"].data_ptr(),
+                                          ctypes.addressof(m["groups"]), m["dev_specs"].data_ptr(),
+                                          ctypes.addressof(m["cspecs"]), len(m["cspecs"]))
+            _native.call("mlg_rollout_selfplay_mix", _native.byref(self._cspec), _native.byref(st), _native.byref(d),
+                         _native.ptr(p_h), _native.byref(cmix), _native.byref(mb_h), _native.byref(mb_a),
+                         _native.byref(run_info), float(eps_h), float(eps_a), int(bool(test_mode)),
+                         _native.stream_ptr(self.device))
+        else:
+            _native.call("mlg_rollout_selfplay", _native.byref(self._cspec), _native.byref(st), _native.byref(d),
+                         _native.ptr(p_h), _native.ptr(p_a), _native.byref(mb_h),
+                         _native.byref(mb_a), _native.byref(run_info), float(eps_h), float(eps_a),
+                         int(bool(test_mode)), _native.stream_ptr(self.device))
         if ev is not None:
             ev[1].record()
             self.timing.append(ev)
