@@ -42,6 +42,8 @@
  *   mlg_coma_policy_loss the COMA actor loss         src/marl/learners/coma_learner.py:75-96
  *   mlg_qlearner_*     QLearner.train               src/marl/learners/q_learner.py:34-131
  *                      + clip_grad_norm_ + RMSprop.step (q_learner.py:104-105, learner.py:25-31)
+ *   mlg_per_*          Memory / BinarySumTree / PrioritizedReplayBuffer
+ *                      src/marl/components/replay_buffers/prioritized_replay_buffer.py:8-224
  */
 #ifndef MALEAGUE_H
 #define MALEAGUE_H
@@ -269,6 +271,8 @@ typedef struct {
     float gamma, lr, optim_alpha, optim_eps, grad_norm_clip;
     int32_t agent; /* 0 DRQN (rnn: everything above), 1 feed-forward (dqn): see above */
     int32_t distinct; /* 0 one shared agent, 1 one DRQN per agent slot (mac: distinct): see above */
+    int32_t per;      /* 1: prioritized replay (below): the loss weights MlgLearnerBufs.is_weight and the per-episode
+                         errors td_abs; 0: neither pointer is read and every launch is the one of the unweighted call */
 } MlgLearnerCfg;
 
 typedef struct {
@@ -291,6 +295,14 @@ typedef struct {
                                     [N], one per network, each += the same count */
     const int32_t *host_rows;    /* HOST copy of the slot map (B <= 64): travels as a kernel argument,
                                     batch.rows is then ignored */
+    /* per = 1 only (prioritized replay): loss = sum_b w_b sum_t (mask td)^2 / sum(mask), so d loss / d q_tot =
+     * 2 w_b mtd mask / sum(mask); td_error_abs, q_taken_mean, target_mean, mask_sum and trained_steps stay unweighted.
+     * td_abs[b] = sum_t |mask td| / sum_t mask of episode b (IQL: both sums also over the agents; 0 for an episode with
+     * no masked step): the TD kernel stores each row's |mask td| and one more small launch adds an episode's rows in a
+     * fixed order (no float atomics: the same call gives the same bits). With every weight 1 the parameters, gradients
+     * and stats have the bits of the per = 0 call. describe appends " + per"; the workspace grows by B (T - 1) floats. */
+    const float *is_weight;      /* [B] importance weights (mlg_per_sample) */
+    float *td_abs;               /* [B] out */
 } MlgLearnerBufs;
 
 int64_t mlg_qlearner_param_counts(const MlgLearnerCfg *c, int64_t *n_agent, int64_t *n_mixer);
@@ -310,7 +322,8 @@ int mlg_qlearner_train(const MlgLearnerCfg *c, const MlgLearnerBufs *b, void *st
  * the agent part is dx-h32 | dx-h64 | dx-h128 followed by /bwd-split/q1..q6 (the <H, true> forms of the agent kernels,
  * prep_kernel<true> and the repeating weight-gradient kernels; the H = 64 fused backward is not carried over), e.g.
  * "dx-h64/bwd-split/q1 + qmix-generic"; the mixer part is iql, vdn-fast / vdn, qmix-generic, qmix1-e{E} or
- * qmix-he{HE}-e{E} (no qmix-split: the hypernet tiles ride in the shared agent's recurrence launch only). Nonzero
+ * qmix-he{HE}-e{E} (no qmix-split: the hypernet tiles ride in the shared agent's recurrence launch only). With per = 1
+ * " + per" follows the mixer part (the PER form of the same TD kernel and the per-episode reduce). Nonzero
  * (mlg_last_error) where mlg_qlearner_train would refuse the cfg. */
 int mlg_qlearner_describe(const MlgLearnerCfg *c, char *name, int32_t name_cap);
 
@@ -751,6 +764,35 @@ int mlg_rollout_distinct(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgent
  * refuse the spec or the dims. */
 int mlg_rollout_distinct_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, char *name, int32_t name_cap,
                                   int64_t *lds_bytes);
+
+/* ---- Prioritized episode replay (replay.hip) ----------------------------------------------------
+ * The reference's Memory / BinarySumTree (src/marl/components/replay_buffers/prioritized_replay_buffer.py:8-135) on a
+ * flat fp32 priority vector, one entry per replay slot, in slot order. priority = (|err| + e)^a, formed in double and
+ * rounded once; priorities must be > 0 (e > 0 makes them so). One launch of one workgroup each; nothing is copied to
+ * the host and nothing waits. Every sum and maximum is taken in a fixed order (no float atomics).
+ *
+ * mlg_per_sample: B stratified draws over the slots [0, n_live). cum[j] = the fp64 inclusive sum of priorities[0..j];
+ * total = cum[n_live - 1]; u_i = mlg_u01(mlg_rng(seed, mlg_ctr(draw, 0, MLG_PURPOSE_PER = 6, i)));
+ * s_i = (i + u_i) * total / B in fp64; rows[i] = the first slot j with cum[j] >= s_i (BinarySumTree._retrieve in slot
+ * order; duplicates are possible); is_weight[i] = (n_live p / total)^-beta over the maximum of the B draws, in fp64,
+ * stored as fp32. The scan stays in LDS up to mlg_per_lds_slots() live slots; above that it lives in scan_workspace
+ * (n_live doubles, 16-byte aligned, any contents). Refused by name: n_live > mlg_per_max_slots() (>= 65536), B > 4096,
+ * a missing or short workspace. */
+int32_t mlg_per_lds_slots(void);
+int32_t mlg_per_max_slots(void);
+int mlg_per_sample(const float *priorities, int32_t n_live, int32_t B, uint64_t seed, uint32_t draw, double beta,
+                   int32_t *rows, float *is_weight, double *scan_workspace, int64_t scan_workspace_doubles,
+                   void *stream);
+/* The priorities of the `count` <= ring_size slots (slot0 + k) % ring_size a rollout or an insert just wrote:
+ * *max_priority (a device scalar the caller starts at 1), or with errors [count] the priority of errors[k]; the maximum
+ * is raised to the largest priority written. */
+int mlg_per_insert(float *priorities, int32_t ring_size, int32_t slot0, int32_t count, const float *errors, double e,
+                   double a, float *max_priority, void *stream);
+/* After a train call: priorities[rows[b]] = the priority of td_abs[b] (MlgLearnerBufs.td_abs), rows NULL = identity;
+ * the maximum is raised. Duplicated slots are the same episode and receive the same value. A row outside
+ * [0, n_slots) writes nothing. */
+int mlg_per_update(float *priorities, int32_t n_slots, const int32_t *rows, const float *td_abs, int32_t B, double e,
+                   double a, float *max_priority, void *stream);
 
 const char *mlg_last_error(void);
 const char *mlg_version(void);

@@ -8,6 +8,7 @@
 //   agent_q     fc2 for every (t, row), fully parallel
 //   mix_td      per (b, t) row: gather chosen Q, double-Q target, QMixer fwd (online+target),
 //               TD error, masked MSE partials, QMixer backward -> dQ and mixer deltas         (:55-98)
+//   per_reduce  prioritized replay only (cfg.per = 1): the per-episode errors from the TD kernel's rows
 //   agent_bwd4  reverse-time GRU backward on 4-row tiles (gru4_device.h)                     (:103)
 //   agent_dx    dX = W_ih^T dGI * relu' for every (t, row), fully parallel
 //   wgrad       every weight/bias gradient as sum_rows delta^T x, one wave per 64x64 block and row chunk
@@ -195,7 +196,7 @@ struct WsLayout {
     int64_t p_on, p_tg, wihT, mix_on, mix_tg;
     int64_t in, x, hs, hs_tg, gi_on, gi_tg, gr, gz, gn, ghn, mac, tmac, dq, d2, dgi, dgh, da;
     int64_t srow, l1act, d1, da2, df2, dv2, hyp_on, hyp_tg;
-    int64_t part, msum, rows, mlen, l16, flag, alive, abits, mbits, nrm, slab, total;
+    int64_t part, msum, rows, mlen, l16, flag, alive, abits, mbits, tdrow, nrm, slab, total;
     int n_mix_tiles, n_tasks, hyp_stride;
 };
 
@@ -1192,13 +1193,23 @@ struct MixOut {
     float *srow, *l1act, *d1, *da2, *df2, *dv2, *dq, *d2, *part;
 };
 
+// Prioritized replay (MlgLearnerCfg.per = 1): the PER = true form of each TD kernel scales d loss /
+// d q_tot and the loss partial of episode b by w[b] and stores each live row's masked |td| (IQL: summed over the row's
+// agents) to tdrow [RM]; per_reduce_kernel then adds an episode's rows. The PER = false forms read neither pointer and
+// are the instantiations an unweighted call has always launched. With w = 1 the arithmetic has the same bits: 2 * 1 and
+// 1 * x are exact.
+struct PerIo {
+    const float* w;
+    float* tdrow;
+};
+
 // FAST (state rows of <= 64 features, <= 8 agents, <= 16 actions): the prefetching mixer forward (MixerPF), the
 // backward reusing its hyper_w_1 outputs with the W_a2^T / W_f2^T operands loaded up front, gather_q_pf.
 // Identical arithmetic either way.
-template <int HE, int E, bool FAST = false>
+template <int HE, int E, bool FAST = false, bool PER = false>
 __global__ void __launch_bounds__(128) mix_td_kernel(LCfg c, MlgBatch bt, MixPtrs Mon, MixPtrs Mtg, MixPack mp,
                                                     const float* __restrict__ mac, const float* __restrict__ tmac_,
-                                                    const float* __restrict__ msum_p, MixOut o, Skip sk) {
+                                                    const float* __restrict__ msum_p, MixOut o, Skip sk, PerIo pw) {
     using Mx = Mixer<HE, E>;
     using MP = MixerPF<HE, E, 4, MIXPF_N>;
     floatx4 w1c[MIXPF_N][Mx::TE];  // FAST: the online forward's pre-abs hyper_w_1 outputs
@@ -1269,10 +1280,16 @@ __global__ void __launch_bounds__(128) mix_td_kernel(LCfg c, MlgBatch bt, MixPtr
     }
     const float y = rwd + c.gamma * (1.f - term) * tgt;          // q_learner.py:86
     const float mtd = (qtot - y) * m;                             // :89-95
-    const float dy = 2.f * mtd * m / msum;                        // d loss / d q_tot
+    float dy = 2.f * mtd * m / msum;                              // d loss / d q_tot
+    float wb = 1.f;
+    if constexpr (PER) {  // the weighted loss; this row's share of its episode's error
+        wb = pw.w[b];
+        dy = 2.f * wb * mtd * m / msum;
+        if (live && g == 0) pw.tdrow[rm] = fabsf(mtd);
+    }
     // ---- loss / stat partials (one row per lane of group 0) ----
     {
-        float p0 = g == 0 ? mtd * mtd : 0.f, p1 = g == 0 ? fabsf(mtd) : 0.f;
+        float p0 = g == 0 ? (PER ? wb * (mtd * mtd) : mtd * mtd) : 0.f, p1 = g == 0 ? fabsf(mtd) : 0.f;
         float p2 = g == 0 ? qtot * m : 0.f, p3 = g == 0 ? y * m : 0.f;
         p0 = row_sum16(p0);
         p1 = row_sum16(p1);
@@ -1488,10 +1505,10 @@ struct Mixer1 {
 // to carry a gradient back through: the weight-gradient deltas are the pre-abs hyper outputs' own (da2 [RM][N E] for
 // hyper_w_1, df2 [RM][E] for hyper_w_final, d1 = [b1 | vh] [RM][2 E]), all against the state row; l1act [RM][E] keeps
 // V's hidden activations for V.2.
-template <int E>
+template <int E, bool PER = false>
 __global__ void __launch_bounds__(128) mix_td1_kernel(LCfg c, MlgBatch bt, MixPtrs Mon, MixPtrs Mtg, MixPack mp,
                                                      const float* __restrict__ mac, const float* __restrict__ tmac_,
-                                                     const float* __restrict__ msum_p, MixOut o, Skip sk) {
+                                                     const float* __restrict__ msum_p, MixOut o, Skip sk, PerIo pw) {
     using Mx = Mixer1<E>;
     __shared__ float tgt_sh[16];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
@@ -1531,9 +1548,15 @@ __global__ void __launch_bounds__(128) mix_td1_kernel(LCfg c, MlgBatch bt, MixPt
     const float tgt = tgt_sh[col];
     const float y = rwd + c.gamma * (1.f - term) * tgt;  // q_learner.py:86
     const float mtd = (qtot - y) * m;                     // :89-95
-    const float dy = 2.f * mtd * m / msum;                // d loss / d q_tot
+    float dy = 2.f * mtd * m / msum;                      // d loss / d q_tot
+    float wb = 1.f;
+    if constexpr (PER) {  // the weighted loss; this row's share of its episode's error
+        wb = pw.w[b];
+        dy = 2.f * wb * mtd * m / msum;
+        if (live && g == 0) pw.tdrow[rm] = fabsf(mtd);
+    }
     {
-        float p0 = g == 0 ? mtd * mtd : 0.f, p1 = g == 0 ? fabsf(mtd) : 0.f;
+        float p0 = g == 0 ? (PER ? wb * (mtd * mtd) : mtd * mtd) : 0.f, p1 = g == 0 ? fabsf(mtd) : 0.f;
         float p2 = g == 0 ? qtot * m : 0.f, p3 = g == 0 ? y * m : 0.f;
         p0 = row_sum16(p0);
         p1 = row_sum16(p1);
@@ -1611,9 +1634,10 @@ __global__ void __launch_bounds__(128) mix_td1_kernel(LCfg c, MlgBatch bt, MixPt
 // 16 (b, t) rows, as the mixer kernels' tiles:
 // lane (col, g) takes row col's agents g, g + 4, ... in order; the four groups of a row and then the 16 rows are summed
 // in a fixed order into the tile's four partials. Writes the same sparse dq / d2 deltas as the mixer kernels.
+template <bool PER = false>
 __global__ void __launch_bounds__(64) iql_td_kernel(LCfg c, MlgBatch bt, const float* __restrict__ mac,
                                                    const float* __restrict__ tmac_, float* __restrict__ msum_p,
-                                                   MixOut o, Skip sk) {
+                                                   MixOut o, Skip sk, PerIo pw) {
     const int lane = threadIdx.x, col = lane & 15, g = lane >> 4;
     const float melems = msum_p[0] * (float)c.N;  // sum of the expanded mask (q_learner.py:92)
     if (blockIdx.x == 0 && lane == 0) msum_p[2] = melems;  // finish_kernel's mask sum for this call (msum[2] is free)
@@ -1632,14 +1656,17 @@ __global__ void __launch_bounds__(64) iql_td_kernel(LCfg c, MlgBatch bt, const f
         const float m = mask_at(bt, b, t);
         const float rwd = bt.reward[bslot(bt, b) * bt.T1 + t];
         const float term = (float)bt.terminated[bslot(bt, b) * bt.T1 + t];
+        float wb = 1.f;
+        if constexpr (PER) wb = pw.w[b];
         for (int n = g; n < c.N; n += 4) {
             int a;
             float cq, tq;
             gather_q1(c, bt, mac, tmac, b, t, n, a, cq, tq);
             const float y = rwd + c.gamma * (1.f - term) * tq;  // q_learner.py:86
             const float mtd = (cq - y) * m;                      // :89-95
-            const float dy = 2.f * mtd * m / melems;             // d loss / d Q_chosen[b, t, n]
-            p0 += mtd * mtd;
+            float dy = 2.f * mtd * m / melems;                   // d loss / d Q_chosen[b, t, n]
+            if constexpr (PER) dy = 2.f * wb * mtd * m / melems;
+            p0 += PER ? wb * (mtd * mtd) : mtd * mtd;
             p1 += fabsf(mtd);
             p2 += cq * m;
             p3 += y * m;
@@ -1653,6 +1680,9 @@ __global__ void __launch_bounds__(64) iql_td_kernel(LCfg c, MlgBatch bt, const f
     for (int k = 0; k < 4; ++k) {
         p[k] += __shfl_xor(p[k], 16);
         p[k] += __shfl_xor(p[k], 32);
+        if constexpr (PER) {  // the row's |td| over its agents: groups 0..3 in this fixed order
+            if (k == 1 && live && g == 0) pw.tdrow[rm] = p[1];
+        }
         p[k] = row_sum16(p[k]);
     }
     if (lane == 0) {
@@ -1748,10 +1778,10 @@ __global__ void __launch_bounds__(512) rec4_mixpre_kernel(LCfg c, AgentLayout L,
     mix_pre_tile<64, 32>(c, bt, Mon, Mtg, mp, o, sk, tile, w & 1, threadIdx.x & 63);
 }
 
-template <int HE, int E>
+template <int HE, int E, bool PER = false>
 __global__ void __launch_bounds__(128) mix_td2_kernel(LCfg c, MlgBatch bt, MixPtrs Mon, const float* __restrict__ mac,
                                                       const float* __restrict__ tmac_, const float* __restrict__ msum_p,
-                                                      HypOut hy, MixOut o, Skip sk) {
+                                                      HypOut hy, MixOut o, Skip sk, PerIo pw) {
     using Mx = Mixer<HE, E>;
     using MP = MixerPF<HE, E, 4, MIXPF_N>;
     constexpr int TE = Mx::TE, T1H = Mx::T1H;
@@ -1847,9 +1877,15 @@ __global__ void __launch_bounds__(128) mix_td2_kernel(LCfg c, MlgBatch bt, MixPt
     const float tgt = tgt_sh[col];
     const float y = rwd + c.gamma * (1.f - term) * tgt;  // q_learner.py:86
     const float mtd = (qtot - y) * m;                     // :89-95
-    const float dy = 2.f * mtd * m / msum;                // d loss / d q_tot
+    float dy = 2.f * mtd * m / msum;                      // d loss / d q_tot
+    float wb = 1.f;
+    if constexpr (PER) {  // the weighted loss; this row's share of its episode's error
+        wb = pw.w[b];
+        dy = 2.f * wb * mtd * m / msum;
+        if (live && g == 0) pw.tdrow[rm] = fabsf(mtd);
+    }
     {
-        float p0 = g == 0 ? mtd * mtd : 0.f, p1 = g == 0 ? fabsf(mtd) : 0.f;
+        float p0 = g == 0 ? (PER ? wb * (mtd * mtd) : mtd * mtd) : 0.f, p1 = g == 0 ? fabsf(mtd) : 0.f;
         float p2 = g == 0 ? qtot * m : 0.f, p3 = g == 0 ? y * m : 0.f;
         p0 = row_sum16(p0);
         p1 = row_sum16(p1);
@@ -2053,6 +2089,28 @@ __global__ void __launch_bounds__(512) agent_dx_kernel(LCfg c, const float* __re
 }
 
 // ================================================================================================
+// Prioritized replay: td_abs[b] = sum_t tdrow[b (T - 1) + t] / (div sum_t mask(b, t)) over the episode's live
+// transitions t < mlen[b] (the rows the PER form of the TD kernel stored in this call), div = N for IQL (the mask
+// expanded over the agents), else 1; 0 for an episode with no masked step. One wave per episode: lane l adds the steps
+// l, l + 64, ... in ascending order, then the 64 partial sums meet in a butterfly -- a fixed order, no atomics.
+__global__ void __launch_bounds__(64) per_reduce_kernel(LCfg c, MlgBatch bt, const float* __restrict__ tdrow, Skip sk,
+                                                       float div, float* __restrict__ td_abs) {
+    const int b = blockIdx.x, lane = threadIdx.x, Tm = c.T - 1;
+    const int n = min((int)sk.mlen[b], Tm);
+    float e = 0.f, m = 0.f;
+    for (int t = lane; t < n; t += 64) {
+        e += tdrow[(int64_t)b * Tm + t];
+        m += mask_at(bt, b, t);
+    }
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        e += __shfl_xor(e, k);
+        m += __shfl_xor(m, k);
+    }
+    if (lane == 0) td_abs[b] = m > 0.f ? e / (m * div) : 0.f;
+}
+
+// ================================================================================================
 // clip_grad_norm_ + RMSprop over all parameters (grid-wide; every block derives the same norm from the
 // per-block partials in a fixed order), loss/stat reduction in block 0, which also reports the planned forward blocks
 // (stats[7]) and clears Skip::flag for the next call.
@@ -2117,6 +2175,7 @@ struct Plan {
     WsLayout w;
     int64_t n_agent, n_mixer;
     int layers;  // qmix hypernet_layers (1 or 2)
+    int per;     // MlgLearnerCfg.per: the PER forms of the TD kernels + per_reduce_kernel
 };
 
 int check_cfg(const MlgLearnerCfg* c) {
@@ -2138,6 +2197,7 @@ int check_cfg(const MlgLearnerCfg* c) {
         MLG_REQUIRE(!c->obs_agent_id, "learner: obs_agent_id=%d with distinct=1 unsupported (a slot's network is its id)",
                     c->obs_agent_id);
     }
+    MLG_REQUIRE(c->per == 0 || c->per == 1, "learner: per=%d unsupported (0 uniform replay, 1 prioritized replay)", c->per);
     if (c->mixer == 2) {
         MLG_REQUIRE(c->hypernet_layers == 1 || c->hypernet_layers == 2, "learner: qmix hypernet_layers=%d unsupported (1, 2)",
                     c->hypernet_layers);
@@ -2175,6 +2235,7 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
     c.ff = cfg->agent == 1;
     c.dx = cfg->distinct == 1;
     p.layers = cfg->mixer == 2 ? cfg->hypernet_layers : 2;
+    p.per = cfg->per;
     MlgAgentDims d{cfg->d_obs, cfg->A, cfg->N, cfg->H, c.d_in, cfg->obs_last_action, cfg->obs_agent_id};
     p.L = c.ff ? make_ff_layout(d) : make_agent_layout(d);
     p.ao = c.ff ? ff_offs(c.H, c.d_in, c.A) : agent_offs(c.H, c.d_in, c.A);
@@ -2233,6 +2294,7 @@ Plan make_plan(const MlgLearnerCfg* cfg, int T1) {
     w.alive = take(c.dx ? c.N : 0);  // distinct networks: a word per slot (prep_kernel<true>)
     w.abits = take((T * R + 31) / 32);
     w.mbits = take((RM + 31) / 32);
+    w.tdrow = take(p.per ? RM : 0);  // prioritized replay only: the rows' masked |td| (PerIo)
     w.nrm = 0;  // placed after the slab (size known once the jobs are built)
     w.slab = o;
     w.total = o;  // + slab size, filled by make_jobs
@@ -2382,8 +2444,8 @@ int make_dispatch(const Plan& p, Dispatch* out) {
 }
 
 // "<agent part> + <mixer part>" of a dispatch (mlg_qlearner_describe; the names are listed in maleague.h)
-void dispatch_name(const LCfg& c, const Dispatch& d, char* name, size_t cap) {
-    char mix[32];
+void dispatch_name(const LCfg& c, const Dispatch& d, int per, char* name, size_t cap) {
+    char mix[40];
     switch (d.mix) {
         case MIX_IQL: snprintf(mix, sizeof mix, "iql"); break;
         case MIX_VDN_FAST: snprintf(mix, sizeof mix, "vdn-fast"); break;
@@ -2394,6 +2456,7 @@ void dispatch_name(const LCfg& c, const Dispatch& d, char* name, size_t cap) {
         case MIX_QMIX1: snprintf(mix, sizeof mix, "qmix1-e%d", c.E); break;
         case MIX_QMIX_WIDTHS: snprintf(mix, sizeof mix, "qmix-he%d-e%d", c.HE, c.E); break;
     }
+    if (per) strcat(mix, " + per");  // the PER forms of the TD kernel and per_reduce_kernel
     if (c.ff) snprintf(name, cap, "ff-h%d/q%d + %s", c.H, d.q_tiles, mix);
     else if (c.dx) snprintf(name, cap, "dx-h%d/bwd-split/q%d + %s", c.H, d.q_tiles, mix);
     else snprintf(name, cap, "h%d/%s/q%d + %s", c.H, d.fused ? "bwd-fused" : "bwd-split", d.q_tiles, mix);
@@ -2555,42 +2618,63 @@ int run_train(Plan& p, const MlgLearnerCfg* cfg, const MlgLearnerBufs* bufs, hip
                            ws + p.w.p_tg, ws + p.w.hs, ws + p.w.hs_tg, ws + p.w.mac, ws + p.w.tmac, sk);
     MixOut mo{ws + p.w.srow, ws + p.w.l1act, ws + p.w.d1, ws + p.w.da2, ws + p.w.df2, ws + p.w.dv2,
               ws + p.w.dq, ws + p.w.d2, ws + p.w.part};
-#define MLG_MIX_LAUNCH(K)                                                                                       \
+    // prioritized replay: the <.., true> form of the same kernel, then the per-episode reduce. <.., false> is the
+    // instantiation the defaulted template arguments name: an unweighted call launches what it always has.
+    const bool per = p.per != 0;
+    const PerIo pw{per ? bufs->is_weight : nullptr, per ? ws + p.w.tdrow : nullptr};
+#define MLG_MIX_LAUNCH_K(K)                                                                                     \
     hipLaunchKernelGGL((K), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, Mtg, p.mp, ws + p.w.mac, ws + p.w.tmac, \
-                       ws + p.w.msum, mo, sk)
+                       ws + p.w.msum, mo, sk, pw)
+#define MLG_MIX_LAUNCH(K, ...)                                     \
+    do {                                                           \
+        if (per) MLG_MIX_LAUNCH_K((K<__VA_ARGS__, true>));         \
+        else MLG_MIX_LAUNCH_K((K<__VA_ARGS__, false>));            \
+    } while (0)
     switch (dsp.mix) {
         case MIX_IQL:
-            hipLaunchKernelGGL(iql_td_kernel, dim3(p.w.n_mix_tiles), dim3(64), 0, s, c, bt, ws + p.w.mac, ws + p.w.tmac,
-                               ws + p.w.msum, mo, sk);
+            if (per)
+                hipLaunchKernelGGL(iql_td_kernel<true>, dim3(p.w.n_mix_tiles), dim3(64), 0, s, c, bt, ws + p.w.mac,
+                                   ws + p.w.tmac, ws + p.w.msum, mo, sk, pw);
+            else
+                hipLaunchKernelGGL(iql_td_kernel<false>, dim3(p.w.n_mix_tiles), dim3(64), 0, s, c, bt, ws + p.w.mac,
+                                   ws + p.w.tmac, ws + p.w.msum, mo, sk, pw);
             break;
         case MIX_QMIX_SPLIT:
-            hipLaunchKernelGGL((mix_td2_kernel<64, 32>), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon, ws + p.w.mac,
-                               ws + p.w.tmac, ws + p.w.msum, hy, mo, sk);
+            if (per)
+                hipLaunchKernelGGL((mix_td2_kernel<64, 32, true>), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon,
+                                   ws + p.w.mac, ws + p.w.tmac, ws + p.w.msum, hy, mo, sk, pw);
+            else
+                hipLaunchKernelGGL((mix_td2_kernel<64, 32, false>), dim3(p.w.n_mix_tiles), dim3(128), 0, s, c, bt, Mon,
+                                   ws + p.w.mac, ws + p.w.tmac, ws + p.w.msum, hy, mo, sk, pw);
             break;
         case MIX_VDN_FAST:
-        case MIX_QMIX_FAST1: MLG_MIX_LAUNCH((mix_td_kernel<64, 32, true>)); break;
+        case MIX_QMIX_FAST1: MLG_MIX_LAUNCH(mix_td_kernel, 64, 32, true); break;
         case MIX_QMIX1:
-            if (c.E == 16) MLG_MIX_LAUNCH(mix_td1_kernel<16>);
-            else if (c.E == 32) MLG_MIX_LAUNCH(mix_td1_kernel<32>);
-            else MLG_MIX_LAUNCH(mix_td1_kernel<64>);
+            if (c.E == 16) MLG_MIX_LAUNCH(mix_td1_kernel, 16);
+            else if (c.E == 32) MLG_MIX_LAUNCH(mix_td1_kernel, 32);
+            else MLG_MIX_LAUNCH(mix_td1_kernel, 64);
             break;
         case MIX_VDN:
-        case MIX_QMIX_DFLT: MLG_MIX_LAUNCH((mix_td_kernel<64, 32>)); break;
+        case MIX_QMIX_DFLT: MLG_MIX_LAUNCH(mix_td_kernel, 64, 32, false); break;
         case MIX_QMIX_WIDTHS:
             switch (c.HE * 1000 + c.E) {
-                case 32016: MLG_MIX_LAUNCH((mix_td_kernel<32, 16>)); break;
-                case 32032: MLG_MIX_LAUNCH((mix_td_kernel<32, 32>)); break;
-                case 32064: MLG_MIX_LAUNCH((mix_td_kernel<32, 64>)); break;
-                case 64016: MLG_MIX_LAUNCH((mix_td_kernel<64, 16>)); break;
-                case 64064: MLG_MIX_LAUNCH((mix_td_kernel<64, 64>)); break;
-                case 128016: MLG_MIX_LAUNCH((mix_td_kernel<128, 16>)); break;
-                case 128032: MLG_MIX_LAUNCH((mix_td_kernel<128, 32>)); break;
-                case 128064: MLG_MIX_LAUNCH((mix_td_kernel<128, 64>)); break;
+                case 32016: MLG_MIX_LAUNCH(mix_td_kernel, 32, 16, false); break;
+                case 32032: MLG_MIX_LAUNCH(mix_td_kernel, 32, 32, false); break;
+                case 32064: MLG_MIX_LAUNCH(mix_td_kernel, 32, 64, false); break;
+                case 64016: MLG_MIX_LAUNCH(mix_td_kernel, 64, 16, false); break;
+                case 64064: MLG_MIX_LAUNCH(mix_td_kernel, 64, 64, false); break;
+                case 128016: MLG_MIX_LAUNCH(mix_td_kernel, 128, 16, false); break;
+                case 128032: MLG_MIX_LAUNCH(mix_td_kernel, 128, 32, false); break;
+                case 128064: MLG_MIX_LAUNCH(mix_td_kernel, 128, 64, false); break;
                 default: return mlg::fail("learner: no mixer kernel for hypernet_embed=%d mixing_embed_dim=%d", c.HE, c.E);
             }
             break;
     }
 #undef MLG_MIX_LAUNCH
+#undef MLG_MIX_LAUNCH_K
+    if (per)
+        hipLaunchKernelGGL(per_reduce_kernel, dim3(c.B), dim3(64), 0, s, c, bt, ws + p.w.tdrow, sk,
+                           c.mixer == 0 ? (float)c.N : 1.f, bufs->td_abs);
     // weight gradients: fc2 and the mixer's jobs (final after the mixer kernel, table view JA) run as extra
     // workgroups of the reverse-recurrence launch (H = 64, bwd4_wgrad_kernel); fc1 / W_ih / W_hh (view JB) after
     // agent_dx; one reduce over the whole table
@@ -2683,7 +2767,7 @@ extern "C" int mlg_qlearner_describe(const MlgLearnerCfg* c, char* name, int32_t
     Dispatch d;
     if (make_dispatch(p, &d)) return 1;
     char full[64];
-    dispatch_name(p.c, d, full, sizeof full);
+    dispatch_name(p.c, d, p.per, full, sizeof full);
     MLG_REQUIRE((size_t)name_cap > strlen(full), "qlearner_describe: name buffer of %d bytes too small", name_cap);
     strcpy(name, full);
     return 0;
@@ -2699,6 +2783,7 @@ extern "C" int mlg_qlearner_train(const MlgLearnerCfg* c, const MlgLearnerBufs* 
     MLG_REQUIRE(bt.B == c->B && bt.T1 >= c->T, "qlearner_train: batch B=%d T1=%d vs cfg B=%d T=%d", bt.B, bt.T1, c->B, c->T);
     MLG_REQUIRE(!b->host_rows || c->B <= MLG_INLINE_ROWS, "qlearner_train: host_rows needs B <= %d (got %d)",
                 MLG_INLINE_ROWS, c->B);
+    MLG_REQUIRE(!c->per || (b->is_weight && b->td_abs), "qlearner_train: per=1 needs is_weight and td_abs");
     Plan p = make_plan(c, bt.T1);
     hipStream_t s = (hipStream_t)stream;
     if (c->H == 64) return run_train<64>(p, c, b, s);

@@ -72,13 +72,15 @@ class MlgLearnerCfg(ctypes.Structure):
                                               "mixer", "double_q", "obs_last_action", "obs_agent_id"]] + \
                [(n, ctypes.c_float) for n in ["gamma", "lr", "optim_alpha", "optim_eps", "grad_norm_clip"]] + \
                [("agent", ctypes.c_int32),  # 0 DRQN, 1 feed-forward (dqn)
-                ("distinct", ctypes.c_int32)]  # 1: one DRQN per agent slot (mac: distinct), vectors [agent 0 | .. | mixer]
+                ("distinct", ctypes.c_int32),  # 1: one DRQN per agent slot (mac: distinct), vectors [agent 0 | .. | mixer]
+                ("per", ctypes.c_int32)]  # 1: prioritized replay: the loss weights is_weight, the episode errors td_abs
 
 
 class MlgLearnerBufs(ctypes.Structure):
     _fields_ = [("batch", MlgBatch)] + [(n, ctypes.c_void_p) for n in ["params", "grads", "square_avg",
                                                                       "target_params", "workspace", "stats",
-                                                                      "target_sync", "trained_steps", "host_rows"]]
+                                                                      "target_sync", "trained_steps", "host_rows",
+                                                                      "is_weight", "td_abs"]]
 
 
 class MlgEntityEnvSpec(ctypes.Structure):
@@ -225,6 +227,12 @@ SIGNATURES = {
     "mlg_rollout_selfplay_mix": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _I, _P]),
     "mlg_rollout_selfplay_mix_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
     "mlg_league_record_runs_mix": (ctypes.c_int, [_P, _P, _I, _P, _I, _P, ctypes.c_int64, _I, _P]),
+    "mlg_per_lds_slots": (ctypes.c_int32, []),
+    "mlg_per_max_slots": (ctypes.c_int32, []),
+    "mlg_per_sample": (ctypes.c_int, [_P, _I, _I, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double, _P, _P, _P,
+                                      ctypes.c_int64, _P]),
+    "mlg_per_insert": (ctypes.c_int, [_P, _I, _I, _I, _P, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "mlg_per_update": (ctypes.c_int, [_P, _I, _P, _P, _I, ctypes.c_double, ctypes.c_double, _P, _P]),
     "mlg_last_error": (ctypes.c_char_p, []),
     "mlg_version": (ctypes.c_char_p, []),
 }

@@ -26,8 +26,10 @@ def _time_stride_ok(t: torch.Tensor, T1: int) -> bool:
 
 
 def _sampled_view(batch) -> bool:
-    """A SampledEpisodeBatch not yet materialised: kernels read the buffer through its slot map."""
-    return getattr(batch, "host_rows", None) is not None and getattr(batch, "_data", None) is None
+    """A SampledEpisodeBatch not yet materialised: kernels read the buffer through its slot map (host_rows, or a map
+    drawn on the device: device_rows_only)."""
+    mapped = getattr(batch, "host_rows", None) is not None or getattr(batch, "device_rows_only", False)
+    return mapped and getattr(batch, "_data", None) is None
 
 
 def mlg_batch(batch, required=KEYS, device_rows=True):

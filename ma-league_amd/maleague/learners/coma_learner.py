@@ -41,6 +41,9 @@ def build_td_lambda_targets(rewards, terminated, mask, target_qs, n_agents, gamm
 class COMALearner(Learner):
     def __init__(self, mac, scheme, logger, args, name=None):
         super().__init__(mac, scheme, logger, args, name)
+        if getattr(args, "prioritized_replay", False):
+            raise ValueError(f"COMALearner: prioritized_replay=True is not supported (its kernels take no importance weights "
+                             f"and report no per-episode errors); QLearner does")
         self.n_agents = args.n_agents
         self.n_actions = args.n_actions
         for key, want in (("critic_train_mode", "seq"), ("q_nstep", 0)):

@@ -98,6 +98,8 @@ class QLearner(Learner):
         self._last_stats = None
         self._stats_fresh = False
         self.train_calls = 0
+        # prioritized replay: the latest call's per-episode errors (device, [B]) when the batch carried .is_weight
+        self.last_td_abs = None
         # one network per agent slot: mlg_qlearner_train with cfg.distinct = 1; autograd stays enabled for the unrolled
         # branch (MLG_DISTINCT_LEARNER=unrolled), which the fused call never enters (it runs no torch graph)
         self._distinct = isinstance(mac, DistinctMAC)
@@ -167,7 +169,17 @@ class QLearner(Learner):
             self._tviews = [a.seat_trained_counter(self._tcount[i]) for i, a in enumerate(agents)]
         return self._tcount
 
-    def _cfg(self, B, T):
+    def _is_weight(self, batch):
+        """The batch's importance weights (a PrioritizedReplayBuffer sample) as fp32 [B] on the device, else None."""
+        w = getattr(batch, "is_weight", None)
+        if w is None:
+            return None
+        w = torch.as_tensor(w, dtype=torch.float32).to(self.device).contiguous().reshape(-1)
+        if w.numel() != batch.batch_size:
+            raise ValueError(f"is_weight has {w.numel()} entries for {batch.batch_size} episodes")
+        return w
+
+    def _cfg(self, B, T, per=False):
         a = self.args
         d = self._online().dims()
         mixer = 2 if isinstance(self.mixer, QMixer) else (1 if isinstance(self.mixer, VDNMixer) else 0)
@@ -179,7 +191,7 @@ class QLearner(Learner):
                              optim_alpha=float(a.optim_alpha), optim_eps=float(a.optim_eps),
                              grad_norm_clip=float(a.grad_norm_clip),
                              agent=int(not self._distinct and isinstance(self.mac.agent, DQNAgentNetwork)),
-                             distinct=int(self._distinct))
+                             distinct=int(self._distinct), per=int(per))
 
     def train(self, batch, t_env, episode_num: int):
         """q_learner.py:34-131. `t_env` may also be a zero-argument callable, resolved after the device work
@@ -193,7 +205,9 @@ class QLearner(Learner):
             if which != "fused":
                 raise ValueError(f"MLG_DISTINCT_LEARNER={which!r} not recognised (fused, unrolled)")
         lib = _native.load(require_gpu=True)
-        cfg = self._cfg(batch.batch_size, batch.max_seq_length)
+        weights = self._is_weight(batch)
+        cfg = self._cfg(batch.batch_size, batch.max_seq_length, per=weights is not None)
+        td_abs = None if weights is None else torch.empty(batch.batch_size, dtype=torch.float32, device=self.device)
         need = lib.mlg_qlearner_workspace_floats(_native.byref(cfg))
         if need < 0:
             raise _native.NativeError(lib.mlg_last_error().decode())
@@ -212,9 +226,12 @@ class QLearner(Learner):
         bufs = _native.MlgLearnerBufs(mb, self._flat.flat.data_ptr(), self._grads.data_ptr(), self._sq.data_ptr(),
                                       self._tflat.flat.data_ptr(), self._ws.data_ptr(), self._stats.data_ptr(),
                                       self._tflat.flat.data_ptr() if sync else None, counter.data_ptr(),
-                                      None if host_rows is None else host_rows.ctypes.data)
+                                      None if host_rows is None else host_rows.ctypes.data,
+                                      None if weights is None else weights.data_ptr(),
+                                      None if td_abs is None else td_abs.data_ptr())
         _native.call("mlg_qlearner_train", _native.byref(cfg), _native.byref(bufs), _native.stream_ptr(self.device))
         del keep
+        self.last_td_abs = td_abs
         self._step += 1
         self._online().mark_dirty()
         self.train_calls += 1
@@ -283,7 +300,15 @@ class QLearner(Learner):
         mask = mask.expand_as(td)
         mtd = td * mask
         n = mask.sum()
-        loss = (mtd ** 2).sum() / n
+        weights = self._is_weight(batch)  # prioritized replay: the weighted loss, the per-episode errors
+        if weights is None:
+            loss = (mtd ** 2).sum() / n
+            self.last_td_abs = None
+        else:
+            loss = ((mtd ** 2).sum(dim=(1, 2)) * weights).sum() / n
+            with torch.no_grad():
+                ms = mask.sum(dim=(1, 2))
+                self.last_td_abs = torch.where(ms > 0, mtd.abs().sum(dim=(1, 2)) / ms.clamp(min=1), torch.zeros_like(ms))
         self._grads.zero_()
         self._flat.attach_grads(self._grads)  # autograd then accumulates in place
         loss.backward()

@@ -49,6 +49,9 @@ def check_combination(agent, mixer):
 class REFILLearner(Learner):
     def __init__(self, mac, scheme, logger, args, name=None):
         super().__init__(mac, scheme, logger, args, name)
+        if getattr(args, "prioritized_replay", False):
+            raise ValueError(f"REFILLearner: prioritized_replay=True is not supported (its kernels take no importance weights "
+                             f"and report no per-episode errors); QLearner does")
         check_combination(args.agent, args.mixer)
         self.imagine = args.agent == "imagine_entity_attend_rnn"
         if getattr(args, "weight_decay", 0):

@@ -12,7 +12,7 @@ from types import SimpleNamespace
 
 import torch
 
-from ..components.replay_buffer import ReplayBuffer
+from ..components.replay_buffer import PrioritizedReplayBuffer, ReplayBuffer
 from ..components.transforms import OneHot
 from ..controllers import REGISTRY as mac_REGISTRY
 from ..learners import REGISTRY as learner_REGISTRY
@@ -108,9 +108,18 @@ class MultiAgentExperiment:
 
     def _build_learners(self):
         a = self.args
-        self.home_buffer = ReplayBuffer(self.scheme, self.groups, a.buffer_size, self.env_info["episode_limit"] + 1,
-                                        preprocess=self.preprocess,
-                                        device="cpu" if a.buffer_cpu_only else a.device)
+        device = "cpu" if a.buffer_cpu_only else a.device
+        if getattr(a, "prioritized_replay", False):  # prioritized episode replay for the home learner
+            buf = PrioritizedReplayBuffer(self.scheme, self.groups, a.buffer_size, self.env_info["episode_limit"] + 1,
+                                          preprocess=self.preprocess, device=device, seed=int(getattr(a, "seed", 0) or 0))
+            buf.a = float(getattr(a, "per_alpha", buf.a))
+            buf.e = float(getattr(a, "per_eps", buf.e))
+            buf.beta = float(getattr(a, "per_beta", buf.beta))
+            buf.beta_increment_per_sampling = float(getattr(a, "per_beta_increment", buf.beta_increment_per_sampling))
+            self.home_buffer = buf
+        else:
+            self.home_buffer = ReplayBuffer(self.scheme, self.groups, a.buffer_size, self.env_info["episode_limit"] + 1,
+                                            preprocess=self.preprocess, device=device)
         self.home_mac = mac_REGISTRY[a.mac](scheme=self.home_buffer.scheme, groups=self.groups, args=a)
         self.home_learner = learner_REGISTRY[a.learner](mac=self.home_mac, scheme=self.home_buffer.scheme,
                                                         logger=self.logger, args=a, name="home")
@@ -202,13 +211,22 @@ class MultiAgentExperiment:
                 # and t_env resolves only after the learner is queued -- no host sync between the launches
                 sample = self.home_buffer.sample(self.args.batch_size, view=True)
                 self.home_learner.train(sample, LazyTEnv(self.stepper), episode_num)
+                self._update_priorities(sample)
                 return
-            sample = self.home_buffer.sample(self.args.batch_size)
+            drawn = sample = self.home_buffer.sample(self.args.batch_size)
             max_ep_t = int(sample.max_t_filled())
             sample = sample[:, :max_ep_t]
+            if hasattr(drawn, "is_weight"):  # a prioritized sample: the truncated copy trains with its weights
+                sample.is_weight = drawn.is_weight
             if str(sample.device) != str(self.args.device):
                 sample.to(self.args.device)
             self.home_learner.train(sample, self.stepper.t_env, episode_num)
+            self._update_priorities(drawn)
+
+    def _update_priorities(self, sample):
+        """Prioritized replay: the sampled slots take the priorities of the errors the train call just reported."""
+        if isinstance(self.home_buffer, PrioritizedReplayBuffer):
+            self.home_buffer.update_priorities(sample, self.home_learner.last_td_abs)
 
     def _test(self, n_test_runs):
         self.last_test_T = self.stepper.t_env
