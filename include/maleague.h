@@ -642,6 +642,35 @@ int mlg_rollout_policy(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgentDi
 int mlg_rollout_policy_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, char *name, int32_t name_cap,
                                 int64_t *lds_bytes);
 
+/* One full SelfPlayPolicyParallelStepper.run: two pi_logits MACs in one launch. The arguments of mlg_rollout_selfplay
+ * plus mask_before_softmax and test_greedy (one value for both sides). Semantics: mlg_rollout_selfplay on the generic
+ * fp32 arm with the selection site of mlg_rollout_policy on both sides. Side s (0 home, 1 away) uses its own weights
+ * and its own epsilon floor (eps_home / eps_away; zero in test mode). Agent a = s * nh + ln of env b draws
+ * mlg_u01(mlg_rng(mlg_env_key(seed, b), mlg_ctr(episode, t, MLG_PURPOSE_POLICY, a))). Each side is recorded into its
+ * own batch as a test-mode pick (the floor is in the probabilities: no epsilon-greedy redraw). reward[0] / reward[1],
+ * ret_away and the ring / full-write / slot_extent modes are mlg_rollout_selfplay's. Refuses, through mlg_last_error
+ * and without launching, more than 16 agents per side (2 nh tiles over at most 8 waves, at most 4 per wave), hidden
+ * widths other than 32 / 64 / 128 and n_actions beyond five 16-wide action tiles. One launch. */
+int mlg_rollout_selfplay_policy(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgentDims *dims,
+                                const float *home_packed, const float *away_packed, MlgBatch *home, MlgBatch *away,
+                                MlgRunInfo *info, float eps_home, float eps_away, int32_t test_mode,
+                                int32_t mask_before_softmax, int32_t test_greedy, void *stream);
+
+/* Host only, launches nothing (the contract of mlg_rollout_describe). Names: "sp-policy-lds/tpwK" (both sides' weight
+ * images staged in LDS: when both fit beside the env state, H = 32) / "sp-policy-global/tpwK" (weights read from global
+ * memory; MLG_ROLLOUT_GLOBAL_WEIGHTS forces it), K = 1..4 agent tiles per wave. mlg_rollout_selfplay_policy takes its
+ * decision from the same function. Nonzero (mlg_last_error) where it would refuse the spec or the dims. */
+int mlg_rollout_selfplay_policy_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, char *name,
+                                         int32_t name_cap, int64_t *lds_bytes);
+
+/* mlg_crossplay_rollout for pi_logits policies: the same MlgCrossplay block, checks, outputs and summary; the pick is
+ * mlg_rollout_policy's in test mode. test_greedy = 1: the first-index argmax of the masked probabilities; 0: a draw
+ * from the floor-less probabilities on the counter RNG above with c->episode0 as the episode counter. The per-env
+ * results of pair k are bit-identical to one test-mode mlg_rollout_selfplay_policy launch of that pair (env index e,
+ * episode counter episode0) on the global arm. */
+int mlg_crossplay_rollout_policy(const MlgAgentDims *dims, const MlgCrossplay *c, int32_t mask_before_softmax,
+                                 int32_t test_greedy, void *stream);
+
 /* The COMA actor loss (coma_learner.py:75-96), forward and d loss / d pi in one launch. rows = B (T - 1) mask entries,
  * pi / avail / q_vals [rows][N][A], actions [rows][N], mask [rows]: pi is zeroed where unavailable and renormalised,
  * baseline = sum pi q, advantage = q_taken - baseline (a constant for the gradient), pi_taken = 1 where mask == 0,

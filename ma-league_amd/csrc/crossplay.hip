@@ -12,12 +12,19 @@
 // (agent_cell_hidden / agent_q_tile / argmax_*) in the same order, same env step. Env (pair k, episode e) runs as env
 // index e with episode counter episode0, so the results are bit-identical to one mlg_rollout_selfplay per pair.
 //
+// mlg_crossplay_rollout_policy plays pi_logits policies (COMA): the POLICY = true instantiation of the same kernel, whose
+// pick is rollout_policy.hip's test-mode selection (ro_policy_select, coma_device.h) -- the first-index argmax of the
+// masked probabilities, or a draw from the floor-less probabilities on the counter RNG with episode0 as the episode
+// counter. Its per-env results are bit-identical to one test-mode mlg_rollout_selfplay_policy per pair on the global
+// arm.
+//
 // RE, SpecShared, load_spec_tables and ro_take come from rollout_env_device.h, check_spec, LDS_LIMIT_BYTES and allow_lds
 // from rollout_host.h (shared with rollout.hip). cp_observe / cp_env_step are this file's own: the env step without an
 // EpisodeBatch.
 #include <cstdlib>
 
 #include "agent_device.h"
+#include "coma_device.h"
 #include "rollout_env_device.h"
 #include "rollout_host.h"
 
@@ -83,6 +90,8 @@ struct CpArgs {
     const MlgEnvSpec* specs;
     int n_pool, n_specs, wg_per_pair, E;
     uint32_t episode0;
+    int flags;  // POLICY only: bit 1 mask_before_softmax, bit 2 test_greedy (rollout_policy_kernel's flags, test mode);
+                // in what was padding: the Q instantiations read their arguments where they did
     float* workspace;  // used iff the rows are not in LDS: [grid][obs_words + avail_words]
     int32_t* ep_len;
     float *ret, *ret_away;
@@ -173,7 +182,7 @@ __device__ void cp_env_step(const EnvTables& T, const SpecShared& SS, const CpSh
     cp_observe(T, SS, sh, R, true, inv_p);
 }
 
-template <int H, int TPW>
+template <int H, int TPW, bool POLICY = false>
 __global__ void __launch_bounds__(512) crossplay_kernel(CpArgs a, CpShape sh, AgentLayout L, CpLds lay) {
     constexpr int HC = H / 16;
     extern __shared__ __attribute__((aligned(16))) int smem[];
@@ -288,12 +297,26 @@ __global__ void __launch_bounds__(512) crossplay_kernel(CpArgs a, CpShape sh, Ag
             in.agent = valid ? ln : 0;
             agent_cell_hidden<H>(Wv, L, in, h[ti], lane);
             const int32_t* av = valid ? R.lavail + (e * N + ag) * A : nullptr;
-            ArgmaxState as{-INFINITY, 1 << 30};
-            for (int at = 0; at < n_at; ++at) {
-                const floatx4 q = agent_q_tile<H>(Wv, h[ti], at, lane);
-                argmax_accumulate(as, q, av, at, A, lane);
+            int act;
+            if constexpr (POLICY) {  // rollout_policy_kernel's selection site in test mode
+                floatx4 qt[RO_MAXAT];
+#pragma unroll
+                for (int at = 0; at < RO_MAXAT; ++at)
+                    qt[at] = at < n_at ? agent_q_tile<H>(Wv, h[ti], at, lane) : floatx4{0.f, 0.f, 0.f, 0.f};
+                const bool greedy = (a.flags & 4) != 0;
+                float u = 0.f;
+                if (valid && !greedy)
+                    u = mlg_u01(mlg_rng(mlg_env_key(sh.seed, e0 + e),
+                                        mlg_ctr(a.episode0, (uint32_t)t, MLG_PURPOSE_POLICY, (uint32_t)ag)));
+                act = ro_policy_select(qt, n_at, av, A, lane, 0.f, (a.flags & 2) != 0, true, greedy, u);
+            } else {
+                ArgmaxState as{-INFINITY, 1 << 30};
+                for (int at = 0; at < n_at; ++at) {
+                    const floatx4 q = agent_q_tile<H>(Wv, h[ti], at, lane);
+                    argmax_accumulate(as, q, av, at, A, lane);
+                }
+                act = argmax_reduce(as);
             }
-            const int act = argmax_reduce(as);
             if (valid && g == 0) R.pact[e * N + ag] = act;
         }
         __syncthreads();
@@ -407,15 +430,17 @@ int check_crossplay_dims(const MlgAgentDims* d) {
     return 0;
 }
 
-template <int H, int TPW>
+template <int H, int TPW, bool POLICY>
 int launch_crossplay(int grid, int threads, hipStream_t s, const CpArgs& a, const CpShape& sh, const AgentLayout& L,
                      const CpLds& lay) {
     const size_t bytes = (size_t)lay.total * 4;
-    auto kern = crossplay_kernel<H, TPW>;
+    auto kern = crossplay_kernel<H, TPW, POLICY>;
     if (int rc = allow_lds(kern, bytes, "crossplay")) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), bytes, s, a, sh, L, lay);
     return 0;
 }
+
+int crossplay_rollout(const MlgAgentDims* dims, const MlgCrossplay* c, bool policy, int flags, void* stream);
 
 }  // namespace
 
@@ -432,6 +457,18 @@ extern "C" int64_t mlg_crossplay_workspace_floats(const MlgAgentDims* dims, int3
 }
 
 extern "C" int mlg_crossplay_rollout(const MlgAgentDims* dims, const MlgCrossplay* c, void* stream) {
+    return crossplay_rollout(dims, c, false, 0, stream);
+}
+
+extern "C" int mlg_crossplay_rollout_policy(const MlgAgentDims* dims, const MlgCrossplay* c,
+                                            int32_t mask_before_softmax, int32_t test_greedy, void* stream) {
+    return crossplay_rollout(dims, c, true, (mask_before_softmax ? 2 : 0) | (test_greedy ? 4 : 0), stream);
+}
+
+namespace {
+
+// Both entry points: the checks, the launch of crossplay_kernel<H, TPW, policy> and the summary.
+int crossplay_rollout(const MlgAgentDims* dims, const MlgCrossplay* c, bool policy, int flags, void* stream) {
     if (check_crossplay_dims(dims)) return 1;
     MLG_REQUIRE(c != nullptr, "crossplay: null argument block");
     MLG_REQUIRE(c->packed_pool && c->pairs && c->host_pairs && c->specs && c->host_specs && c->workspace,
@@ -482,6 +519,8 @@ extern "C" int mlg_crossplay_rollout(const MlgAgentDims* dims, const MlgCrosspla
     MLG_REQUIRE(grid64 <= 0x7fffffff && (int64_t)c->n_pairs * c->E <= 0x3fffffff,
                 "crossplay: n_pairs=%d x E=%d is too large for one launch", c->n_pairs, c->E);
     const AgentLayout L = make_agent_layout(*dims);
+    MLG_REQUIRE(!policy || L.Ap <= 16 * RO_MAXAT, "crossplay: n_actions=%d does not fit %d action tiles (policy pick)",
+                dims->n_actions, RO_MAXAT);
     const int tiles = 2 * ((RE * nh + 15) / 16);
     const int W = tiles < 8 ? tiles : 8;
     const int tpw = (tiles + W - 1) / W;
@@ -508,6 +547,7 @@ extern "C" int mlg_crossplay_rollout(const MlgAgentDims* dims, const MlgCrosspla
     a.ret_away = c->ret_away;
     a.won = c->won;
     a.draw = c->draw;
+    a.flags = flags;
     CpShape sh;
     sh.U = s0.U;
     sh.N = s0.n_agents;
@@ -521,7 +561,9 @@ extern "C" int mlg_crossplay_rollout(const MlgAgentDims* dims, const MlgCrosspla
     hipStream_t s = (hipStream_t)stream;
     const int grid = (int)grid64, threads = W * 64;
     int rc = 0;
-#define MLG_CP(HH, TT) rc = launch_crossplay<HH, TT>(grid, threads, s, a, sh, L, lay)
+#define MLG_CP(HH, TT)                                                                           \
+    rc = policy ? launch_crossplay<HH, TT, true>(grid, threads, s, a, sh, L, lay) \
+                : launch_crossplay<HH, TT, false>(grid, threads, s, a, sh, L, lay)
 #define MLG_CP_H(HH)                   \
     do {                               \
         if (tpw == 1) MLG_CP(HH, 1);   \
@@ -541,6 +583,8 @@ extern "C" int mlg_crossplay_rollout(const MlgAgentDims* dims, const MlgCrosspla
                        c->draw, c->E, c->summary);
     return mlg::check_launch("crossplay_summary_kernel");
 }
+
+}  // namespace
 
 extern "C" int mlg_pack_agent_pool(const MlgAgentDims* dims, const float* flat, int64_t row_stride, int32_t P,
                                    float* packed_pool, void* stream) {

@@ -1,4 +1,5 @@
-// rollout_policy.hip -- one ParallelStepper.run with a pi_logits MAC (COMA): mlg_rollout_policy.
+// rollout_policy.hip -- one ParallelStepper.run with a pi_logits MAC (COMA): mlg_rollout_policy, and one
+// SelfPlayPolicyParallelStepper.run with two of them: mlg_rollout_selfplay_policy.
 //
 // The generic fp32 rollout kernel (rollout.hip's rollout_kernel: a workgroup owns RE = 16 envs for the whole episode,
 // wave w owns the 16-row agent tiles w, w + W, ..., GRU hidden state in VGPRs, env state in LDS) with the selection
@@ -20,108 +21,14 @@ int check_agent_dims(const MlgAgentDims* d);  // agent.hip
 
 namespace {
 
-// Multinomial policy pick for the lane's row (mlg_rollout_policy: MultiAgentController._softmax,
-// multi_agent_controller.py:78-99, then MultinomialActionSelector.select, action_selectors.py:11-32, with the draw rule
-// of mlg_select_multinomial). qt[at][r] is the logit of action 16 at + 4 g + r; the four lanes col + 16 g of a row
-// share the work and every one returns the action. Sums add each lane's four entries first, then the lanes in
-// ascending g, then the tiles in ascending order. All 64 lanes must be active; av == nullptr: every action available.
-constexpr int RO_MAXAT = 5;  // n_actions = 5 + U <= 69 fits five 16-wide tiles
-__device__ __forceinline__ int ro_policy_select(floatx4 (&qt)[RO_MAXAT], int n_at, const int32_t* av, int A, int lane,
-                                                float eps, bool mask, bool test_mode, bool greedy, float u) {
-    const int g = lane >> 4;
-    auto xor_f = [](float v, int m) { return __shfl_xor(v, m); };
-    unsigned ok = 0u;  // bit 4 at + r: the action is in range and available
-    float mx = -INFINITY;
-#pragma unroll
-    for (int at = 0; at < RO_MAXAT; ++at)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int a = at * 16 + 4 * g + r;
-            const bool in = at < n_at && a < A;
-            const bool on = in && (av == nullptr || av[a] != 0);
-            ok |= (unsigned)on << (4 * at + r);
-            const float x = in ? ((mask && !on) ? -1e10f : qt[at][r]) : -INFINITY;
-            qt[at][r] = x;
-            mx = fmaxf(mx, x);
-        }
-    mx = fmaxf(mx, xor_f(mx, 16));
-    mx = fmaxf(mx, xor_f(mx, 32));
-    int K = __popc(ok);
-    K += __shfl_xor(K, 16);
-    K += __shfl_xor(K, 32);
-    float s = 0.f;
-#pragma unroll
-    for (int at = 0; at < RO_MAXAT; ++at)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            qt[at][r] = expf(qt[at][r] - mx);  // exp(-inf) = 0 for the entries out of range
-            s += qt[at][r];
-        }
-    s += xor_f(s, 16);
-    s += xor_f(s, 32);
-    const float keep = 1.f - eps, floor_p = eps / (float)(mask ? K : A);
-    // m_k: the probability where available, else 0
-#pragma unroll
-    for (int at = 0; at < RO_MAXAT; ++at)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float p = qt[at][r] / s;
-            qt[at][r] = ((ok >> (4 * at + r)) & 1u) ? (test_mode ? p : keep * p + floor_p) : 0.f;
-        }
-    if (greedy) {
-        ArgmaxState as{-INFINITY, 1 << 30};
-#pragma unroll
-        for (int at = 0; at < RO_MAXAT; ++at)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int a = at * 16 + 4 * g + r;
-                const float v = ((ok >> (4 * at + r)) & 1u) ? qt[at][r] : -INFINITY;
-                if (a < A && amax_better(v, a, as.bv, as.bi)) { as.bv = v; as.bi = a; }
-            }
-        const int act = argmax_reduce(as);
-        return act < A ? act : 0;
-    }
-    const int col = lane & 15;
-    float total = 0.f;
-#pragma unroll
-    for (int at = 0; at < RO_MAXAT; ++at) {
-        const float ls = ((qt[at][0] + qt[at][1]) + qt[at][2]) + qt[at][3];
-        total = (((total + __shfl(ls, col)) + __shfl(ls, col + 16)) + __shfl(ls, col + 32)) + __shfl(ls, col + 48);
-    }
-    const float thr = u * total;
-    float run = 0.f;
-    int pick = 1 << 30, last = -1;
-#pragma unroll
-    for (int at = 0; at < RO_MAXAT; ++at) {
-        const float ls = ((qt[at][0] + qt[at][1]) + qt[at][2]) + qt[at][3];
-        const float s0 = __shfl(ls, col), s1 = __shfl(ls, col + 16), s2 = __shfl(ls, col + 32),
-                    s3 = __shfl(ls, col + 48);
-        float c = run;
-        if (g > 0) c += s0;
-        if (g > 1) c += s1;
-        if (g > 2) c += s2;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (!((ok >> (4 * at + r)) & 1u)) continue;
-            const int a = at * 16 + 4 * g + r;
-            c += qt[at][r];
-            last = a;
-            if (pick == (1 << 30) && c > thr) pick = a;
-        }
-        run = (((run + s0) + s1) + s2) + s3;
-    }
-    pick = min(pick, __shfl_xor(pick, 16));
-    pick = min(pick, __shfl_xor(pick, 32));
-    last = max(last, __shfl_xor(last, 16));
-    last = max(last, __shfl_xor(last, 32));
-    return pick != (1 << 30) ? pick : (last >= 0 ? last : 0);
-}
-
-// flags: bit 0 test_mode, bit 1 mask_before_softmax, bit 2 test_greedy. One policy side (sd.ns = 1).
+// flags: bit 0 test_mode, bit 1 mask_before_softmax, bit 2 test_greedy. SP = false: one policy side (sd.ns = 1,
+// mlg_rollout_policy). SP = true: two policy sides (sd.ns = 2, mlg_rollout_selfplay_policy): side s picks with its own
+// weights -- WLDS: the away image follows the home image in LDS -- and its own epsilon floor sd.eps[s]. SP is a
+// template flag, not a branch on sd.ns: the SP = false instantiations are the code they were without it.
 // The body is rollout_kernel's (rollout.hip) line for line but for the selection site; it is written out twice because
 // a shared __forceinline__ body with the selection passed in as a callable made the compiler allocate registers
 // differently in every instantiation of both kernels.
-template <int H, int TPW, bool WLDS>
+template <int H, int TPW, bool WLDS, bool SP = false>
 __global__ void __launch_bounds__(512) rollout_policy_kernel(MlgEnvSpec spec, MlgEnvState st, AgentLayout L, Sides sd,
                                                             MlgRunInfo info, int flags, RolloutLds lay) {
     constexpr int HC = H / 16;
@@ -136,6 +43,7 @@ __global__ void __launch_bounds__(512) rollout_policy_kernel(MlgEnvSpec spec, Ml
     const bool any_full_write = sd.bt[0].full_write || (sd.ns > 1 && sd.bt[1].full_write);
     load_spec_tables(spec, SS);
     if (WLDS) load_weights_to_lds(sd.P[0], L, lay.lw, reinterpret_cast<float*>(smem + lay.wts));
+    if (WLDS && SP) load_weights_to_lds(sd.P[1], L, lay.lw, reinterpret_cast<float*>(smem + lay.wts) + lay.lw.total);
     const EnvTables T = make_tables(spec, SS);
     const float inv_p = 1.0f / (float)pow2_at_least(spec.grid);
     ro_reset<RoNoStamps>(T, SS, spec, st, R, sd, e0, inv_p);
@@ -168,7 +76,8 @@ __global__ void __launch_bounds__(512) rollout_policy_kernel(MlgEnvSpec spec, Ml
             // live across the episode loop in (spilled) registers.
             int zero = 0;
             asm volatile("" : "+s"(zero));
-            const WView Wv = WLDS ? lds_view(reinterpret_cast<const float*>(smem + lay.wts) + zero, lay.lw, L)
+            const int lds_side = (SP && side) ? lay.lw.total : 0;  // SP: the away image follows the home image
+            const WView Wv = WLDS ? lds_view(reinterpret_cast<const float*>(smem + lay.wts) + lds_side + zero, lay.lw, L)
                                   : global_view((side ? sd.P[1] : sd.P[0]) + zero, L);
             const MlgBatch bt = side_batch(sd, side);
             const int64_t bt_off = valid ? ((int64_t)side_slot(R, side, e) * T1 + t) * nh + ln : 0;
@@ -188,7 +97,8 @@ __global__ void __launch_bounds__(512) rollout_policy_kernel(MlgEnvSpec spec, Ml
             if (valid && !greedy)
                 u = mlg_u01(mlg_rng(mlg_env_key(spec.seed, e0 + e),
                                     mlg_ctr(R.episode[e], (uint32_t)t, MLG_PURPOSE_POLICY, (uint32_t)a)));
-            const int act = ro_policy_select(qt, n_at, av, A, lane, sd.eps[0], (flags & 2) != 0, tm, greedy, u);
+            const float eps = (SP && side) ? sd.eps[1] : sd.eps[0];
+            const int act = ro_policy_select(qt, n_at, av, A, lane, eps, (flags & 2) != 0, tm, greedy, u);
             // recorded as a test-mode pick (no epsilon-greedy redraw): the epsilon floor is in the probabilities
             if (valid && g == 0) ro_record_action(spec, R, sd, act, av, e, a, e0 + e, t, 1);
         }
@@ -267,6 +177,78 @@ int launch_policy(const PolicyPlan& p, int grid, hipStream_t s, const MlgEnvSpec
     return launch_policy_t<H, TPW, false>(grid, p.waves * 64, s, spec, st, p.L, sd, info, flags, p.lay);
 }
 
+// ---- two policy sides: mlg_rollout_selfplay_policy -------------------------------------------------------------------
+// plan_selfplay_policy is the one place that decides which rollout_policy_kernel<H, TPW, WLDS, true> runs; the entry
+// point launches what it returns and mlg_rollout_selfplay_policy_describe reports it. Checks what depends on the spec
+// and the agent dims alone. sp-policy-lds: both sides' images in LDS when they fit next to the env state (H = 32; one
+// 3v3 H = 64 image is ~117 KB); sp-policy-global: weights read from HBM / L2, also when MLG_ROLLOUT_GLOBAL_WEIGHTS is
+// set (as it forces v1-global in rollout.hip).
+// The env is the symmetric two-policy-team scenario and `dims` describes one side of it (rollout.hip's check for
+// mlg_rollout_selfplay, under this entry point's name).
+int check_selfplay_dims(const MlgEnvSpec* spec, const MlgAgentDims* dims, const char* who) {
+    MLG_REQUIRE(spec->n_policy_teams == 2 && spec->n_agents % 2 == 0,
+                "%s: %d agents in %d policy teams do not fit the symmetric two-team scenario "
+                "(stepper_utils.py:9)", who, spec->n_agents, spec->n_policy_teams);
+    const int nh = spec->n_agents / 2;
+    MLG_REQUIRE(dims->n_agents == nh && dims->n_actions == spec->n_actions && dims->d_obs == 8 * spec->U,
+                "%s: agent dims do not match one side of the env (N=%d/%d A=%d/%d d_obs=%d/%d)", who,
+                dims->n_agents, nh, dims->n_actions, spec->n_actions, dims->d_obs, 8 * spec->U);
+    for (int a = 0; a < nh; ++a)
+        MLG_REQUIRE(spec->team[spec->agent_unit[a]] == spec->policy_team &&
+                        spec->team[spec->agent_unit[nh + a]] == 1 - spec->policy_team,
+                    "%s: agents 0..%d must be the home team, %d..%d the away team", who, nh - 1, nh, 2 * nh - 1);
+    return 0;
+}
+
+RolloutLds make_selfplay_policy_lds(const AgentLayout& L, int U, int n_agents, bool weights_in_lds) {
+    RolloutLds r;
+    r.lw = make_lds_weights(L);
+    r.weights_in_lds = weights_in_lds;
+    int64_t o = 0;
+    r.wts = ro_take(o, weights_in_lds ? 2 * (int64_t)r.lw.total : 0);  // home image, then away image
+    r.env = make_env_lds(o, U, n_agents);
+    r.total = o;
+    return r;
+}
+
+int plan_selfplay_policy(const MlgEnvSpec* spec, const MlgAgentDims* dims, PolicyPlan* p) {
+    if (check_selfplay_dims(spec, dims, "rollout_selfplay_policy")) return 1;
+    p->L = make_agent_layout(*dims);
+    MLG_REQUIRE(p->L.Ap <= 16 * RO_MAXAT, "rollout_selfplay_policy: n_actions=%d does not fit %d action tiles",
+                dims->n_actions, RO_MAXAT);
+    const int nh = spec->n_agents / 2;
+    const int tiles = 2 * ((RE * nh + 15) / 16);
+    p->waves = tiles < 8 ? tiles : 8;
+    p->tpw = (tiles + p->waves - 1) / p->waves;
+    MLG_REQUIRE(p->tpw <= 4, "rollout_selfplay_policy: %d agent tiles per wave > 4 (more than 16 agents per side)",
+                p->tpw);
+    MLG_REQUIRE(p->L.H == 32 || p->L.H == 64 || p->L.H == 128,
+                "rollout_selfplay_policy: rnn_hidden_dim=%d unsupported (32, 64, 128)", p->L.H);
+    p->lay = make_selfplay_policy_lds(p->L, spec->U, spec->n_agents, true);
+    // the LDS arm is instantiated for H = 32 alone: two H = 64 images never fit
+    p->wlds = p->L.H == 32 && (int64_t)p->lay.total * 4 <= LDS_LIMIT_BYTES && !getenv("MLG_ROLLOUT_GLOBAL_WEIGHTS");
+    if (!p->wlds) {
+        p->lay = make_selfplay_policy_lds(p->L, spec->U, spec->n_agents, false);
+        MLG_REQUIRE((int64_t)p->lay.total * 4 <= LDS_LIMIT_BYTES,
+                    "rollout_selfplay_policy: the env state of %d units does not fit in LDS", spec->U);
+    }
+    snprintf(p->name, sizeof p->name, "sp-policy-%s/tpw%d", p->wlds ? "lds" : "global", p->tpw);
+    return 0;
+}
+
+template <int H, int TPW>
+int launch_selfplay_policy(const PolicyPlan& p, int grid, hipStream_t s, const MlgEnvSpec& spec, const MlgEnvState& st,
+                           const Sides& sd, const MlgRunInfo& info, int flags) {
+    const size_t bytes = (size_t)p.lay.total * 4;
+    auto kern = rollout_policy_kernel<H, TPW, false, true>;
+    if constexpr (H == 32) {
+        if (p.wlds) kern = rollout_policy_kernel<H, TPW, true, true>;
+    }
+    if (int rc = allow_lds(kern, bytes, "rollout_selfplay_policy")) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(p.waves * 64), bytes, s, spec, st, p.L, sd, info, flags, p.lay);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int mlg_rollout_policy_describe(const MlgEnvSpec* spec, const MlgAgentDims* dims, char* name,
@@ -318,4 +300,63 @@ extern "C" int mlg_rollout_policy(const MlgEnvSpec* spec, MlgEnvState* st, const
 #undef MLG_RO
     if (rc) return rc;
     return mlg::check_launch("rollout_policy_kernel");
+}
+
+extern "C" int mlg_rollout_selfplay_policy_describe(const MlgEnvSpec* spec, const MlgAgentDims* dims, char* name,
+                                                    int32_t name_cap, int64_t* lds_bytes) {
+    if (check_spec(spec) || check_agent_dims(dims)) return 1;
+    MLG_REQUIRE(name && name_cap > 0 && lds_bytes, "rollout_selfplay_policy_describe: null output");
+    PolicyPlan plan;
+    if (int rc = plan_selfplay_policy(spec, dims, &plan)) return rc;
+    MLG_REQUIRE((size_t)name_cap > strlen(plan.name),
+                "rollout_selfplay_policy_describe: name buffer of %d bytes too small", name_cap);
+    strcpy(name, plan.name);
+    *lds_bytes = (int64_t)plan.lay.total * 4;
+    return 0;
+}
+
+extern "C" int mlg_rollout_selfplay_policy(const MlgEnvSpec* spec, MlgEnvState* st, const MlgAgentDims* dims,
+                                           const float* home_packed, const float* away_packed, MlgBatch* home,
+                                           MlgBatch* away, MlgRunInfo* info, float eps_home, float eps_away,
+                                           int32_t test_mode, int32_t mask_before_softmax, int32_t test_greedy,
+                                           void* stream) {
+    if (check_spec(spec) || check_state(st) || check_agent_dims(dims)) return 1;
+    MLG_REQUIRE(home_packed && away_packed && info, "rollout_selfplay_policy: null pointer");
+    if (check_rollout_batch(home, spec, st, "rollout_selfplay_policy (home)") ||
+        check_rollout_batch(away, spec, st, "rollout_selfplay_policy (away)"))
+        return 1;
+    MLG_REQUIRE(info->ep_len && info->ret && info->won && info->draw,
+                "rollout_selfplay_policy: run info has null tensors");
+    PolicyPlan plan;
+    if (int rc = plan_selfplay_policy(spec, dims, &plan)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Sides sd;
+    sd.bt[0] = *home;
+    sd.bt[1] = *away;
+    sd.P[0] = home_packed;
+    sd.P[1] = away_packed;
+    sd.eps[0] = test_mode ? 0.f : eps_home;
+    sd.eps[1] = test_mode ? 0.f : eps_away;
+    sd.ns = 2;
+    sd.nh = spec->n_agents / 2;
+    const int flags = (test_mode ? 1 : 0) | (mask_before_softmax ? 2 : 0) | (test_greedy ? 4 : 0);
+    const int grid = (st->B + RE - 1) / RE;
+    int rc = 0;
+#define MLG_RO(HH, TT) rc = launch_selfplay_policy<HH, TT>(plan, grid, s, *spec, *st, sd, *info, flags)
+#define MLG_RO_H(HH)               \
+    if (plan.tpw == 1) MLG_RO(HH, 1);      \
+    else if (plan.tpw == 2) MLG_RO(HH, 2); \
+    else if (plan.tpw == 3) MLG_RO(HH, 3); \
+    else MLG_RO(HH, 4)
+    if (plan.L.H == 64) {
+        MLG_RO_H(64);
+    } else if (plan.L.H == 32) {
+        MLG_RO_H(32);
+    } else {
+        MLG_RO_H(128);
+    }
+#undef MLG_RO_H
+#undef MLG_RO
+    if (rc) return rc;
+    return mlg::check_launch("rollout_policy_kernel (self-play)");
 }

@@ -208,6 +208,9 @@ SIGNATURES = {
     "mlg_select_multinomial": (ctypes.c_int, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "mlg_rollout_policy": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _I, _I, _P]),
     "mlg_rollout_policy_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
+    "mlg_rollout_selfplay_policy": (ctypes.c_int, [_P] * 8 + [ctypes.c_float, ctypes.c_float, _I, _I, _I, _P]),
+    "mlg_rollout_selfplay_policy_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
+    "mlg_crossplay_rollout_policy": (ctypes.c_int, [_P, _P, _I, _I, _P]),
     "mlg_coma_policy_loss": (ctypes.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "mlg_coma_param_count": (ctypes.c_int64, [_P]),
     "mlg_coma_workspace_floats": (ctypes.c_int64, [_P]),
@@ -305,6 +308,20 @@ def rollout_policy_describe(spec: MlgEnvSpec, dims: MlgAgentDims) -> tuple[str, 
     rc = lib.mlg_rollout_policy_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name), ctypes.byref(lds))
     if rc != 0:
         raise NativeError(f"mlg_rollout_policy_describe failed: {lib.mlg_last_error().decode()}")
+    return name.value.decode(), int(lds.value)
+
+
+def rollout_selfplay_policy_describe(spec: MlgEnvSpec, dims: MlgAgentDims) -> tuple[str, int]:
+    """(arm name, dynamic LDS bytes) of the launch mlg_rollout_selfplay_policy would make for this spec and one side's
+    agent dims under the current MLG_ROLLOUT_GLOBAL_WEIGHTS environment: "sp-policy-lds/tpwK" or "sp-policy-global/tpwK"
+    (mlg_rollout_selfplay_policy_describe: host only, needs no GPU)."""
+    lib = load()
+    name = ctypes.create_string_buffer(32)
+    lds = ctypes.c_int64(0)
+    rc = lib.mlg_rollout_selfplay_policy_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name),
+                                                  ctypes.byref(lds))
+    if rc != 0:
+        raise NativeError(f"mlg_rollout_selfplay_policy_describe failed: {lib.mlg_last_error().decode()}")
     return name.value.decode(), int(lds.value)
 
 

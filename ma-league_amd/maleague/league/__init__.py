@@ -1,5 +1,6 @@
 from .distributed import DistributedLeague
-from .evaluation import CrossPlayEvaluator, CrossPlayResult, aggregate, avg_proportional_loss, build_pairs
+from .evaluation import (CrossPlayEvaluator, CrossPlayResult, PolicyCrossPlayEvaluator, aggregate, avg_proportional_loss,
+                         build_pairs, evaluator_for)
 from .instance import LeagueInstance, league_roles_for
 from .matchmaking import REGISTRY as MATCHMAKING_REGISTRY
 from .payoff import (REGISTRY, FSPSampling, PayoffEntry, PayoffWrapper, PFSPSampling, SPSampling,
@@ -10,5 +11,5 @@ from .roles import (ROLES, LeagueExploiter, LeagueView, MainExploiter, MainPlaye
 __all__ = ["DistributedLeague", "LeagueInstance", "league_roles_for", "MATCHMAKING_REGISTRY", "PayoffEntry",
            "PayoffWrapper", "PFSPSampling", "FSPSampling", "SPSampling", "REGISTRY", "episode_result", "ROLES",
            "LeagueView", "MainPlayer", "MainExploiter", "LeagueExploiter", "SimplePlayer", "alphastar_roles",
-           "remove_monotonic_suffix", "CrossPlayEvaluator", "CrossPlayResult", "aggregate", "avg_proportional_loss",
-           "build_pairs"]
+           "remove_monotonic_suffix", "CrossPlayEvaluator", "PolicyCrossPlayEvaluator", "evaluator_for",
+           "CrossPlayResult", "aggregate", "avg_proportional_loss", "build_pairs"]

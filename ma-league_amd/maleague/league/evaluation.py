@@ -8,6 +8,10 @@ the training stepper. ``CrossPlayEvaluator`` plays every (home, away, roster) pa
 written, and a second kernel reduces the per-env results to one summary row per pair. Every pair sees the same
 ``episodes`` spawn draws (env index e, episode counter ``episode0 + launch``): common random numbers.
 
+``PolicyCrossPlayEvaluator`` is the same evaluation for ``pi_logits`` policies (COMA): ``mlg_crossplay_rollout_policy``
+picks with the policy softmax in test mode (greedy, or a draw with ``test_greedy=False``); ``evaluator_for`` picks
+the class by ``args.agent_output_type``.
+
 The training payoff (``DistributedLeague.payoff``) holds epsilon-greedy training games of the pairs the matchmaker
 drew; this table is separate and never written into it.
 """
@@ -142,9 +146,7 @@ class CrossPlayEvaluator:
     def __init__(self, args, device, episodes_per_launch: Optional[int] = None):
         self.args = args
         self.device = torch.device(device)
-        if getattr(args, "agent_output_type", "q") != "q":
-            raise NotImplementedError("cross-play evaluation plays greedy over Q values: agent_output_type="
-                                      f"{args.agent_output_type!r} is not supported (COMA in the league is out of scope)")
+        self._check_output_type(args)
         if getattr(args, "agent", "rnn") != "rnn":
             raise NotImplementedError("cross-play evaluation runs the recurrent agent (agent='rnn') only: "
                                       f"agent={args.agent!r} is not supported (agent='dqn' and the other non-DRQN "
@@ -158,6 +160,15 @@ class CrossPlayEvaluator:
         self._buf = {}
         self.launches = 0
         self.last = None  # per-env outputs and summary of the last launch (device views)
+
+    def _check_output_type(self, args):
+        if getattr(args, "agent_output_type", "q") != "q":
+            raise NotImplementedError("cross-play evaluation plays greedy over Q values: agent_output_type="
+                                      f"{args.agent_output_type!r} is not supported (COMA in the league is out of scope "
+                                      "for CrossPlayEvaluator; pi_logits policies are PolicyCrossPlayEvaluator)")
+
+    def _launch(self, dims, c, stream):
+        _native.call("mlg_crossplay_rollout", _native.byref(dims), _native.byref(c), stream)
 
     # ---- specs / dims ---------------------------------------------------------------------------------------
     def spec_of(self, plan) -> TeamsEnvSpec:
@@ -250,7 +261,7 @@ class CrossPlayEvaluator:
                                      (int(episode0) + k) & 0xFFFFFFFF, ws.data_ptr(), ws.numel(), ep_len.data_ptr(),
                                      ret.data_ptr(), ret_away.data_ptr(), won.data_ptr(), draw.data_ptr(),
                                      summary.data_ptr())
-            _native.call("mlg_crossplay_rollout", _native.byref(dims), _native.byref(c), stream)
+            self._launch(dims, c, stream)
             self.launches += 1
             self.last = {"E": E, "ep_len": ep_len[:n * E].view(n, E), "ret": ret[:n * E].view(n, E),
                          "ret_away": ret_away[:n * E].view(n, E), "won": won[:2 * n * E].view(n, E, 2),
@@ -263,5 +274,31 @@ class CrossPlayEvaluator:
         return aggregate(host, pairs, pairs.shape)
 
 
+class PolicyCrossPlayEvaluator(CrossPlayEvaluator):
+    """CrossPlayEvaluator for ``pi_logits`` policies (COMA): every pair in one launch of
+    ``mlg_crossplay_rollout_policy``, the pick being the policy rollout's in test mode -- the first-index argmax of the
+    masked probabilities with ``args.test_greedy`` (default), else a draw from the floor-less probabilities on the
+    counter RNG with the launch's episode counter. ``args.mask_before_softmax`` as in training."""
+
+    def _check_output_type(self, args):
+        if getattr(args, "agent_output_type", "q") != "pi_logits":
+            raise NotImplementedError("policy cross-play evaluation picks from the policy softmax: agent_output_type="
+                                      f"{getattr(args, 'agent_output_type', 'q')!r} is not supported (Q policies are "
+                                      "CrossPlayEvaluator)")
+
+    def _launch(self, dims, c, stream):
+        a = self.args
+        _native.call("mlg_crossplay_rollout_policy", _native.byref(dims), _native.byref(c),
+                     int(bool(getattr(a, "mask_before_softmax", True))), int(bool(getattr(a, "test_greedy", True))),
+                     stream)
+
+
+def evaluator_for(args, device, episodes_per_launch: Optional[int] = None) -> CrossPlayEvaluator:
+    """The evaluator of ``args.agent_output_type``: PolicyCrossPlayEvaluator for 'pi_logits', else CrossPlayEvaluator."""
+    cls = PolicyCrossPlayEvaluator if getattr(args, "agent_output_type", "q") == "pi_logits" else CrossPlayEvaluator
+    return cls(args, device, episodes_per_launch)
+
+
 __all__ = ["PairTable", "build_pairs", "aggregate", "avg_proportional_loss", "CrossPlayResult", "CrossPlayEvaluator",
+           "PolicyCrossPlayEvaluator", "evaluator_for",
            "GAMES", "WINS", "LOSSES", "DRAWS", "RET_HOME", "RET_AWAY", "EP_LEN"]

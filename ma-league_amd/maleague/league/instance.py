@@ -59,6 +59,10 @@ class LeagueInstance:
         if int(opponents_per_match) < 1:
             raise ValueError(f"opponents_per_match={opponents_per_match} must be >= 1")
         self.opponents_per_match = int(opponents_per_match)
+        if self.opponents_per_match > 1 and getattr(args, "agent_output_type", "q") == "pi_logits":
+            raise NotImplementedError(f"LeagueInstance(opponents_per_match={self.opponents_per_match}): opponent "
+                                      "mixtures with agent_output_type='pi_logits' are not supported (a pi_logits "
+                                      "match plays one opponent)")
         self.opponents = []      # the draws of the current match (pids; equal draws repeat)
         self.group_draw = None   # mixture match: the draw (index into opponents) of every 16-env group
         if getattr(args, "mac", "basic") == "distinct":
@@ -255,7 +259,7 @@ class LeagueInstance:
         ``pairs[r::world]`` and the per-cell totals are summed over the ranks (host-staged under gloo, as
         sync_payoff). Returns the CrossPlayResult (rows / columns in ``pids`` order) and logs
         ``league_eval_win_rate_mean`` per home pid. The training payoff is not touched."""
-        from .evaluation import CrossPlayEvaluator, CrossPlayResult, build_pairs
+        from .evaluation import CrossPlayResult, build_pairs, evaluator_for
         lg = self.league
         if lg.current is None:
             raise RuntimeError("evaluate_pool: the league's agent pool is empty (no exchange yet)")
@@ -268,7 +272,7 @@ class LeagueInstance:
         # a pid is its row in [current | historical] (params_of)
         table = build_pairs(pids, pids, self.team_of if self.teams is not None else None)
         if getattr(self, "_evaluator", None) is None:
-            self._evaluator = CrossPlayEvaluator(self.experiment.args, lg.device)
+            self._evaluator = evaluator_for(self.experiment.args, lg.device)  # by agent_output_type
         mine = table[lg.rank::lg.world] if lg._dist else table
         totals = self._evaluator.evaluate([lg.current, lg.historical], mine, episodes).totals
         if lg._dist:

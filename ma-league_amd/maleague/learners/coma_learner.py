@@ -165,6 +165,9 @@ class COMALearner(Learner):
         self._grad_norm = torch.nn.utils.clip_grad_norm_(self.agent_params, self.args.grad_norm_clip)
         self.agent_optimiser.step()
         self.mac.agent.mark_dirty()
+        # trained steps accumulate on the agent's device counter, no host wait (the reference's COMA learner never
+        # calls update_trained_steps; the league's checkpoint thresholds need the count: DESIGN.md §7)
+        self.mac.agent.add_trained_steps(torch.count_nonzero(mask))
         self._astats = stats.detach()
         self.train_calls += 1
 

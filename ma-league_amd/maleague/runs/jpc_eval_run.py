@@ -6,7 +6,8 @@ proportional loss (eval/methods.py:8-18) says how much a policy loses when it me
 
 The reference trains and evaluates in a process ``Pool`` and runs one ``evaluate_mean_returns`` per pair. Here the
 instances train one after another on this GPU, their policies stay on the device as rows of one pool tensor, and ONE
-``CrossPlayEvaluator.evaluate`` call plays all instances_num^2 pairs in one launch (league.evaluation).
+``CrossPlayEvaluator.evaluate`` call (``PolicyCrossPlayEvaluator`` for ``pi_logits`` policies) plays all instances_num^2
+pairs in one launch (league.evaluation).
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ from typing import List
 import torch
 
 from ..envs.plans import mirror_plan
-from ..league.evaluation import CrossPlayEvaluator, CrossPlayResult, avg_proportional_loss, build_pairs
+from ..league.evaluation import CrossPlayResult, avg_proportional_loss, build_pairs, evaluator_for
 from .sp_ma_experiment import SelfPlayMultiAgentExperiment, agent_vector
 
 
@@ -67,4 +68,5 @@ class JointPolicyCorrelationEvaluationRun:
         n = self.instances_num
         self.logger.info("Evaluate {} pairings for {} episodes.".format(n * n, self.eval_episodes))
         pairs = build_pairs(range(n), range(n, 2 * n))
-        return CrossPlayEvaluator(self._instance_args(0), pool.device).evaluate(pool, pairs, self.eval_episodes)
+        # CrossPlayEvaluator, or PolicyCrossPlayEvaluator for pi_logits policies (COMA)
+        return evaluator_for(self._instance_args(0), pool.device).evaluate(pool, pairs, self.eval_episodes)

@@ -13,6 +13,7 @@ import torch
 from ..controllers import REGISTRY as mac_REGISTRY
 from ..learners.q_learner import FlatParams
 from ..utils.flat import module_flat_view
+from ..steppers import SELF_POLICY_REGISTRY as self_policy_steppers_REGISTRY
 from ..steppers import SELF_REGISTRY as self_steppers_REGISTRY
 from .ma_experiment import MultiAgentExperiment
 
@@ -76,7 +77,10 @@ class SelfPlayMultiAgentExperiment(MultiAgentExperiment):
         return env_scheme
 
     def _build_stepper(self, log_start_t=0):
-        return self_steppers_REGISTRY[self.args.runner](args=self.args, logger=self.logger, log_start_t=log_start_t)
+        # two pi_logits MACs (COMA) roll out through the policy softmax and the multinomial draw
+        reg = self_policy_steppers_REGISTRY if getattr(self.args, "agent_output_type", "q") == "pi_logits" \
+            else self_steppers_REGISTRY
+        return reg[self.args.runner](args=self.args, logger=self.logger, log_start_t=log_start_t)
 
     def _init_stepper(self):
         # (re)initialised every call like the reference (sp_ma_experiment.py:54-58): the away MAC may change

@@ -2,10 +2,13 @@
 same keys resolve to the entity-env steppers (see build_stepper)."""
 from .entity_stepper import EntityEpisodeStepper, EntityParallelStepper
 from .parallel_stepper import EnvStepper, EpisodeStepper, ParallelStepper
-from .self_play_stepper import OpponentMix, SelfPlayParallelStepper, SelfPlayStepper
+from .self_play_stepper import (OpponentMix, SelfPlayParallelStepper, SelfPlayPolicyParallelStepper, SelfPlayPolicyStepper,
+                                SelfPlayStepper)
 
 REGISTRY = {"episode": EpisodeStepper, "parallel": ParallelStepper}
 SELF_REGISTRY = {"episode": SelfPlayStepper, "parallel": SelfPlayParallelStepper}
+# two pi_logits MACs (COMA in self-play and the league): the policy softmax and the multinomial draw on both sides
+SELF_POLICY_REGISTRY = {"episode": SelfPlayPolicyStepper, "parallel": SelfPlayPolicyParallelStepper}
 ENTITY_REGISTRY = {"episode": EntityEpisodeStepper, "parallel": EntityParallelStepper}
 
 
@@ -15,5 +18,5 @@ def build_stepper(args, logger, log_start_t=0):
 
 
 __all__ = ["EnvStepper", "OpponentMix", "EpisodeStepper", "ParallelStepper", "SelfPlayParallelStepper", "SelfPlayStepper",
-           "EntityParallelStepper", "EntityEpisodeStepper", "REGISTRY", "SELF_REGISTRY", "ENTITY_REGISTRY",
-           "build_stepper"]
+           "SelfPlayPolicyParallelStepper", "SelfPlayPolicyStepper", "EntityParallelStepper", "EntityEpisodeStepper",
+           "REGISTRY", "SELF_REGISTRY", "SELF_POLICY_REGISTRY", "ENTITY_REGISTRY", "build_stepper"]

@@ -12,6 +12,10 @@ home and ``reward[1]`` for away; stepper_utils.build_pre_transition_data, steppe
 Opponent mixture (``set_opponent_mix``): one launch of ``mlg_rollout_selfplay_mix`` plays the home policy against one
 away policy -- and one roster -- per group of 16 envs; env b runs exactly as in the plain launch against its group's
 opponent.
+
+Two ``pi_logits`` MACs (COMA in self-play and the league): ``SelfPlayPolicyParallelStepper`` / ``SelfPlayPolicyStepper``
+(``SELF_POLICY_REGISTRY``) make the same run with one launch of ``mlg_rollout_selfplay_policy``: each side's outputs go
+through the policy softmax with that side's epsilon floor and the action is drawn by the multinomial rule.
 """
 from __future__ import annotations
 
@@ -127,10 +131,7 @@ class SelfPlayParallelStepper(ParallelStepper):
             raise ValueError("self-play needs an away MAC (initialize(..., home_mac, away_mac))")
         for side, mac in (("home", home_mac), ("away", away_mac)):
             refuse_distinct(mac, f"self-play rollouts ({side} MAC)")
-            if getattr(mac, "agent_output_type", "q") != "q":
-                raise NotImplementedError(f"self-play rollouts select epsilon-greedy over Q values: the {side} MAC's "
-                                          f"agent_output_type={mac.agent_output_type!r} is not supported (COMA in "
-                                          "self-play is out of scope)")
+            self._check_output_type(side, mac)
             agent = getattr(mac, "agent", None)
             if agent is not None and not isinstance(agent, DRQNAgentNetwork):
                 raise NotImplementedError(f"self-play rollouts run the recurrent agent (agent='rnn') only: the {side} "
@@ -139,6 +140,13 @@ class SelfPlayParallelStepper(ParallelStepper):
         ParallelStepper.initialize(self, scheme, groups, preprocess, home_mac)
         self.away_mac = away_mac
         self._away_buf = None
+
+    def _check_output_type(self, side, mac):
+        if getattr(mac, "agent_output_type", "q") != "q":
+            raise NotImplementedError(f"self-play rollouts select epsilon-greedy over Q values: the {side} MAC's "
+                                      f"agent_output_type={mac.agent_output_type!r} is not supported (COMA in "
+                                      "self-play is out of scope for SelfPlayParallelStepper; two pi_logits MACs are "
+                                      "SelfPlayPolicyParallelStepper, steppers.SELF_POLICY_REGISTRY['parallel'])")
 
     @property
     def epsilons(self):
@@ -215,10 +223,7 @@ class SelfPlayParallelStepper(ParallelStepper):
                          _native.byref(run_info), float(eps_h), float(eps_a), int(bool(test_mode)),
                          _native.stream_ptr(self.device))
         else:
-            _native.call("mlg_rollout_selfplay", _native.byref(self._cspec), _native.byref(st), _native.byref(d),
-                         _native.ptr(p_h), _native.ptr(p_a), _native.byref(mb_h),
-                         _native.byref(mb_a), _native.byref(run_info), float(eps_h), float(eps_a),
-                         int(bool(test_mode)), _native.stream_ptr(self.device))
+            self._launch_selfplay(st, d, p_h, p_a, mb_h, mb_a, run_info, eps_h, eps_a, test_mode)
         if ev is not None:
             ev[1].record()
             self.timing.append(ev)
@@ -229,8 +234,15 @@ class SelfPlayParallelStepper(ParallelStepper):
         return self.home_batch, self.away_batch, LazyEnvInfos(self, self._run_id)
 
 
-class SelfPlayStepper(SelfPlayParallelStepper):
-    """Single-env self-play stepper (self_play_stepper.py:9-147): B = 1, returns the final env_info dict."""
+    def _launch_selfplay(self, st, d, p_h, p_a, mb_h, mb_a, run_info, eps_h, eps_a, test_mode):
+        _native.call("mlg_rollout_selfplay", _native.byref(self._cspec), _native.byref(st), _native.byref(d),
+                     _native.ptr(p_h), _native.ptr(p_a), _native.byref(mb_h),
+                     _native.byref(mb_a), _native.byref(run_info), float(eps_h), float(eps_a),
+                     int(bool(test_mode)), _native.stream_ptr(self.device))
+
+
+class _SingleEnv:
+    """B = 1 form of a self-play stepper (self_play_stepper.py:9-147): returns the final env_info dict."""
 
     def __init__(self, args, logger, log_start_t=0):
         assert args.batch_size_run == 1
@@ -242,3 +254,48 @@ class SelfPlayStepper(SelfPlayParallelStepper):
         self.logger.log_stat("home_epsilon", eh, self.log_t)
         self.logger.log_stat("away_epsilon", ea, self.log_t)
         return home, away, infos[-1]
+
+
+class SelfPlayStepper(_SingleEnv, SelfPlayParallelStepper):
+    """Single-env self-play stepper (self_play_stepper.py:9-147): B = 1, returns the final env_info dict."""
+
+
+class SelfPlayPolicyParallelStepper(SelfPlayParallelStepper):
+    """Self-play of two ``pi_logits`` MACs (COMA; in the reference the self-play steppers only call
+    ``mac.select_actions``, so they run any registered algorithm): one launch of ``mlg_rollout_selfplay_policy`` per
+    run. Each side's epsilon floor comes from its own selector's schedule, ``mask_before_softmax`` / ``test_greedy``
+    from args (one value for both sides). Batches, rewards, run summary and ring / away-batch reuse are
+    SelfPlayParallelStepper's."""
+
+    def _check_output_type(self, side, mac):
+        if getattr(mac, "agent_output_type", "q") != "pi_logits":
+            raise NotImplementedError(f"policy self-play rollouts draw from the policy softmax: the {side} MAC's "
+                                      f"agent_output_type={getattr(mac, 'agent_output_type', 'q')!r} is not supported "
+                                      "(both MACs must be 'pi_logits'; one Q side against one policy side is out of "
+                                      "scope, two Q MACs are steppers.SELF_REGISTRY)")
+
+    def set_opponent_mix(self, mix):
+        if mix is None:
+            return
+        raise NotImplementedError("opponent mixtures with agent_output_type='pi_logits' are not supported "
+                                  "(mlg_rollout_selfplay_mix selects epsilon-greedy over Q values; a pi_logits match "
+                                  "plays one opponent)")
+
+    def describe_rollout(self):
+        if self.home_mac is None:
+            raise MultiAgentControllerNotInitialized()
+        return _native.rollout_selfplay_policy_describe(self._cspec, self.home_mac.agent.dims())
+
+    def _launch_selfplay(self, st, d, p_h, p_a, mb_h, mb_a, run_info, eps_h, eps_a, test_mode):
+        a = self.args
+        sel = self.home_mac.action_selector
+        _native.call("mlg_rollout_selfplay_policy", _native.byref(self._cspec), _native.byref(st), _native.byref(d),
+                     _native.ptr(p_h), _native.ptr(p_a), _native.byref(mb_h), _native.byref(mb_a),
+                     _native.byref(run_info), float(eps_h), float(eps_a), int(bool(test_mode)),
+                     int(bool(getattr(a, "mask_before_softmax", True))),
+                     int(bool(getattr(a, "test_greedy", getattr(sel, "test_greedy", True)))),
+                     _native.stream_ptr(self.device))
+
+
+class SelfPlayPolicyStepper(_SingleEnv, SelfPlayPolicyParallelStepper):
+    """Single-env form of SelfPlayPolicyParallelStepper: B = 1, returns the final env_info dict."""
