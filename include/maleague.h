@@ -794,6 +794,38 @@ int mlg_rollout_distinct(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgent
 int mlg_rollout_distinct_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, char *name, int32_t name_cap,
                                   int64_t *lds_bytes);
 
+/* One full self-play run with one DRQN per agent slot on both sides (two DistinctMACs), in one launch. It is
+ * mlg_rollout_selfplay on the generic fp32 arm with one change: agent ln of side s acts with block ln of side s's
+ * pool. home_pool / away_pool: [nh][mlg_packed_agent_size(dims)], the layout mlg_pack_agent_pool writes, 16-byte
+ * aligned. `dims` describe one side's MAC: n_agents = nh = spec->n_agents / 2, obs_agent_id must be 0. Everything else
+ * is mlg_rollout_selfplay's, bit for bit: the RNG key mlg_env_key(seed, b), the global agent index s * nh + ln as the
+ * epsilon stream index, one epsilon per side, reward[0] / reward[1] and ret_away, the ring, full-write and slot_extent
+ * modes and the run summary. With nh equal networks per side a run stores the bits of mlg_rollout_selfplay's generic
+ * fp32 kernel (MLG_ROLLOUT_KERNEL=v1).
+ * Structure (rollout_distinct_kernel's): a workgroup owns 16 envs, env state in LDS, hidden state in VGPRs; the agent
+ * phase is agent-major: there are 2 * nh tiles, tile a = s * nh + ln is agent ln of side s across the workgroup's 16
+ * envs; wave w owns tiles w, w + W, ... (a wave's tiles may belong to different sides; the side, its batch, its pool
+ * and its epsilon are per tile and wave-uniform). Weights are read from global memory. No float atomics: two runs from
+ * the same state are bit-identical.
+ * Dispatch: tiles = 2 * nh, waves W = min(tiles, 8), tpw = ceil(tiles / W); names "dxsp-global/tpwK": nh 1..4 tpw1,
+ * 5..8 tpw2, 9..12 tpw3, 13..16 tpw4. nh > 16, obs_agent_id = 1, H outside 32 / 64 / 128 and dims that do not match
+ * the spec are refused through mlg_last_error, without launching. */
+int mlg_rollout_selfplay_distinct(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgentDims *dims,
+                                  const float *home_pool, const float *away_pool, MlgBatch *home, MlgBatch *away,
+                                  MlgRunInfo *info, float eps_home, float eps_away, int32_t test_mode, void *stream);
+/* Host only, launches nothing (the contract of mlg_rollout_describe). mlg_rollout_selfplay_distinct takes its decision
+ * from the same function. Nonzero (mlg_last_error) where it would refuse the spec or the dims. */
+int mlg_rollout_selfplay_distinct_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, char *name,
+                                           int32_t name_cap, int64_t *lds_bytes);
+
+/* mlg_crossplay_rollout for distinct policies: the same MlgCrossplay block, checks, outputs and summary. packed_pool
+ * holds n_pool * nh blocks (nh = dims->n_agents), policy p being blocks [p * nh, (p + 1) * nh); n_pool counts
+ * policies. dims->obs_agent_id must be 0; at most 16 agents per side. The tile layout is agent-major as in
+ * mlg_rollout_selfplay_distinct; the obs / avail rows, in LDS or in the workspace slice, are read by column = env. Env
+ * (pair k, episode e) is bit-identical to env e of one test-mode mlg_rollout_selfplay_distinct of that pair with
+ * episode counter episode0. The workspace need is mlg_crossplay_workspace_floats'. */
+int mlg_crossplay_rollout_distinct(const MlgAgentDims *dims, const MlgCrossplay *c, void *stream);
+
 /* ---- Prioritized episode replay (replay.hip) ----------------------------------------------------
  * The reference's Memory / BinarySumTree (src/marl/components/replay_buffers/prioritized_replay_buffer.py:8-135) on a
  * flat fp32 priority vector, one entry per replay slot, in slot order. priority = (|err| + e)^a, formed in double and

@@ -338,6 +338,152 @@ __global__ void __launch_bounds__(512) crossplay_kernel(CpArgs a, CpShape sh, Ag
     }
 }
 
+// mlg_crossplay_rollout_distinct: policies with one DRQN per agent slot (mac: distinct). The pool holds n_pool * nh
+// blocks, policy p being blocks [p nh, (p + 1) nh). The body is crossplay_kernel's Q instantiation with the agent
+// phase agent-major, as rollout_selfplay_distinct_kernel's (distinct_selfplay.hip): tile a = s nh + ln is agent ln of
+// side s across the workgroup's 16 envs (column = env), 2 nh tiles, wave w owns tiles w, w + W, ...; the weight view
+// of a tile is wave-uniform. The obs / avail rows (LDS or the workspace slice) are read by column = env. Env (pair k,
+// episode e) is bit-identical to env e of one test-mode mlg_rollout_selfplay_distinct of that pair with episode
+// counter episode0. A kernel of its own, not a template flag of crossplay_kernel, for the reason rollout_policy.hip
+// records.
+template <int H, int TPW>
+__global__ void __launch_bounds__(512) crossplay_distinct_kernel(CpArgs a, CpShape sh, AgentLayout L, CpLds lay) {
+    constexpr int HC = H / 16;
+    extern __shared__ __attribute__((aligned(16))) int smem[];
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), W = nthr >> 6;
+    const int pair = blockIdx.x / a.wg_per_pair, e0 = (blockIdx.x % a.wg_per_pair) * RE;
+    const int64_t out = (int64_t)pair * a.E;
+    const MlgCrossplayPair pr = a.pairs[pair];
+    const int U = sh.U, N = sh.N, A = sh.A, nh = sh.nh;
+    // As crossplay_kernel: a device pair row that is out of range plays nothing (ep_len -1).
+    if ((unsigned)pr.home >= (unsigned)a.n_pool || (unsigned)pr.away >= (unsigned)a.n_pool ||
+        (unsigned)pr.spec >= (unsigned)a.n_specs) {
+        for (int e = tid; e < RE; e += nthr) {
+            if (e0 + e >= a.E) continue;
+            const int64_t b = out + e0 + e;
+            a.ep_len[b] = -1;
+            a.ret[b] = 0.f;
+            a.ret_away[b] = 0.f;
+            a.won[2 * b] = a.won[2 * b + 1] = 0;
+            a.draw[b] = 0;
+        }
+        return;
+    }
+    SpecShared& SS = *reinterpret_cast<SpecShared*>(smem + lay.spec);
+    CpEnv R;
+    R.x = smem + lay.x;
+    R.y = smem + lay.y;
+    R.hp = smem + lay.hp;
+    R.nhp = smem + lay.nhp;
+    R.act = smem + lay.act;
+    R.pact = smem + lay.pact;
+    R.prev = smem + lay.prev;
+    R.status = smem + lay.status;
+    R.stepped = smem + lay.stepped;
+    R.len = smem + lay.len;
+    R.misc = smem + lay.misc;
+    R.ret = reinterpret_cast<float*>(smem + lay.ret);
+    R.ret2 = reinterpret_cast<float*>(smem + lay.ret2);
+    R.ldo = lay.ldo;
+    if (lay.obs >= 0) {
+        R.lobs = reinterpret_cast<float*>(smem + lay.obs);
+        R.lavail = smem + lay.avail;
+    } else {  // one step of this workgroup's rows in its workspace slice (written and read by this workgroup only)
+        float* ws = a.workspace + (int64_t)blockIdx.x * (lay.obs_words + lay.avail_words);
+        R.lobs = ws;
+        R.lavail = reinterpret_cast<int32_t*>(ws + lay.obs_words);
+    }
+    load_spec_tables(a.specs[pr.spec], SS);  // the pair's roster, from device memory
+    EnvTables T;
+    T.team = SS.team;
+    T.role = SS.role;
+    T.melee = SS.melee;
+    T.agent = SS.agent;
+    T.U = U;
+    T.grid = sh.grid;
+    T.episode_limit = sh.episode_limit;
+    T.stochastic = sh.stochastic;
+    const float inv_p = 1.0f / (float)pow2_at_least(sh.grid);
+    // policy p = blocks [p nh, (p + 1) nh) of the pool
+    const float* P0 = a.pool + (int64_t)pr.home * nh * a.pool_stride;
+    const float* P1 = a.pool + (int64_t)pr.away * nh * a.pool_stride;
+
+    // ---- reset: env (pair, e) = env index e0 + e, episode counter episode0 ----
+    for (int e = tid; e < RE; e += nthr) {
+        R.len[e] = 0;
+        R.ret[e] = 0.f;
+        R.ret2[e] = 0.f;
+        R.stepped[e] = 0;
+        R.status[e] = e0 + e < a.E ? 0 : 2;
+    }
+    __syncthreads();
+    for (int i = tid; i < RE * U; i += nthr) {
+        const int e = i / U, u = i % U;
+        if (R.status[e] == 2) continue;
+        const int tm = SS.team[u];
+        env_spawn_unit(T, mlg_env_key(sh.seed, e0 + e), a.episode0, u, SS.team_first[tm], SS.team_size[tm], R.x + e * U,
+                       R.y + e * U, R.hp + e * U);
+    }
+    __syncthreads();
+    cp_observe(T, SS, sh, R, false, inv_p);
+    __syncthreads();
+
+    floatx4 h[TPW][HC];
+#pragma unroll
+    for (int ti = 0; ti < TPW; ++ti)
+#pragma unroll
+        for (int c = 0; c < HC; ++c) h[ti][c] = floatx4{0.f, 0.f, 0.f, 0.f};
+    const int e = lane & 15, g = lane >> 4;  // column = env of the workgroup
+    const int n_at = L.Ap / 16;
+    const int T1 = sh.episode_limit + 1;
+    for (int t = 0; t < T1; ++t) {
+        // ---- agent phase: tile ag = agent ln of side s in the envs with status 0 or 1, greedy ----
+#pragma unroll
+        for (int ti = 0; ti < TPW; ++ti) {
+            const int ag = wave + ti * W;  // the tile's global agent index s nh + ln: wave-uniform
+            if (ag >= N) continue;
+            const int side = ag >= nh, ln = ag - side * nh;
+            const bool valid = R.status[e] < 2;  // envs past E carry status 2 from the reset
+            if (!__any(valid)) continue;  // wave-uniform skip once every env is done
+            // opaque zero offset per tile: keeps t- and tile-invariant weight loads out of (spilled) registers
+            int zero = 0;
+            asm volatile("" : "+s"(zero));
+            const WView Wv = global_view((side ? P1 : P0) + (int64_t)ln * a.pool_stride + zero, L);
+            RowIn in;
+            in.x = valid ? R.lobs + (e * N + ag) * R.ldo : nullptr;
+            in.onehot = nullptr;
+            in.prev_action = (valid && t > 0) ? R.prev[e * N + ag] : -1;
+            in.agent = 0;
+            agent_cell_hidden<H>(Wv, L, in, h[ti], lane);
+            const int32_t* av = valid ? R.lavail + (e * N + ag) * A : nullptr;
+            ArgmaxState as{-INFINITY, 1 << 30};
+            for (int at = 0; at < n_at; ++at) {
+                const floatx4 q = agent_q_tile<H>(Wv, h[ti], at, lane);
+                argmax_accumulate(as, q, av, at, A, lane);
+            }
+            const int act = argmax_reduce(as);
+            if (valid && g == 0) R.pact[e * N + ag] = act;
+        }
+        __syncthreads();
+        cp_env_step(T, SS, sh, R, a, out, e0, t, inv_p);
+        if (tid == 0) {
+            int n = 0;
+            for (int x = 0; x < RE; ++x) n += R.status[x] < 2;
+            R.misc[0] = n > 0;
+        }
+        __syncthreads();
+        if (!R.misc[0]) break;
+    }
+    for (int x = tid; x < RE; x += nthr) {
+        if (e0 + x >= a.E) continue;
+        const int64_t b = out + e0 + x;
+        a.ep_len[b] = R.len[x];
+        a.ret[b] = R.ret[x];
+        a.ret_away[b] = R.ret2[x];
+    }
+}
+
 // summary[pair][8] from the per-env results, one wave per pair, in the fixed order maleague.h documents.
 __global__ void __launch_bounds__(64) crossplay_summary_kernel(const int32_t* __restrict__ ep_len,
                                                               const float* __restrict__ ret,
@@ -440,7 +586,18 @@ int launch_crossplay(int grid, int threads, hipStream_t s, const CpArgs& a, cons
     return 0;
 }
 
-int crossplay_rollout(const MlgAgentDims* dims, const MlgCrossplay* c, bool policy, int flags, void* stream);
+template <int H, int TPW>
+int launch_crossplay_distinct(int grid, int threads, hipStream_t s, const CpArgs& a, const CpShape& sh,
+                              const AgentLayout& L, const CpLds& lay) {
+    const size_t bytes = (size_t)lay.total * 4;
+    auto kern = crossplay_distinct_kernel<H, TPW>;
+    if (int rc = allow_lds(kern, bytes, "crossplay_distinct")) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), bytes, s, a, sh, L, lay);
+    return 0;
+}
+
+int crossplay_rollout(const MlgAgentDims* dims, const MlgCrossplay* c, bool policy, int flags, void* stream,
+                      bool distinct = false);
 
 }  // namespace
 
@@ -465,11 +622,22 @@ extern "C" int mlg_crossplay_rollout_policy(const MlgAgentDims* dims, const MlgC
     return crossplay_rollout(dims, c, true, (mask_before_softmax ? 2 : 0) | (test_greedy ? 4 : 0), stream);
 }
 
+// Distinct per-agent networks: c->packed_pool holds c->n_pool * dims->n_agents blocks, policy p being blocks
+// [p nh, (p + 1) nh); everything else is mlg_crossplay_rollout's. The workspace need is mlg_crossplay_workspace_floats'.
+extern "C" int mlg_crossplay_rollout_distinct(const MlgAgentDims* dims, const MlgCrossplay* c, void* stream) {
+    return crossplay_rollout(dims, c, false, 0, stream, true);
+}
+
 namespace {
 
-// Both entry points: the checks, the launch of crossplay_kernel<H, TPW, policy> and the summary.
-int crossplay_rollout(const MlgAgentDims* dims, const MlgCrossplay* c, bool policy, int flags, void* stream) {
+// The entry points: the checks, the launch of crossplay_kernel<H, TPW, policy> (distinct: of
+// crossplay_distinct_kernel<H, TPW>) and the summary.
+int crossplay_rollout(const MlgAgentDims* dims, const MlgCrossplay* c, bool policy, int flags, void* stream,
+                      bool distinct) {
     if (check_crossplay_dims(dims)) return 1;
+    MLG_REQUIRE(!distinct || dims->obs_agent_id == 0,
+                "crossplay_distinct: obs_agent_id must be 0 (distinct agent networks take no agent id: network i is "
+                "agent i)");
     MLG_REQUIRE(c != nullptr, "crossplay: null argument block");
     MLG_REQUIRE(c->packed_pool && c->pairs && c->host_pairs && c->specs && c->host_specs && c->workspace,
                 "crossplay: null pool / pairs / specs / workspace pointer");
@@ -521,7 +689,7 @@ int crossplay_rollout(const MlgAgentDims* dims, const MlgCrossplay* c, bool poli
     const AgentLayout L = make_agent_layout(*dims);
     MLG_REQUIRE(!policy || L.Ap <= 16 * RO_MAXAT, "crossplay: n_actions=%d does not fit %d action tiles (policy pick)",
                 dims->n_actions, RO_MAXAT);
-    const int tiles = 2 * ((RE * nh + 15) / 16);
+    const int tiles = distinct ? 2 * nh : 2 * ((RE * nh + 15) / 16);  // distinct: one tile per agent of either side
     const int W = tiles < 8 ? tiles : 8;
     const int tpw = (tiles + W - 1) / W;
     MLG_REQUIRE(tpw <= 4, "crossplay: n_agents=%d per side needs %d agent tiles per wave > 4", nh, tpw);
@@ -562,8 +730,9 @@ int crossplay_rollout(const MlgAgentDims* dims, const MlgCrossplay* c, bool poli
     const int grid = (int)grid64, threads = W * 64;
     int rc = 0;
 #define MLG_CP(HH, TT)                                                                           \
-    rc = policy ? launch_crossplay<HH, TT, true>(grid, threads, s, a, sh, L, lay) \
-                : launch_crossplay<HH, TT, false>(grid, threads, s, a, sh, L, lay)
+    rc = distinct ? launch_crossplay_distinct<HH, TT>(grid, threads, s, a, sh, L, lay)           \
+         : policy ? launch_crossplay<HH, TT, true>(grid, threads, s, a, sh, L, lay)              \
+                  : launch_crossplay<HH, TT, false>(grid, threads, s, a, sh, L, lay)
 #define MLG_CP_H(HH)                   \
     do {                               \
         if (tpw == 1) MLG_CP(HH, 1);   \
@@ -578,7 +747,7 @@ int crossplay_rollout(const MlgAgentDims* dims, const MlgCrossplay* c, bool poli
 #undef MLG_CP_H
 #undef MLG_CP
     if (rc) return rc;
-    if (mlg::check_launch("crossplay_kernel")) return 1;
+    if (mlg::check_launch(distinct ? "crossplay_distinct_kernel" : "crossplay_kernel")) return 1;
     hipLaunchKernelGGL(crossplay_summary_kernel, dim3(c->n_pairs), dim3(64), 0, s, c->ep_len, c->ret, c->ret_away, c->won,
                        c->draw, c->E, c->summary);
     return mlg::check_launch("crossplay_summary_kernel");

@@ -227,6 +227,9 @@ SIGNATURES = {
     "mlg_mac_forward_distinct": (ctypes.c_int, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "mlg_rollout_distinct": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
     "mlg_rollout_distinct_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
+    "mlg_rollout_selfplay_distinct": (ctypes.c_int, [_P] * 8 + [ctypes.c_float, ctypes.c_float, _I, _P]),
+    "mlg_rollout_selfplay_distinct_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
+    "mlg_crossplay_rollout_distinct": (ctypes.c_int, [_P, _P, _P]),
     "mlg_rollout_selfplay_mix": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _I, _P]),
     "mlg_rollout_selfplay_mix_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
     "mlg_league_record_runs_mix": (ctypes.c_int, [_P, _P, _I, _P, _I, _P, ctypes.c_int64, _I, _P]),
@@ -346,6 +349,19 @@ def rollout_distinct_describe(spec: MlgEnvSpec, dims: MlgAgentDims) -> tuple[str
     rc = lib.mlg_rollout_distinct_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name), ctypes.byref(lds))
     if rc != 0:
         raise NativeError(f"mlg_rollout_distinct_describe failed: {lib.mlg_last_error().decode()}")
+    return name.value.decode(), int(lds.value)
+
+
+def rollout_selfplay_distinct_describe(spec: MlgEnvSpec, dims: MlgAgentDims) -> tuple[str, int]:
+    """(arm name "dxsp-global/tpwK", dynamic LDS bytes) of the launch mlg_rollout_selfplay_distinct would make for this
+    spec and one side's agent dims (mlg_rollout_selfplay_distinct_describe: host only, needs no GPU)."""
+    lib = load()
+    name = ctypes.create_string_buffer(32)
+    lds = ctypes.c_int64(0)
+    rc = lib.mlg_rollout_selfplay_distinct_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name),
+                                                    ctypes.byref(lds))
+    if rc != 0:
+        raise NativeError(f"mlg_rollout_selfplay_distinct_describe failed: {lib.mlg_last_error().decode()}")
     return name.value.decode(), int(lds.value)
 
 

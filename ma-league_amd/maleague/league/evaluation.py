@@ -10,7 +10,8 @@ written, and a second kernel reduces the per-env results to one summary row per 
 
 ``PolicyCrossPlayEvaluator`` is the same evaluation for ``pi_logits`` policies (COMA): ``mlg_crossplay_rollout_policy``
 picks with the policy softmax in test mode (greedy, or a draw with ``test_greedy=False``); ``evaluator_for`` picks
-the class by ``args.agent_output_type``.
+the class by ``args.agent_output_type``. ``DistinctCrossPlayEvaluator`` is the evaluation for ``mac: distinct`` policies
+(one DRQN per agent slot, a pool row being a policy's N networks back to back): ``mlg_crossplay_rollout_distinct``.
 
 The training payoff (``DistributedLeague.payoff``) holds epsilon-greedy training games of the pairs the matchmaker
 drew; this table is separate and never written into it.
@@ -151,9 +152,7 @@ class CrossPlayEvaluator:
             raise NotImplementedError("cross-play evaluation runs the recurrent agent (agent='rnn') only: "
                                       f"agent={args.agent!r} is not supported (agent='dqn' and the other non-DRQN "
                                       "agents in cross-play are out of scope)")
-        if getattr(args, "mac", "basic") == "distinct":
-            raise NotImplementedError("cross-play evaluation packs one parameter-shared network per policy: "
-                                      "mac='distinct' is not supported (cross-play over distinct MACs is out of scope)")
+        self._check_mac(args)
         self.E = int(episodes_per_launch or getattr(args, "league_eval_batch", 512))
         if self.E < 1:
             raise ValueError(f"episodes_per_launch={self.E}")
@@ -167,8 +166,20 @@ class CrossPlayEvaluator:
                                       f"{args.agent_output_type!r} is not supported (COMA in the league is out of scope "
                                       "for CrossPlayEvaluator; pi_logits policies are PolicyCrossPlayEvaluator)")
 
+    def _check_mac(self, args):
+        if getattr(args, "mac", "basic") == "distinct":
+            raise NotImplementedError(f"{type(self).__name__} packs one parameter-shared network per policy: "
+                                      "mac='distinct' is not supported here (cross-play over distinct MACs is "
+                                      "DistinctCrossPlayEvaluator, league.evaluation.evaluator_for)")
+
     def _launch(self, dims, c, stream):
         _native.call("mlg_crossplay_rollout", _native.byref(dims), _native.byref(c), stream)
+
+    def _pack_pool(self, dims, t, dst_ptr, stream):
+        """Pack the policies of one pool tensor [P, row] to ``dst_ptr``; returns the blocks written per policy."""
+        _native.call("mlg_pack_agent_pool", _native.byref(dims), t.data_ptr(), int(t.stride(0)), int(t.shape[0]),
+                     dst_ptr, stream)
+        return 1
 
     # ---- specs / dims ---------------------------------------------------------------------------------------
     def spec_of(self, plan) -> TeamsEnvSpec:
@@ -188,6 +199,10 @@ class CrossPlayEvaluator:
         return _native.MlgAgentDims(d_obs=d_obs, n_actions=A, n_agents=nh, hidden=int(a.rnn_hidden_dim),
                                     d_in=d_obs + (A if la else 0) + (nh if ai else 0), obs_last_action=int(la),
                                     obs_agent_id=int(ai))
+
+    def _blocks(self, dims) -> int:
+        """Packed blocks per policy (one shared network)."""
+        return 1
 
     def _tensor(self, name, numel, dtype):
         t = self._buf.get(name)
@@ -226,7 +241,7 @@ class CrossPlayEvaluator:
         if psize < 0:
             raise _native.NativeError(lib.mlg_last_error().decode())
         P = sum(int(t.shape[0]) for t in pools)
-        packed = self._tensor("packed_pool", P * psize, torch.float32)
+        packed = self._tensor("packed_pool", P * psize * self._blocks(dims), torch.float32)
         row = 0
         for t in pools:
             if t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or (t.shape[0] > 1 and t.stride(1) != 1):
@@ -234,9 +249,7 @@ class CrossPlayEvaluator:
                                           f"contiguous rows, got {t.dtype} {tuple(t.shape)} on {t.device}")
             if t.shape[0] == 0:
                 continue
-            _native.call("mlg_pack_agent_pool", _native.byref(dims), t.data_ptr(), int(t.stride(0)), int(t.shape[0]),
-                         packed.data_ptr() + row * psize * 4, stream)
-            row += int(t.shape[0])
+            row += int(t.shape[0]) * self._pack_pool(dims, t, packed.data_ptr() + row * psize * 4, stream)
         # ---- pair and spec tables: host copies for validation, device copies for the launch ----
         host_pairs = pairs.pairs.to(torch.int32).contiguous()
         dev_pairs = host_pairs.to(self.device)
@@ -293,12 +306,57 @@ class PolicyCrossPlayEvaluator(CrossPlayEvaluator):
                      stream)
 
 
+class DistinctCrossPlayEvaluator(CrossPlayEvaluator):
+    """CrossPlayEvaluator for ``mac: distinct`` policies (one DRQN per agent slot): every pair in one launch of
+    ``mlg_crossplay_rollout_distinct``. A pool row is a policy's ``nh`` networks back to back, agent 0 first, each in
+    named_parameters() order (``nh x n_params`` floats: runs.sp_ma_experiment.agent_vector of a DistinctMAC); a pool
+    tensor is packed with one ``mlg_pack_agent_pool`` call over its ``P * nh`` rows of stride ``n_params``."""
+
+    def _check_mac(self, args):
+        if getattr(args, "mac", "basic") != "distinct":
+            raise NotImplementedError(f"DistinctCrossPlayEvaluator evaluates mac='distinct' policies only, got mac="
+                                      f"{getattr(args, 'mac', 'basic')!r} (parameter-shared policies are "
+                                      "CrossPlayEvaluator)")
+
+    def dims_of(self, spec: TeamsEnvSpec) -> _native.MlgAgentDims:
+        a = self.args
+        nh, d_obs, A = max(spec.n_agents // 2, 1), 8 * spec.U, spec.n_actions
+        la = bool(getattr(a, "obs_last_action", True))
+        # distinct networks take no agent id (network i is agent i)
+        return _native.MlgAgentDims(d_obs=d_obs, n_actions=A, n_agents=nh, hidden=int(a.rnn_hidden_dim),
+                                    d_in=d_obs + (A if la else 0), obs_last_action=int(la), obs_agent_id=0)
+
+    def _blocks(self, dims) -> int:
+        return int(dims.n_agents)
+
+    def _pack_pool(self, dims, t, dst_ptr, stream):
+        nh, H, A = int(dims.n_agents), int(dims.hidden), int(dims.n_actions)
+        n_params = H * int(dims.d_in) + H + 6 * H * H + 6 * H + A * H + A
+        P = int(t.shape[0])
+        if int(t.shape[1]) != nh * n_params:
+            raise _native.NativeError(f"evaluate: pool rows of {int(t.shape[1])} floats for {nh} networks of "
+                                      f"{n_params} parameters each ({nh * n_params})")
+        if P > 1 and int(t.stride(0)) != nh * n_params:
+            raise _native.NativeError("evaluate: distinct pool tensors must be contiguous (row stride "
+                                      f"{int(t.stride(0))} != {nh * n_params})")
+        _native.call("mlg_pack_agent_pool", _native.byref(dims), t.data_ptr(), n_params, P * nh, dst_ptr, stream)
+        return nh
+
+    def _launch(self, dims, c, stream):
+        _native.call("mlg_crossplay_rollout_distinct", _native.byref(dims), _native.byref(c), stream)
+
+
 def evaluator_for(args, device, episodes_per_launch: Optional[int] = None) -> CrossPlayEvaluator:
-    """The evaluator of ``args.agent_output_type``: PolicyCrossPlayEvaluator for 'pi_logits', else CrossPlayEvaluator."""
-    cls = PolicyCrossPlayEvaluator if getattr(args, "agent_output_type", "q") == "pi_logits" else CrossPlayEvaluator
+    """The evaluator of ``args``: DistinctCrossPlayEvaluator for mac 'distinct' with agent_output_type 'q', else by
+    ``args.agent_output_type``: PolicyCrossPlayEvaluator for 'pi_logits', else CrossPlayEvaluator."""
+    out = getattr(args, "agent_output_type", "q")
+    if getattr(args, "mac", "basic") == "distinct" and out == "q":
+        cls = DistinctCrossPlayEvaluator
+    else:
+        cls = PolicyCrossPlayEvaluator if out == "pi_logits" else CrossPlayEvaluator
     return cls(args, device, episodes_per_launch)
 
 
 __all__ = ["PairTable", "build_pairs", "aggregate", "avg_proportional_loss", "CrossPlayResult", "CrossPlayEvaluator",
-           "PolicyCrossPlayEvaluator", "evaluator_for",
+           "PolicyCrossPlayEvaluator", "DistinctCrossPlayEvaluator", "evaluator_for",
            "GAMES", "WINS", "LOSSES", "DRAWS", "RET_HOME", "RET_AWAY", "EP_LEN"]

@@ -12,6 +12,8 @@ branch mixes are realised inside a match, the results land in K payoff cells and
 Processes, queues and the coordinator are replaced by one rank per GPU and DistributedLeague collectives.
 The self-play experiment is built once per instance and its adversary swapped between matches (the
 reference rebuilds LeagueExperiment -- replay buffer, optimizer state -- for every match).
+``DistinctLeagueInstance`` is the same loop for ``mac: distinct`` (one network per agent slot): a player's pool row is
+its N networks back to back; ``league_instance_for`` picks the class by ``args.mac``.
 """
 from __future__ import annotations
 
@@ -65,9 +67,7 @@ class LeagueInstance:
                                       "match plays one opponent)")
         self.opponents = []      # the draws of the current match (pids; equal draws repeat)
         self.group_draw = None   # mixture match: the draw (index into opponents) of every 16-env group
-        if getattr(args, "mac", "basic") == "distinct":
-            raise NotImplementedError("LeagueInstance shares one parameter-shared agent per player with the league: "
-                                      "mac='distinct' is not supported (a league over distinct MACs is out of scope)")
+        self._check_mac(args)
         self.args, self.logger, self.league = args, logger, league
         self.pid = league.player()
         self.mode = mode
@@ -102,6 +102,20 @@ class LeagueInstance:
         self.history = []  # (league iteration, opponent pid, historical?)
         self.episode = 0
 
+    def _check_mac(self, args):
+        if getattr(args, "mac", "basic") == "distinct":
+            raise NotImplementedError("LeagueInstance shares one parameter-shared agent per player with the league: "
+                                      "mac='distinct' is not supported here (a league over distinct MACs is "
+                                      "DistinctLeagueInstance, league.instance.league_instance_for)")
+
+    def _counter_agent(self, mac):
+        """The network whose trained-steps counter is this player's."""
+        return mac.agent
+
+    def _agent_state(self, mac):
+        """What load_home_agent takes from a pre-trained MAC."""
+        return mac.agent.state_dict()
+
     def _plan(self, ai: bool):
         """The home team mirrored (league_experiment_process.py:57-62 with away=None): this player's league team,
         or the env config's own plan when the league has no team compositions."""
@@ -135,7 +149,7 @@ class LeagueInstance:
             exp.start(play_time_seconds=play_time_seconds)
         else:
             exp.start(max_iterations=iterations)
-        self.experiment.load_home_agent(exp.home_mac.agent.state_dict())
+        self.experiment.load_home_agent(self._agent_state(exp.home_mac))
         del exp
 
     def view(self) -> LeagueView:
@@ -150,7 +164,7 @@ class LeagueInstance:
         home = self.experiment.home_mac
         self.league.sync_payoff()
         # payoff + this player's trained steps in one device -> host read (matchmaking then runs on the host copy)
-        agent = home.agent
+        agent = self._counter_agent(home)
         counter = agent.trained_counter(self.league.device) if hasattr(agent, "trained_counter") else None
         dev_steps = self.league.host_snapshot(counter)
         steps = agent.trained_steps_with(dev_steps) if counter is not None else int(agent.trained_steps)
@@ -295,6 +309,40 @@ class LeagueInstance:
             self.play(iterations_per_match)
         self.league.sync_payoff()
         return self.history
+
+
+class DistinctLeagueInstance(LeagueInstance):
+    """LeagueInstance for ``mac: distinct``: every player is a DistinctMAC (one DRQN per agent slot -- the league's
+    heterogeneous rosters are the case for it), its pool row the N networks back to back, agent 0 first, each in
+    named_parameters() order (``N x n_params`` floats: agent_vector / load_agent_vector). Matches run through
+    SelfPlayDistinctParallelStepper (one mlg_rollout_selfplay_distinct launch per run), the home side trains in the
+    fused learner (cfg.distinct = 1) and evaluate_pool plays DistinctCrossPlayEvaluator. One opponent per match."""
+
+    def __init__(self, args, logger, league: DistributedLeague, mode="matchmaking", role=None, seed=0,
+                 experiment=None, teams=None, opponents_per_match: int = 1):
+        if int(opponents_per_match) > 1:
+            raise NotImplementedError(f"DistinctLeagueInstance(opponents_per_match={opponents_per_match}): opponent "
+                                      "mixtures with mac='distinct' are not supported (a match of DistinctMACs plays "
+                                      "one opponent)")
+        super().__init__(args, logger, league, mode=mode, role=role, seed=seed, experiment=experiment, teams=teams,
+                         opponents_per_match=opponents_per_match)
+
+    def _check_mac(self, args):
+        if getattr(args, "mac", "basic") != "distinct":
+            raise NotImplementedError(f"DistinctLeagueInstance runs mac='distinct' only, got mac="
+                                      f"{getattr(args, 'mac', 'basic')!r} (parameter-shared MACs are LeagueInstance)")
+
+    def _counter_agent(self, mac):
+        return mac.agents[0]  # the learner's one optimizer launch counts for all N networks: their counters are equal
+
+    def _agent_state(self, mac):
+        return [a.state_dict() for a in mac.agents]
+
+
+def league_instance_for(args, logger, league, **kw) -> LeagueInstance:
+    """The league instance of ``args.mac``: DistinctLeagueInstance for 'distinct', else LeagueInstance."""
+    cls = DistinctLeagueInstance if getattr(args, "mac", "basic") == "distinct" else LeagueInstance
+    return cls(args, logger, league, **kw)
 
 
 def league_roles_for(world: int, args) -> list:

@@ -204,7 +204,7 @@ def main(argv=None) -> dict:
     cfg["league_eval_seed"] = seed  # one env seed for every rank's share of the evaluation pairs (equal terms)
     args = to_args(cfg)
 
-    from maleague.league import DistributedLeague, LeagueInstance, PayoffEntry
+    from maleague.league import DistributedLeague, PayoffEntry, league_instance_for
     max_hist = a.max_historical if a.max_historical is not None else 4 * world
     lg = DistributedLeague(n_players=world, device=dev, seed=seed, max_historical=max_hist)
     token = datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
@@ -227,9 +227,10 @@ def main(argv=None) -> dict:
     else:
         from maleague.custom_logging import MainLogger
         logger = MainLogger(args=args)
-        inst = LeagueInstance(args, logger, lg, mode="matchmaking" if roles[0] is None else "rolebased",
-                              role=None if roles[0] is None else roles, seed=seed, teams=player_teams,
-                              opponents_per_match=int(cfg.get("league_opponents_per_match", 1) or 1))
+        # LeagueInstance, or DistinctLeagueInstance with mac=distinct (one network per agent slot)
+        inst = league_instance_for(args, logger, lg, mode="matchmaking" if roles[0] is None else "rolebased",
+                                   role=None if roles[0] is None else roles, seed=seed, teams=player_teams,
+                                   opponents_per_match=int(cfg.get("league_opponents_per_match", 1) or 1))
         play_s = float(cfg.get("play_time_mins", 1.0)) * 60.0
         runtime_s = float(cfg.get("league_runtime_hours", 0.0)) * 3600.0
         if a.pretrain_iterations is not None:

@@ -68,5 +68,6 @@ class JointPolicyCorrelationEvaluationRun:
         n = self.instances_num
         self.logger.info("Evaluate {} pairings for {} episodes.".format(n * n, self.eval_episodes))
         pairs = build_pairs(range(n), range(n, 2 * n))
-        # CrossPlayEvaluator, or PolicyCrossPlayEvaluator for pi_logits policies (COMA)
+        # CrossPlayEvaluator, PolicyCrossPlayEvaluator for pi_logits policies (COMA), or DistinctCrossPlayEvaluator for
+        # mac: distinct (a pool row is then a policy's N networks back to back)
         return evaluator_for(self._instance_args(0), pool.device).evaluate(pool, pairs, self.eval_episodes)

@@ -3,6 +3,10 @@ LeagueExperiment, src/runs/train/league_experiment.py:6-24).
 
 The opposing team is a second, frozen policy instead of the scripted AI: both MACs act in the same
 fused rollout launch (SelfPlayParallelStepper), only the home learner trains (sp_ma_experiment.py:81).
+
+With ``mac: distinct`` both MACs are DistinctMACs (one network per agent slot) and the launch is
+SelfPlayDistinctParallelStepper's; an agent vector is then the N networks back to back, agent 0 first, each in
+named_parameters() order (the learner's flat layout).
 """
 from __future__ import annotations
 
@@ -11,33 +15,46 @@ from typing import OrderedDict
 import torch
 
 from ..controllers import REGISTRY as mac_REGISTRY
+from ..controllers.distinct_controller import DistinctMAC
 from ..learners.q_learner import FlatParams
 from ..utils.flat import module_flat_view
+from ..steppers import SELF_DISTINCT_REGISTRY as self_distinct_steppers_REGISTRY
 from ..steppers import SELF_POLICY_REGISTRY as self_policy_steppers_REGISTRY
 from ..steppers import SELF_REGISTRY as self_steppers_REGISTRY
 from .ma_experiment import MultiAgentExperiment
 
 
+def _networks(mac):
+    """(the module holding the MAC's agent parameters, what repacks them): the shared agent network, or a DistinctMAC's
+    ModuleList -- its parameters() are the N networks back to back, agent 0 first -- and the MAC itself (its pool)."""
+    if isinstance(mac, DistinctMAC):
+        return mac.agents, mac
+    return mac.agent, mac.agent
+
+
 def agent_vector(mac) -> torch.Tensor:
-    """The MAC's agent parameters as one flat vector (named_parameters order): a view of them when they are back
-    to back in one buffer (a learner's FlatParams -- callers copy what they keep), else a concatenated copy."""
-    flat = module_flat_view(mac.agent)
+    """The MAC's agent parameters as one flat vector (named_parameters order; a DistinctMAC's N networks back to back,
+    agent 0 first): a view of them when they are back to back in one buffer (a learner's FlatParams -- callers copy
+    what they keep), else a concatenated copy."""
+    net, _ = _networks(mac)
+    flat = module_flat_view(net)
     if flat is not None:
         return flat.detach()
-    return torch.nn.utils.parameters_to_vector(mac.agent.parameters()).detach()
+    return torch.nn.utils.parameters_to_vector(net.parameters()).detach()
 
 
 @torch.no_grad()
 def load_agent_vector(mac, vec: torch.Tensor):
     """In-place copy (keeps a learner's flat-parameter views valid; bumps versions -> weights repacked)."""
-    flat = module_flat_view(mac.agent)
+    net, packer = _networks(mac)
+    flat = module_flat_view(net)
     if flat is not None:  # parameters back to back in one buffer: one copy
         if flat.numel() != vec.numel():
             raise ValueError(f"parameter vector of {vec.numel()} floats for an agent of {flat.numel()}")
         flat.copy_(vec.reshape(-1))
-        mac.agent.mark_dirty()  # writes through the flat view bump no parameter version: repack explicitly
+        packer.mark_dirty()  # writes through the flat view bump no parameter version: repack explicitly
         return
-    params = list(mac.agent.parameters())
+    params = list(net.parameters())
     n = sum(p.numel() for p in params)
     if n != vec.numel():
         raise ValueError(f"parameter vector of {vec.numel()} floats for an agent of {n}")
@@ -46,6 +63,8 @@ def load_agent_vector(mac, vec: torch.Tensor):
         k = p.numel()
         p.copy_(vec[off:off + k].view_as(p))
         off += k
+    if packer is mac:  # a DistinctMAC repacks its pool
+        mac.mark_dirty()
 
 
 class SelfPlayMultiAgentExperiment(MultiAgentExperiment):
@@ -54,11 +73,13 @@ class SelfPlayMultiAgentExperiment(MultiAgentExperiment):
         # the away agent uses the home buffer's scheme (sp_ma_experiment.py:24-25)
         self.away_mac = mac_REGISTRY[self.args.mac](self.home_buffer.scheme, self.groups, self.args)
         # the frozen opponent's parameters as views of one flat buffer: an opponent swap is one copy
-        FlatParams(self.away_mac.agent.parameters(), self.args.device)
+        # (a DistinctMAC's N networks in agent order: its pool then packs in one mlg_pack_agent_pool launch)
+        FlatParams(_networks(self.away_mac)[0].parameters(), self.args.device)
 
     def load_adversary(self, agent: OrderedDict):
-        """Frozen opponent parameters (a DRQN state_dict), sp_ma_experiment.py:27-29."""
-        self.away_mac.load_state_dict(agent=agent)
+        """Frozen opponent parameters (a DRQN state_dict; mac: distinct: the list of N state dicts),
+        sp_ma_experiment.py:27-29."""
+        self.away_mac.load_state_dict(agent)
         del agent
 
     def load_adversary_vector(self, vec: torch.Tensor):
@@ -78,8 +99,13 @@ class SelfPlayMultiAgentExperiment(MultiAgentExperiment):
 
     def _build_stepper(self, log_start_t=0):
         # two pi_logits MACs (COMA) roll out through the policy softmax and the multinomial draw
-        reg = self_policy_steppers_REGISTRY if getattr(self.args, "agent_output_type", "q") == "pi_logits" \
-            else self_steppers_REGISTRY
+        # two DistinctMACs (mac: distinct) through mlg_rollout_selfplay_distinct
+        if getattr(self.args, "mac", "basic") == "distinct":
+            reg = self_distinct_steppers_REGISTRY
+        elif getattr(self.args, "agent_output_type", "q") == "pi_logits":
+            reg = self_policy_steppers_REGISTRY
+        else:
+            reg = self_steppers_REGISTRY
         return reg[self.args.runner](args=self.args, logger=self.logger, log_start_t=log_start_t)
 
     def _init_stepper(self):
@@ -117,7 +143,8 @@ class LeagueExperiment(SelfPlayMultiAgentExperiment):
         self.last_test_T = self.stepper.t_env  # tests skipped in the league to save compute (:17-19)
 
     def load_home_agent(self, agent: OrderedDict):
-        self.home_mac.load_state_dict(agent=agent)
+        """A DRQN state_dict (mac: distinct: the list of N state dicts)."""
+        self.home_mac.load_state_dict(agent)
         del agent
 
     def load_adversary_mix(self, rows, group_opponent, teams=None, home=None):

@@ -2,13 +2,16 @@
 same keys resolve to the entity-env steppers (see build_stepper)."""
 from .entity_stepper import EntityEpisodeStepper, EntityParallelStepper
 from .parallel_stepper import EnvStepper, EpisodeStepper, ParallelStepper
-from .self_play_stepper import (OpponentMix, SelfPlayParallelStepper, SelfPlayPolicyParallelStepper, SelfPlayPolicyStepper,
+from .self_play_stepper import (OpponentMix, SelfPlayDistinctParallelStepper, SelfPlayDistinctStepper,
+                                SelfPlayParallelStepper, SelfPlayPolicyParallelStepper, SelfPlayPolicyStepper,
                                 SelfPlayStepper)
 
 REGISTRY = {"episode": EpisodeStepper, "parallel": ParallelStepper}
 SELF_REGISTRY = {"episode": SelfPlayStepper, "parallel": SelfPlayParallelStepper}
 # two pi_logits MACs (COMA in self-play and the league): the policy softmax and the multinomial draw on both sides
 SELF_POLICY_REGISTRY = {"episode": SelfPlayPolicyStepper, "parallel": SelfPlayPolicyParallelStepper}
+# two DistinctMACs (mac: distinct in self-play and the league): one network per agent slot on both sides
+SELF_DISTINCT_REGISTRY = {"episode": SelfPlayDistinctStepper, "parallel": SelfPlayDistinctParallelStepper}
 ENTITY_REGISTRY = {"episode": EntityEpisodeStepper, "parallel": EntityParallelStepper}
 
 
@@ -18,5 +21,6 @@ def build_stepper(args, logger, log_start_t=0):
 
 
 __all__ = ["EnvStepper", "OpponentMix", "EpisodeStepper", "ParallelStepper", "SelfPlayParallelStepper", "SelfPlayStepper",
-           "SelfPlayPolicyParallelStepper", "SelfPlayPolicyStepper", "EntityParallelStepper", "EntityEpisodeStepper",
-           "REGISTRY", "SELF_REGISTRY", "SELF_POLICY_REGISTRY", "ENTITY_REGISTRY", "build_stepper"]
+           "SelfPlayPolicyParallelStepper", "SelfPlayPolicyStepper", "SelfPlayDistinctParallelStepper",
+           "SelfPlayDistinctStepper", "EntityParallelStepper", "EntityEpisodeStepper", "REGISTRY", "SELF_REGISTRY",
+           "SELF_POLICY_REGISTRY", "SELF_DISTINCT_REGISTRY", "ENTITY_REGISTRY", "build_stepper"]

@@ -16,6 +16,10 @@ opponent.
 Two ``pi_logits`` MACs (COMA in self-play and the league): ``SelfPlayPolicyParallelStepper`` / ``SelfPlayPolicyStepper``
 (``SELF_POLICY_REGISTRY``) make the same run with one launch of ``mlg_rollout_selfplay_policy``: each side's outputs go
 through the policy softmax with that side's epsilon floor and the action is drawn by the multinomial rule.
+
+Two ``DistinctMAC``s (mac: distinct, one DRQN per agent slot on both sides): ``SelfPlayDistinctParallelStepper`` /
+``SelfPlayDistinctStepper`` (``SELF_DISTINCT_REGISTRY``) make the same run with one launch of
+``mlg_rollout_selfplay_distinct``: agent ln of side s acts with network ln of side s's MAC.
 """
 from __future__ import annotations
 
@@ -28,7 +32,7 @@ import torch
 from .. import _native
 from ..components.batch_view import mlg_batch
 from ..components.replay_buffer import RingEpisodeBatch
-from ..controllers.distinct_controller import refuse_distinct
+from ..controllers.distinct_controller import DistinctMAC
 from ..exceptions import MultiAgentControllerNotInitialized
 from ..modules.agents import DRQNAgentNetwork
 from .parallel_stepper import LazyEnvInfos, ParallelStepper
@@ -130,7 +134,11 @@ class SelfPlayParallelStepper(ParallelStepper):
         if away_mac is None:
             raise ValueError("self-play needs an away MAC (initialize(..., home_mac, away_mac))")
         for side, mac in (("home", home_mac), ("away", away_mac)):
-            refuse_distinct(mac, f"self-play rollouts ({side} MAC)")
+            if isinstance(mac, DistinctMAC):
+                raise NotImplementedError(f"{type(self).__name__} does not support mac='distinct' (one network per "
+                                          f"agent slot; the {side} MAC): it drives parameter-shared MACs (mac='basic') "
+                                          "only. Two DistinctMACs are SelfPlayDistinctParallelStepper, "
+                                          "steppers.SELF_DISTINCT_REGISTRY['parallel']")
             self._check_output_type(side, mac)
             agent = getattr(mac, "agent", None)
             if agent is not None and not isinstance(agent, DRQNAgentNetwork):
@@ -201,7 +209,7 @@ class SelfPlayParallelStepper(ParallelStepper):
             self.away_batch = self.new_batch_fn()
             mb_a, k = mlg_batch(self.away_batch)
         keep.append(k)
-        h_agent, a_agent = self.home_mac.agent, self.away_mac.agent
+        h_agent, a_agent = self._packers()
         d, d_a = h_agent.dims(), a_agent.dims()
         if any(getattr(d, f) != getattr(d_a, f) for f, _ in d._fields_):
             raise ValueError("home and away agents must have the same architecture")
@@ -233,6 +241,10 @@ class SelfPlayParallelStepper(ParallelStepper):
         self._finish_post()
         return self.home_batch, self.away_batch, LazyEnvInfos(self, self._run_id)
 
+
+    def _packers(self):
+        """What gives each side's dims() and packed() weights: the shared agent network."""
+        return self.home_mac.agent, self.away_mac.agent
 
     def _launch_selfplay(self, st, d, p_h, p_a, mb_h, mb_a, run_info, eps_h, eps_a, test_mode):
         _native.call("mlg_rollout_selfplay", _native.byref(self._cspec), _native.byref(st), _native.byref(d),
@@ -299,3 +311,50 @@ class SelfPlayPolicyParallelStepper(SelfPlayParallelStepper):
 
 class SelfPlayPolicyStepper(_SingleEnv, SelfPlayPolicyParallelStepper):
     """Single-env form of SelfPlayPolicyParallelStepper: B = 1, returns the final env_info dict."""
+
+
+class SelfPlayDistinctParallelStepper(SelfPlayParallelStepper):
+    """Self-play of two ``DistinctMAC``s (mac: distinct): one launch of ``mlg_rollout_selfplay_distinct`` per run, agent
+    ln of side s acting with network ln of side s's packed pool (``DistinctMAC.packed()``). Selection is
+    SelfPlayParallelStepper's (epsilon-greedy over Q values, one epsilon per side, the same counter-RNG streams), and so
+    are the batches, rewards, run summary and ring / away-batch reuse."""
+
+    def initialize(self, scheme, groups, preprocess, home_mac, away_mac=None):
+        if away_mac is None:
+            raise ValueError("self-play needs an away MAC (initialize(..., home_mac, away_mac))")
+        for side, mac in (("home", home_mac), ("away", away_mac)):
+            if not isinstance(mac, DistinctMAC):
+                raise NotImplementedError(f"{type(self).__name__} drives two DistinctMACs (mac='distinct'): the {side} "
+                                          f"MAC is a {type(mac).__name__} (a distinct side against a parameter-shared "
+                                          "side is out of scope; two parameter-shared MACs are steppers.SELF_REGISTRY)")
+        d, d_a = home_mac.dims(), away_mac.dims()
+        if any(getattr(d, f) != getattr(d_a, f) for f, _ in d._fields_):
+            raise ValueError("home and away DistinctMACs must have the same architecture (equal agent dims)")
+        ParallelStepper.initialize(self, scheme, groups, preprocess, home_mac)
+        self.away_mac = away_mac
+        self._away_buf = None
+
+    def set_opponent_mix(self, mix):
+        if mix is None:
+            return
+        raise NotImplementedError("opponent mixtures with mac='distinct' are not supported (mlg_rollout_selfplay_mix "
+                                  "reads one parameter-shared network per opponent; a match of DistinctMACs plays one "
+                                  "opponent)")
+
+    def describe_rollout(self):
+        if self.home_mac is None:
+            raise MultiAgentControllerNotInitialized()
+        return _native.rollout_selfplay_distinct_describe(self._cspec, self.home_mac.dims())
+
+    def _packers(self):
+        return self.home_mac, self.away_mac  # a DistinctMAC has dims() and packed() itself (the pool of N networks)
+
+    def _launch_selfplay(self, st, d, p_h, p_a, mb_h, mb_a, run_info, eps_h, eps_a, test_mode):
+        _native.call("mlg_rollout_selfplay_distinct", _native.byref(self._cspec), _native.byref(st), _native.byref(d),
+                     _native.ptr(p_h), _native.ptr(p_a), _native.byref(mb_h), _native.byref(mb_a),
+                     _native.byref(run_info), float(eps_h), float(eps_a), int(bool(test_mode)),
+                     _native.stream_ptr(self.device))
+
+
+class SelfPlayDistinctStepper(_SingleEnv, SelfPlayDistinctParallelStepper):
+    """Single-env form of SelfPlayDistinctParallelStepper: B = 1, returns the final env_info dict."""
