@@ -765,6 +765,44 @@ int mlg_rollout_ff(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgentDims *
 int mlg_rollout_ff_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, char *name, int32_t name_cap,
                             int64_t *lds_bytes);
 
+/* Packs P flat feed-forward parameter rows (DQNAgentNetwork.PARAM_ORDER: fc1.weight, fc1.bias, fc2.weight, fc2.bias;
+ * row p at flat + p * row_stride floats) into packed_pool [P][mlg_ff_packed_size(dims)]; each row equals mlg_ff_pack()
+ * of the same parameters bit for bit (the contract of mlg_pack_agent_pool). One launch. NULL pointers, P < 1 and a
+ * row_stride below the parameter count are refused through mlg_last_error. */
+int mlg_ff_pack_pool(const MlgAgentDims *dims, const float *flat, int64_t row_stride, int32_t P, float *packed_pool,
+                     void *stream);
+
+/* One full SelfPlayParallelStepper.run with two feed-forward MACs, in one launch: mlg_rollout_selfplay's arguments and
+ * run semantics (`dims` describe one side; home_packed / away_packed are mlg_ff_pack() blocks, 16-byte aligned; the RNG
+ * key mlg_env_key(seed, b), the global agent index s * nh + ln as the epsilon stream index, one epsilon per side,
+ * reward[0] / reward[1] and ret_away, the ring, full-write and slot_extent modes and the run summary).
+ * Structure (mlg_rollout_ff's): a workgroup owns 16 envs for the whole episode, env state in LDS; the agent phase is
+ * fc1 -> ReLU -> fc2 per action tile -> masked first-index argmax -> epsilon-greedy redraw, no hidden state carried.
+ * The two-side tile layout is mlg_rollout_selfplay_policy's: tps = ceil(16 nh / 16) = nh tiles per side, tile >= tps
+ * is the away side, row r = (tile - side * tps) * 16 + col is env r / nh, side-local agent ln = r % nh (the agent-id
+ * input); the weight view, the batch and the epsilon of a tile are its side's.
+ * Dispatch: tiles = 2 * nh, waves W = min(tiles, 8), tpw = ceil(tiles / W). Names "ffsp-lds/tpwK": both sides' weight
+ * images in LDS beside the env state, the home image first; "ffsp-global/tpwK": weights read from global memory (the
+ * images do not fit, or MLG_ROLLOUT_GLOBAL_WEIGHTS is set). The two arms differ in where a weight is read from, not in
+ * the order of any sum. No float atomics: two runs from the same state are bit-identical.
+ * Refused through mlg_last_error, without launching: more than 16 agents per side (the message names the tile count),
+ * dims that are not one side of the env, a spec without two policy teams, H outside 32 / 64 / 128. */
+int mlg_rollout_selfplay_ff(const MlgEnvSpec *spec, MlgEnvState *st, const MlgAgentDims *dims,
+                            const float *home_packed, const float *away_packed, MlgBatch *home, MlgBatch *away,
+                            MlgRunInfo *info, float eps_home, float eps_away, int32_t test_mode, void *stream);
+/* Host only, launches nothing (the contract of mlg_rollout_describe). mlg_rollout_selfplay_ff takes its decision from
+ * the same function. Nonzero (mlg_last_error) where it would refuse the spec or the dims. */
+int mlg_rollout_selfplay_ff_describe(const MlgEnvSpec *spec, const MlgAgentDims *dims, char *name, int32_t name_cap,
+                                     int64_t *lds_bytes);
+
+/* mlg_crossplay_rollout for feed-forward policies: the same MlgCrossplay block, host checks, per-env outputs and
+ * fixed-order summary reduce; packed_pool rows are mlg_ff_packed_size(dims) floats (mlg_ff_pack_pool writes them). Env
+ * (pair k, episode e) is bit-identical to env e of one test-mode mlg_rollout_selfplay_ff of that pair under
+ * specs[pair.spec] with episode counter episode0. MLG_CROSSPLAY_OBS_WORKSPACE=1 forces the obs / avail rows into
+ * `workspace`. No float atomics. */
+int64_t mlg_crossplay_ff_workspace_floats(const MlgAgentDims *dims, int32_t n_pairs, int32_t E);
+int mlg_crossplay_rollout_ff(const MlgAgentDims *dims, const MlgCrossplay *c, void *stream);
+
 /* ---- Distinct per-agent networks (mac: distinct): agent slot i acts with network i, no parameter sharing --------
  * DistinctMAC (src/marl/controllers/distinct_agents_controller.py). packed_pool [N][mlg_packed_agent_size(dims)]:
  * row i is the mlg_pack_agent() block of network i (mlg_pack_agent_pool writes exactly this); N = dims->n_agents is

@@ -224,6 +224,11 @@ SIGNATURES = {
     "mlg_ff_backward": (ctypes.c_int, [_P] * 8 + [_I, _P]),
     "mlg_rollout_ff": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
     "mlg_rollout_ff_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
+    "mlg_ff_pack_pool": (ctypes.c_int, [_P, _P, ctypes.c_int64, _I, _P, _P]),
+    "mlg_rollout_selfplay_ff": (ctypes.c_int, [_P] * 8 + [ctypes.c_float, ctypes.c_float, _I, _P]),
+    "mlg_rollout_selfplay_ff_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
+    "mlg_crossplay_ff_workspace_floats": (ctypes.c_int64, [_P, _I, _I]),
+    "mlg_crossplay_rollout_ff": (ctypes.c_int, [_P, _P, _P]),
     "mlg_mac_forward_distinct": (ctypes.c_int, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "mlg_rollout_distinct": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
     "mlg_rollout_distinct_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
@@ -337,6 +342,20 @@ def rollout_ff_describe(spec: MlgEnvSpec, dims: MlgAgentDims) -> tuple[str, int]
     rc = lib.mlg_rollout_ff_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name), ctypes.byref(lds))
     if rc != 0:
         raise NativeError(f"mlg_rollout_ff_describe failed: {lib.mlg_last_error().decode()}")
+    return name.value.decode(), int(lds.value)
+
+
+def rollout_selfplay_ff_describe(spec: MlgEnvSpec, dims: MlgAgentDims) -> tuple[str, int]:
+    """(arm name "ffsp-lds/tpwK" or "ffsp-global/tpwK", dynamic LDS bytes) of the launch mlg_rollout_selfplay_ff would
+    make for this spec and one side's agent dims under the current MLG_ROLLOUT_GLOBAL_WEIGHTS environment
+    (mlg_rollout_selfplay_ff_describe: host only, needs no GPU)."""
+    lib = load()
+    name = ctypes.create_string_buffer(32)
+    lds = ctypes.c_int64(0)
+    rc = lib.mlg_rollout_selfplay_ff_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name),
+                                              ctypes.byref(lds))
+    if rc != 0:
+        raise NativeError(f"mlg_rollout_selfplay_ff_describe failed: {lib.mlg_last_error().decode()}")
     return name.value.decode(), int(lds.value)
 
 

@@ -12,6 +12,8 @@ written, and a second kernel reduces the per-env results to one summary row per 
 picks with the policy softmax in test mode (greedy, or a draw with ``test_greedy=False``); ``evaluator_for`` picks
 the class by ``args.agent_output_type``. ``DistinctCrossPlayEvaluator`` is the evaluation for ``mac: distinct`` policies
 (one DRQN per agent slot, a pool row being a policy's N networks back to back): ``mlg_crossplay_rollout_distinct``.
+``FFCrossPlayEvaluator`` is the evaluation for feed-forward policies (agent: dqn, a pool row being fc1 and fc2 flat):
+``mlg_ff_pack_pool`` and ``mlg_crossplay_rollout_ff``.
 
 The training payoff (``DistributedLeague.payoff``) holds epsilon-greedy training games of the pairs the matchmaker
 drew; this table is separate and never written into it.
@@ -148,10 +150,7 @@ class CrossPlayEvaluator:
         self.args = args
         self.device = torch.device(device)
         self._check_output_type(args)
-        if getattr(args, "agent", "rnn") != "rnn":
-            raise NotImplementedError("cross-play evaluation runs the recurrent agent (agent='rnn') only: "
-                                      f"agent={args.agent!r} is not supported (agent='dqn' and the other non-DRQN "
-                                      "agents in cross-play are out of scope)")
+        self._check_agent(args)
         self._check_mac(args)
         self.E = int(episodes_per_launch or getattr(args, "league_eval_batch", 512))
         if self.E < 1:
@@ -166,6 +165,12 @@ class CrossPlayEvaluator:
                                       f"{args.agent_output_type!r} is not supported (COMA in the league is out of scope "
                                       "for CrossPlayEvaluator; pi_logits policies are PolicyCrossPlayEvaluator)")
 
+    def _check_agent(self, args):
+        if getattr(args, "agent", "rnn") != "rnn":
+            raise NotImplementedError("cross-play evaluation runs the recurrent agent (agent='rnn') only: "
+                                      f"agent={args.agent!r} is not supported (agent='dqn' and the other non-DRQN "
+                                      "agents in cross-play are out of scope)")
+
     def _check_mac(self, args):
         if getattr(args, "mac", "basic") == "distinct":
             raise NotImplementedError(f"{type(self).__name__} packs one parameter-shared network per policy: "
@@ -174,6 +179,14 @@ class CrossPlayEvaluator:
 
     def _launch(self, dims, c, stream):
         _native.call("mlg_crossplay_rollout", _native.byref(dims), _native.byref(c), stream)
+
+    def _packed_size(self, lib, dims) -> int:
+        """Floats of one packed block (negative: the native error is set)."""
+        return int(lib.mlg_packed_agent_size(_native.byref(dims)))
+
+    def _workspace_floats(self, lib, dims, n_pairs, E) -> int:
+        """Workspace floats of one launch (negative: the native error is set)."""
+        return int(lib.mlg_crossplay_workspace_floats(_native.byref(dims), n_pairs, E))
 
     def _pack_pool(self, dims, t, dst_ptr, stream):
         """Pack the policies of one pool tensor [P, row] to ``dst_ptr``; returns the blocks written per policy."""
@@ -237,7 +250,7 @@ class CrossPlayEvaluator:
         dims = self.dims_of(specs[0])
         stream = _native.stream_ptr(self.device)
         # ---- the pool, packed (one launch per pool tensor; rows read in place through their stride) ----
-        psize = int(lib.mlg_packed_agent_size(_native.byref(dims)))
+        psize = self._packed_size(lib, dims)
         if psize < 0:
             raise _native.NativeError(lib.mlg_last_error().decode())
         P = sum(int(t.shape[0]) for t in pools)
@@ -256,7 +269,7 @@ class CrossPlayEvaluator:
         cspecs = (_native.MlgEnvSpec * len(specs))(*[s.to_c() for s in specs])
         dev_specs = torch.frombuffer(bytearray(bytes(cspecs)), dtype=torch.uint8).to(self.device)
         E_max = min(self.E, episodes)
-        ws_floats = int(lib.mlg_crossplay_workspace_floats(_native.byref(dims), n, E_max))
+        ws_floats = self._workspace_floats(lib, dims, n, E_max)
         if ws_floats < 0:
             raise _native.NativeError(lib.mlg_last_error().decode())
         ws = self._tensor("workspace", ws_floats, torch.float32)
@@ -346,17 +359,52 @@ class DistinctCrossPlayEvaluator(CrossPlayEvaluator):
         _native.call("mlg_crossplay_rollout_distinct", _native.byref(dims), _native.byref(c), stream)
 
 
+class FFCrossPlayEvaluator(CrossPlayEvaluator):
+    """CrossPlayEvaluator for feed-forward policies (agent: dqn): every pair in one launch of
+    ``mlg_crossplay_rollout_ff``. A pool row is a policy's four tensors flat in ``DQNAgentNetwork.PARAM_ORDER``
+    (runs.sp_ma_experiment.agent_vector of a feed-forward MAC); a pool tensor is packed by one ``mlg_ff_pack_pool``
+    launch into rows of ``mlg_ff_packed_size`` floats."""
+
+    def _check_agent(self, args):
+        if getattr(args, "agent", "rnn") != "dqn":
+            raise NotImplementedError("FFCrossPlayEvaluator evaluates feed-forward policies (agent='dqn') only, got "
+                                      f"agent={getattr(args, 'agent', 'rnn')!r} (recurrent policies are "
+                                      "CrossPlayEvaluator)")
+
+    def _packed_size(self, lib, dims) -> int:
+        return int(lib.mlg_ff_packed_size(_native.byref(dims)))
+
+    def _workspace_floats(self, lib, dims, n_pairs, E) -> int:
+        return int(lib.mlg_crossplay_ff_workspace_floats(_native.byref(dims), n_pairs, E))
+
+    def _pack_pool(self, dims, t, dst_ptr, stream):
+        H, A = int(dims.hidden), int(dims.n_actions)
+        n_params = H * int(dims.d_in) + H + A * H + A
+        if int(t.shape[1]) != n_params:
+            raise _native.NativeError(f"evaluate: pool rows of {int(t.shape[1])} floats for a feed-forward agent of "
+                                      f"{n_params} parameters")
+        _native.call("mlg_ff_pack_pool", _native.byref(dims), t.data_ptr(), int(t.stride(0)), int(t.shape[0]),
+                     dst_ptr, stream)
+        return 1
+
+    def _launch(self, dims, c, stream):
+        _native.call("mlg_crossplay_rollout_ff", _native.byref(dims), _native.byref(c), stream)
+
+
 def evaluator_for(args, device, episodes_per_launch: Optional[int] = None) -> CrossPlayEvaluator:
-    """The evaluator of ``args``: DistinctCrossPlayEvaluator for mac 'distinct' with agent_output_type 'q', else by
+    """The evaluator of ``args``: DistinctCrossPlayEvaluator for mac 'distinct' with agent_output_type 'q',
+    FFCrossPlayEvaluator for agent 'dqn' with mac 'basic' and agent_output_type 'q', else by
     ``args.agent_output_type``: PolicyCrossPlayEvaluator for 'pi_logits', else CrossPlayEvaluator."""
     out = getattr(args, "agent_output_type", "q")
     if getattr(args, "mac", "basic") == "distinct" and out == "q":
         cls = DistinctCrossPlayEvaluator
+    elif getattr(args, "agent", "rnn") == "dqn" and getattr(args, "mac", "basic") == "basic" and out == "q":
+        cls = FFCrossPlayEvaluator
     else:
         cls = PolicyCrossPlayEvaluator if out == "pi_logits" else CrossPlayEvaluator
     return cls(args, device, episodes_per_launch)
 
 
 __all__ = ["PairTable", "build_pairs", "aggregate", "avg_proportional_loss", "CrossPlayResult", "CrossPlayEvaluator",
-           "PolicyCrossPlayEvaluator", "DistinctCrossPlayEvaluator", "evaluator_for",
+           "PolicyCrossPlayEvaluator", "DistinctCrossPlayEvaluator", "FFCrossPlayEvaluator", "evaluator_for",
            "GAMES", "WINS", "LOSSES", "DRAWS", "RET_HOME", "RET_AWAY", "EP_LEN"]

@@ -65,6 +65,10 @@ class LeagueInstance:
             raise NotImplementedError(f"LeagueInstance(opponents_per_match={self.opponents_per_match}): opponent "
                                       "mixtures with agent_output_type='pi_logits' are not supported (a pi_logits "
                                       "match plays one opponent)")
+        if self.opponents_per_match > 1 and getattr(args, "agent", "rnn") == "dqn":
+            raise NotImplementedError(f"LeagueInstance(opponents_per_match={self.opponents_per_match}): opponent "
+                                      "mixtures with agent='dqn' are not supported (mlg_rollout_selfplay_mix packs "
+                                      "DRQN blocks; a match of feed-forward agents plays one opponent)")
         self.opponents = []      # the draws of the current match (pids; equal draws repeat)
         self.group_draw = None   # mixture match: the draw (index into opponents) of every 16-env group
         self._check_mac(args)

@@ -19,6 +19,7 @@ from ..controllers.distinct_controller import DistinctMAC
 from ..learners.q_learner import FlatParams
 from ..utils.flat import module_flat_view
 from ..steppers import SELF_DISTINCT_REGISTRY as self_distinct_steppers_REGISTRY
+from ..steppers import SELF_FF_REGISTRY as self_ff_steppers_REGISTRY
 from ..steppers import SELF_POLICY_REGISTRY as self_policy_steppers_REGISTRY
 from ..steppers import SELF_REGISTRY as self_steppers_REGISTRY
 from .ma_experiment import MultiAgentExperiment
@@ -100,10 +101,13 @@ class SelfPlayMultiAgentExperiment(MultiAgentExperiment):
     def _build_stepper(self, log_start_t=0):
         # two pi_logits MACs (COMA) roll out through the policy softmax and the multinomial draw
         # two DistinctMACs (mac: distinct) through mlg_rollout_selfplay_distinct
+        # two feed-forward MACs (agent: dqn) through mlg_rollout_selfplay_ff
         if getattr(self.args, "mac", "basic") == "distinct":
             reg = self_distinct_steppers_REGISTRY
         elif getattr(self.args, "agent_output_type", "q") == "pi_logits":
             reg = self_policy_steppers_REGISTRY
+        elif getattr(self.args, "agent", "rnn") == "dqn":
+            reg = self_ff_steppers_REGISTRY
         else:
             reg = self_steppers_REGISTRY
         return reg[self.args.runner](args=self.args, logger=self.logger, log_start_t=log_start_t)

@@ -3,8 +3,8 @@ same keys resolve to the entity-env steppers (see build_stepper)."""
 from .entity_stepper import EntityEpisodeStepper, EntityParallelStepper
 from .parallel_stepper import EnvStepper, EpisodeStepper, ParallelStepper
 from .self_play_stepper import (OpponentMix, SelfPlayDistinctParallelStepper, SelfPlayDistinctStepper,
-                                SelfPlayParallelStepper, SelfPlayPolicyParallelStepper, SelfPlayPolicyStepper,
-                                SelfPlayStepper)
+                                SelfPlayFFParallelStepper, SelfPlayFFStepper, SelfPlayParallelStepper,
+                                SelfPlayPolicyParallelStepper, SelfPlayPolicyStepper, SelfPlayStepper)
 
 REGISTRY = {"episode": EpisodeStepper, "parallel": ParallelStepper}
 SELF_REGISTRY = {"episode": SelfPlayStepper, "parallel": SelfPlayParallelStepper}
@@ -12,6 +12,8 @@ SELF_REGISTRY = {"episode": SelfPlayStepper, "parallel": SelfPlayParallelStepper
 SELF_POLICY_REGISTRY = {"episode": SelfPlayPolicyStepper, "parallel": SelfPlayPolicyParallelStepper}
 # two DistinctMACs (mac: distinct in self-play and the league): one network per agent slot on both sides
 SELF_DISTINCT_REGISTRY = {"episode": SelfPlayDistinctStepper, "parallel": SelfPlayDistinctParallelStepper}
+# two feed-forward MACs (agent: dqn in self-play and the league): no hidden state on either side
+SELF_FF_REGISTRY = {"episode": SelfPlayFFStepper, "parallel": SelfPlayFFParallelStepper}
 ENTITY_REGISTRY = {"episode": EntityEpisodeStepper, "parallel": EntityParallelStepper}
 
 
@@ -22,5 +24,6 @@ def build_stepper(args, logger, log_start_t=0):
 
 __all__ = ["EnvStepper", "OpponentMix", "EpisodeStepper", "ParallelStepper", "SelfPlayParallelStepper", "SelfPlayStepper",
            "SelfPlayPolicyParallelStepper", "SelfPlayPolicyStepper", "SelfPlayDistinctParallelStepper",
-           "SelfPlayDistinctStepper", "EntityParallelStepper", "EntityEpisodeStepper", "REGISTRY", "SELF_REGISTRY",
-           "SELF_POLICY_REGISTRY", "SELF_DISTINCT_REGISTRY", "ENTITY_REGISTRY", "build_stepper"]
+           "SelfPlayDistinctStepper", "SelfPlayFFParallelStepper", "SelfPlayFFStepper", "EntityParallelStepper",
+           "EntityEpisodeStepper", "REGISTRY", "SELF_REGISTRY", "SELF_POLICY_REGISTRY", "SELF_DISTINCT_REGISTRY",
+           "SELF_FF_REGISTRY", "ENTITY_REGISTRY", "build_stepper"]

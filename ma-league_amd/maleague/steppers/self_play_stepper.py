@@ -20,6 +20,10 @@ through the policy softmax with that side's epsilon floor and the action is draw
 Two ``DistinctMAC``s (mac: distinct, one DRQN per agent slot on both sides): ``SelfPlayDistinctParallelStepper`` /
 ``SelfPlayDistinctStepper`` (``SELF_DISTINCT_REGISTRY``) make the same run with one launch of
 ``mlg_rollout_selfplay_distinct``: agent ln of side s acts with network ln of side s's MAC.
+
+Two feed-forward MACs (agent: dqn on both sides): ``SelfPlayFFParallelStepper`` / ``SelfPlayFFStepper``
+(``SELF_FF_REGISTRY``) make the same run with one launch of ``mlg_rollout_selfplay_ff``: selection is epsilon-greedy over
+Q values as in SelfPlayParallelStepper, and no hidden state is carried.
 """
 from __future__ import annotations
 
@@ -34,7 +38,7 @@ from ..components.batch_view import mlg_batch
 from ..components.replay_buffer import RingEpisodeBatch
 from ..controllers.distinct_controller import DistinctMAC
 from ..exceptions import MultiAgentControllerNotInitialized
-from ..modules.agents import DRQNAgentNetwork
+from ..modules.agents import DQNAgentNetwork, DRQNAgentNetwork
 from .parallel_stepper import LazyEnvInfos, ParallelStepper
 
 
@@ -358,3 +362,58 @@ class SelfPlayDistinctParallelStepper(SelfPlayParallelStepper):
 
 class SelfPlayDistinctStepper(_SingleEnv, SelfPlayDistinctParallelStepper):
     """Single-env form of SelfPlayDistinctParallelStepper: B = 1, returns the final env_info dict."""
+
+
+class SelfPlayFFParallelStepper(SelfPlayParallelStepper):
+    """Self-play of two feed-forward MACs (agent: dqn, ``DQNAgentNetwork`` on both sides): one launch of
+    ``mlg_rollout_selfplay_ff`` per run. Selection is SelfPlayParallelStepper's (epsilon-greedy over Q values, one
+    epsilon per side, the same counter-RNG streams), and so are the batches, rewards, run summary and ring / away-batch
+    reuse; ``init_hidden`` of a feed-forward MAC holds nothing the launch reads."""
+
+    def initialize(self, scheme, groups, preprocess, home_mac, away_mac=None):
+        if away_mac is None:
+            raise ValueError("self-play needs an away MAC (initialize(..., home_mac, away_mac))")
+        for side, mac in (("home", home_mac), ("away", away_mac)):
+            if isinstance(mac, DistinctMAC):
+                raise NotImplementedError(f"{type(self).__name__} does not support mac='distinct' (the {side} MAC): "
+                                          "agent='dqn' under mac='distinct' is out of scope; two DistinctMACs of "
+                                          "recurrent networks are SelfPlayDistinctParallelStepper, "
+                                          "steppers.SELF_DISTINCT_REGISTRY['parallel']")
+            if getattr(mac, "agent_output_type", "q") != "q":
+                raise NotImplementedError(f"{type(self).__name__} selects epsilon-greedy over Q values: the {side} "
+                                          f"MAC's agent_output_type={mac.agent_output_type!r} is not supported (COMA "
+                                          "over agent='dqn' is out of scope; two recurrent pi_logits MACs are "
+                                          "SelfPlayPolicyParallelStepper, steppers.SELF_POLICY_REGISTRY['parallel'])")
+            agent = getattr(mac, "agent", None)
+            if isinstance(agent, DRQNAgentNetwork):
+                raise NotImplementedError(f"{type(self).__name__} drives two feed-forward MACs (agent='dqn'): the "
+                                          f"{side} MAC's agent is a DRQNAgentNetwork (a feed-forward side against a "
+                                          "recurrent side is out of scope; two recurrent MACs are "
+                                          "SelfPlayParallelStepper, steppers.SELF_REGISTRY['parallel'])")
+            if not isinstance(agent, DQNAgentNetwork):
+                raise NotImplementedError(f"{type(self).__name__} drives two feed-forward MACs (agent='dqn'): the "
+                                          f"{side} MAC's {type(agent).__name__} is not supported")
+        ParallelStepper.initialize(self, scheme, groups, preprocess, home_mac)
+        self.away_mac = away_mac
+        self._away_buf = None
+
+    def set_opponent_mix(self, mix):
+        if mix is None:
+            return
+        raise NotImplementedError("opponent mixtures with agent='dqn' are not supported (mlg_rollout_selfplay_mix packs "
+                                  "and reads DRQN blocks; a match of feed-forward MACs plays one opponent)")
+
+    def describe_rollout(self):
+        if self.home_mac is None:
+            raise MultiAgentControllerNotInitialized()
+        return _native.rollout_selfplay_ff_describe(self._cspec, self.home_mac.agent.dims())
+
+    def _launch_selfplay(self, st, d, p_h, p_a, mb_h, mb_a, run_info, eps_h, eps_a, test_mode):
+        _native.call("mlg_rollout_selfplay_ff", _native.byref(self._cspec), _native.byref(st), _native.byref(d),
+                     _native.ptr(p_h), _native.ptr(p_a), _native.byref(mb_h), _native.byref(mb_a),
+                     _native.byref(run_info), float(eps_h), float(eps_a), int(bool(test_mode)),
+                     _native.stream_ptr(self.device))
+
+
+class SelfPlayFFStepper(_SingleEnv, SelfPlayFFParallelStepper):
+    """Single-env form of SelfPlayFFParallelStepper: B = 1, returns the final env_info dict."""
