@@ -82,11 +82,11 @@ def policy_agent_params(c):
     return lambda d_in, hidden, n_actions: RS.agent_params(d_in, hidden, n_actions, c.seed)
 
 
-def policy_spec(c):
+def policy_spec(c, grid_size=20, episode_limit=EPISODE_LIMIT):
     from helpers import shape_plan
     from maleague.envs.teams_env import TeamsEnvSpec
-    return TeamsEnvSpec.from_env_args({"match_build_plan": shape_plan(c.plan), "grid_size": 20,
-                                       "stochastic_spawns": True, "episode_limit": EPISODE_LIMIT, "seed": c.seed})
+    return TeamsEnvSpec.from_env_args({"match_build_plan": shape_plan(c.plan), "grid_size": grid_size,
+                                       "stochastic_spawns": True, "episode_limit": episode_limit, "seed": c.seed})
 
 
 def policy_describe(c):
@@ -96,12 +96,15 @@ def policy_describe(c):
     return _native.rollout_policy_describe(spec.to_c(), drqn_dims(spec, c.H))
 
 
-def oracle_policy_run(spec, hidden, seed, scale, mask, episode, mode, n_envs=B, eps=EPS, weights_seed=None):
+def oracle_policy_run(spec, hidden, seed, scale, mask, episode, mode, n_envs=B, eps=EPS, weights_seed=None,
+                      agent_params=None, infos=None):
     """One run of the float64 oracle alone (oracle env, oracle DRQN, coma_ref.softmax_policy) as mlg_rollout_policy
     makes it. mode: "train" (a draw from the probabilities with the epsilon floor), "draw" (test mode without
     test_greedy: a draw from the floor-less probabilities) or "greedy" (the first-index argmax of the masked
     probabilities). -> (batch as host arrays [n_envs, episode_limit + 1, ...], episode lengths, picks, near ties: the
-    picks whose top two masked probabilities lie within DELTA)."""
+    picks whose top two masked probabilities lie within DELTA). ``agent_params``: a callable (d_in, H, n_actions) ->
+    state_dict arrays before the fc2 scale, in place of the seeded draw; ``infos``: a dict that receives env index ->
+    the env's final info."""
     import torch
     import coma_ref as CR
     import envref
@@ -109,8 +112,9 @@ def oracle_policy_run(spec, hidden, seed, scale, mask, episode, mode, n_envs=B, 
     from helpers import ref_envs_for
     N, A, T1 = spec.n_agents, spec.n_actions, spec.episode_limit + 1
     d_in = 8 * spec.U + A + N
-    params = {k: torch.from_numpy(v).double()
-              for k, v in RS.agent_params(d_in, hidden, A, seed if weights_seed is None else weights_seed).items()}
+    drawn = agent_params(d_in, hidden, A) if agent_params is not None else \
+        RS.agent_params(d_in, hidden, A, seed if weights_seed is None else weights_seed)
+    params = {k: torch.from_numpy(v).double() for k, v in drawn.items()}
     params["fc2.weight"] = params["fc2.weight"] * scale
     refs = ref_envs_for(spec, n_envs, seed=seed)
     for r in refs:
@@ -161,7 +165,9 @@ def oracle_policy_run(spec, hidden, seed, scale, mask, episode, mode, n_envs=B, 
             b["state"][e, t], b["obs"][e, t], b["avail_actions"][e, t] = r.state(), obs[e], avail[e]
             b["actions"][e, t, :, 0], b["actions_onehot"][e, t], b["filled"][e, t] = acts[e], last[e], 1
             if status[e] == 0:
-                rew, done, _ = r.step(acts[e])
+                rew, done, info = r.step(acts[e])
+                if done and infos is not None:
+                    infos[e] = info
                 b["reward"][e, t, 0], b["terminated"][e, t, 0] = rew[0], int(done)
                 ep_len[e] = t + 1
                 status[e] = 1 if done else 0

@@ -57,11 +57,11 @@ def plan_of(n_policy, n_scripted):
     return [team_from_codes(codes(n_scripted), True), team_from_codes(codes(n_policy), False)]
 
 
-def spec_of(plan, seed=0):
+def spec_of(plan, seed=0, grid_size=20, episode_limit=EPISODE_LIMIT):
     from helpers import shape_plan
     from maleague.envs.teams_env import TeamsEnvSpec
     return TeamsEnvSpec.from_env_args({"match_build_plan": shape_plan(plan) if isinstance(plan, str) else plan,
-                                       "grid_size": 20, "stochastic_spawns": True, "episode_limit": EPISODE_LIMIT,
+                                       "grid_size": grid_size, "stochastic_spawns": True, "episode_limit": episode_limit,
                                        "seed": seed})
 
 

@@ -78,13 +78,13 @@ def case(cid):
     return next(c for c in CASES if c[0] == cid)
 
 
-def spec_of(plan, seed=0):
+def spec_of(plan, seed=0, grid_size=20, episode_limit=EPISODE_LIMIT):
     """The self-play env spec of a plan name (both teams policy-controlled) or of a list of two team dicts."""
     from helpers import shape_plan
     from maleague.envs.teams_env import TeamsEnvSpec
     return TeamsEnvSpec.from_env_args({"match_build_plan": shape_plan(plan, self_play=True) if isinstance(plan, str)
-                                       else plan, "grid_size": 20, "stochastic_spawns": True,
-                                       "episode_limit": EPISODE_LIMIT, "seed": seed})
+                                       else plan, "grid_size": grid_size, "stochastic_spawns": True,
+                                       "episode_limit": episode_limit, "seed": seed})
 
 
 def dims_of(spec, hidden, last_action=True, agent_id=True):

@@ -103,11 +103,21 @@ def shape_plan(name, self_play=False):
     """match_build_plan for the rollout shape tests: a built-in plan name, or "KvK" (K units per side, unit k of a
     side is TR AR HR TM cyclically, scripted team first), "5v7" (5 policy agents against 7 scripted units, scripted
     team first) or "3v5" (3 policy agents listed first, team 0, against 5 scripted units). self_play: both teams
-    policy-controlled (symmetric plans only)."""
+    policy-controlled (symmetric plans only). Policy-heavy plans name both teams in the order they are listed, a count
+    and "p" (policy) or "s" (scripted) each: "7p2s" is 7 policy units listed first (team 0) against 2 scripted units,
+    "2s7p" the same teams with the scripted one listed first."""
+    import re
     from maleague.envs.plans import available, builtin_plan, team_from_codes
     if name in available():
         return builtin_plan(name, self_play=True) if self_play else name
     codes = lambda k: " ".join(_UNIT_CYCLE[i % 4] for i in range(k))  # noqa: E731
+    heavy = re.fullmatch(r"(\d+)([ps])(\d+)([ps])", name)
+    if heavy:
+        (k0, c0), (k1, c1) = heavy.group(1, 2), heavy.group(3, 4)
+        assert not self_play and {c0, c1} == {"p", "s"}, name
+        policy, scripted = (int(k0), int(k1)) if c0 == "p" else (int(k1), int(k0))
+        assert policy > scripted > 0, name
+        return [team_from_codes(codes(int(k0)), c0 == "s"), team_from_codes(codes(int(k1)), c1 == "s")]
     if name == "5v7":
         assert not self_play
         return [team_from_codes(codes(7), True), team_from_codes(codes(5), False)]
@@ -131,14 +141,14 @@ def drqn_dims(spec, hidden, self_play=False):
 Q_TOL = 1e-4  # the project's bar for Q values and hidden states (fp32 kernels vs the oracle)
 
 
-def build_stepper(device, plan="medium_1h_4t", B=48, episode_limit=40, seed=5, **kw):
+def build_stepper(device, plan="medium_1h_4t", B=48, episode_limit=40, seed=5, grid_size=20, **kw):
     """A ParallelStepper over ``plan`` (a built-in name or a list of two team dicts) with a freshly seeded BasicMAC."""
     import torch
     from maleague.components.episode_batch import EpisodeBatch
     from maleague.controllers import BasicMAC
     from maleague.custom_logging import MainLogger
     from maleague.steppers import ParallelStepper
-    args = qmix_args(batch_size_run=B, seed=seed, env_args={"match_build_plan": plan, "grid_size": 20,
+    args = qmix_args(batch_size_run=B, seed=seed, env_args={"match_build_plan": plan, "grid_size": grid_size,
                                                             "stochastic_spawns": True, "episode_limit": episode_limit},
                      **kw)
     stepper = ParallelStepper(args, MainLogger())
@@ -185,6 +195,10 @@ def check_run(stepper, mac, args, batch, infos, episode, test_mode, eps, envs=No
     assert stepper.t == ep_len.max()
     # --- env side, teacher forced: replay the recorded actions through the C oracle ---
     refs = ref_envs_for(spec, B, seed=args.seed)
+    assert len(infos) == B
+    # infos come in termination order: by episode length, then env index
+    place = np.empty(B, np.int64)
+    place[np.lexsort((np.arange(B), ep_len))] = np.arange(B)
     for b in sub:
         r = refs[b]
         r.episode = episode
@@ -197,20 +211,22 @@ def check_run(stepper, mac, args, batch, infos, episode, test_mode, eps, envs=No
         for t in range(L):
             rew, done, info = r.step(nb["actions"][b, t, :, 0])
             ret += rew[0]
-            assert nb["reward"][b, t, 0] == np.float32(rew[0])
-            assert nb["terminated"][b, t, 0] == int(done) and done == (t == L - 1)
-            np.testing.assert_array_equal(nb["obs"][b, t + 1], r.obs())
-            np.testing.assert_array_equal(nb["state"][b, t + 1], r.state())
-            np.testing.assert_array_equal(nb["avail_actions"][b, t + 1], r.avail())
-        assert rets[b] == np.float32(ret)
-        np.testing.assert_array_equal(nb["filled"][b, :, 0], (np.arange(T1) <= L).astype(np.int64))
+            assert nb["reward"][b, t, 0] == np.float32(rew[0]), ("reward", b, t)
+            assert nb["terminated"][b, t, 0] == int(done) and done == (t == L - 1), ("terminated", b, t, L)
+            np.testing.assert_array_equal(nb["obs"][b, t + 1], r.obs(), err_msg=f"obs env {b} t {t + 1}")
+            np.testing.assert_array_equal(nb["state"][b, t + 1], r.state(), err_msg=f"state env {b} t {t + 1}")
+            np.testing.assert_array_equal(nb["avail_actions"][b, t + 1], r.avail(),
+                                          err_msg=f"avail_actions env {b} t {t + 1}")
+        assert rets[b] == np.float32(ret), ("returns", b)
+        np.testing.assert_array_equal(nb["filled"][b, :, 0], (np.arange(T1) <= L).astype(np.int64),
+                                      err_msg=f"filled env {b}")
         # actions recorded for t = 0..L (the final one after termination), zero beyond
         assert (nb["actions"][b, L + 1:] == 0).all() and (nb["actions_onehot"][b, L + 1:] == 0).all()
         oh = np.zeros((L + 1, N, A), np.float32)
         oh[np.arange(L + 1)[:, None], np.arange(N)[None, :], nb["actions"][b, :L + 1, :, 0]] = 1
         np.testing.assert_array_equal(nb["actions_onehot"][b, :L + 1], oh)
         assert (nb["reward"][b, L:] == 0).all() and (nb["terminated"][b, L:] == 0).all()
-    assert len(infos) == B
+        assert infos[int(place[b])] == info, (b, L, infos[int(place[b])], info)  # the oracle's info of the last step
     # --- agent side: oracle Q on the recorded batch; greedy / epsilon picks bit-exact ---
     tb = {k: torch.from_numpy(v[sub]) for k, v in nb.items()}
     Tm = int(ep_len[sub].max()) + 1
@@ -244,22 +260,22 @@ def check_run(stepper, mac, args, batch, infos, episode, test_mode, eps, envs=No
     return {"greedy": n_checked, "near_ties": n_tie, "epsilon_draws": n_random}
 
 
-def sp_args(B, episode_limit, seed, plan="medium_1h_4t", **kw):
+def sp_args(B, episode_limit, seed, plan="medium_1h_4t", grid_size=20, **kw):
     from maleague.envs.plans import builtin_plan
     mbp = builtin_plan(plan, self_play=True) if isinstance(plan, str) else plan
     return qmix_args(batch_size_run=B, seed=seed,
-                     env_args={"match_build_plan": mbp, "grid_size": 20,
+                     env_args={"match_build_plan": mbp, "grid_size": grid_size,
                                "stochastic_spawns": True, "episode_limit": episode_limit}, **kw)
 
 
-def build_selfplay(device, plan="medium_1h_4t", B=48, episode_limit=40, seed=5, **kw):
+def build_selfplay(device, plan="medium_1h_4t", B=48, episode_limit=40, seed=5, grid_size=20, **kw):
     """A SelfPlayParallelStepper over ``plan`` (both teams policy-controlled) with two freshly seeded BasicMACs."""
     import torch
     from maleague.components.episode_batch import EpisodeBatch
     from maleague.controllers import BasicMAC
     from maleague.custom_logging import MainLogger
     from maleague.steppers import SelfPlayParallelStepper
-    args = sp_args(B, episode_limit, seed, plan, **kw)
+    args = sp_args(B, episode_limit, seed, plan, grid_size=grid_size, **kw)
     stepper = SelfPlayParallelStepper(args, MainLogger())
     info = stepper.get_env_info()
     assert info["n_agents"] % 2 == 0
@@ -546,7 +562,7 @@ def _golden_batch(b, device):
 
 
 def _policy_stepper(device, plan, H, mask, B=17, episode_limit=12, seed=5, agent_params=None, fc2_scale=8.0,
-                    test_greedy=True):
+                    test_greedy=True, grid_size=20):
     """A ParallelStepper with a pi_logits BasicMAC (epsilon 0.3 flat). The agent: torch-seeded, or ``agent_params``, a
     callable (d_in, H, n_actions) -> state_dict arrays; fc2.weight is multiplied by ``fc2_scale`` either way."""
     import torch
@@ -556,7 +572,7 @@ def _policy_stepper(device, plan, H, mask, B=17, episode_limit=12, seed=5, agent
     from maleague.steppers import ParallelStepper
     args = coma_args(batch_size_run=B, seed=seed, rnn_hidden_dim=H, mask_before_softmax=mask, epsilon_start=0.3,
                      epsilon_finish=0.3, test_greedy=test_greedy,
-                     env_args={"match_build_plan": plan, "grid_size": 20, "stochastic_spawns": True,
+                     env_args={"match_build_plan": plan, "grid_size": grid_size, "stochastic_spawns": True,
                                "episode_limit": episode_limit})
     stepper = ParallelStepper(args, MainLogger())
     info = stepper.get_env_info()
