@@ -385,6 +385,29 @@ int mlg_refil_rollout(const MlgEntityEnvSpec *spec, MlgEnvState *st, const MlgRe
 int mlg_refil_rollout_describe(const MlgEntityEnvSpec *spec, const MlgRefilDims *d, char *name, int32_t name_cap,
                                int64_t *lds_bytes);
 
+/* One SelfPlayParallelStepper.run over the two-policy entity env (DESIGN.md §3b'): both teams are policy-controlled
+ * (spec->base: n_policy_teams = 2, scripted = [0, 0], n_agents = 2S, agent_unit[a] = a; home = units 0..S-1, away =
+ * units S..2S-1), an EntityMAC on each side. `d` describes ONE side (n_agents = S, n_entities = 2S); both packed blocks
+ * are mlg_refil_pack_agent's, 16-byte aligned. The home batch is what mlg_refil_rollout records (raw unit order and
+ * action indices, team 0's reward). The away batch holds the same state in the canonical view: entity j' = unit
+ * (j' + S) mod 2S, x mirrored to G - 1 - x, team flipped, obs_mask / entity_mask permuted the same way, actions 3 / 4
+ * swapped and target 5 + j' = raw target 5 + (j' + S) mod 2S in avail, actions, actions_onehot and the last-action
+ * columns; team 1's reward; terminated / filled as home. The env executes the raw image of the away choice (an
+ * unavailable choice is a no-op). Epsilon per side, RNG stream index = global agent index (home n, away S + n); the
+ * random action is the k-th available in the side's own index order. One launch, no host wait. Each batch honours
+ * ring_slot0 / ring_size / full_write / slot_extent on its own. info->ret / ret_away = the two returns, won[2b] = home;
+ * agent_rows counts both sides. entity_last_action may be 0 (no last-action columns). */
+int mlg_refil_rollout_selfplay(const MlgEntityEnvSpec *spec, MlgEnvState *st, const MlgRefilDims *d,
+                               const float *home_packed, const float *away_packed, MlgEntityBatch *home,
+                               MlgEntityBatch *away, MlgRunInfo *info, float eps_home, float eps_away,
+                               int32_t test_mode, void *stream);
+/* Host only, launches nothing (the contract of mlg_refil_rollout_describe). Names: "sp-ro2/kc1", "sp-ro2/kc2",
+ * "sp-ro2/kc3" (two envs per wave, both sides' agent phases per step; entity input width 16 / 32 / 48).
+ * mlg_refil_rollout_selfplay takes its decision from the same function. Nonzero (mlg_last_error) where it would refuse
+ * the spec or dims. */
+int mlg_refil_rollout_selfplay_describe(const MlgEntityEnvSpec *spec, const MlgRefilDims *d, char *name,
+                                        int32_t name_cap, int64_t *lds_bytes);
+
 /* EntityAttentionLayer.forward (src/marl/modules/layers/attention.py:24-79; in = embed = out = 64, 4 heads) over bs
  * items: x [bs][ne][64], pre_mask [bs][nq][ne], post_mask [bs][nq] (uint8, 1 = masked) -> y [bs][nq][64]. Forward
  * only: its backward is mlg_refil_attention_backward below. */

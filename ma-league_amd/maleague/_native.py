@@ -182,6 +182,8 @@ SIGNATURES = {
     "mlg_refil_agent_forward": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "mlg_refil_rollout": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
     "mlg_refil_rollout_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
+    "mlg_refil_rollout_selfplay": (ctypes.c_int, [_P] * 8 + [ctypes.c_float, ctypes.c_float, _I, _P]),
+    "mlg_refil_rollout_selfplay_describe": (ctypes.c_int, [_P, _P, _P, _I, _P]),
     "mlg_refil_attention": (ctypes.c_int, [_P] * 6 + [_I] * 4 + [_P] * 2),
     "mlg_refil_packed_mixer_size": (ctypes.c_int64, [_P]),
     "mlg_refil_pack_mixer": (ctypes.c_int, [_P, _P, _P, _P]),
@@ -393,6 +395,20 @@ def refil_rollout_describe(spec: MlgEntityEnvSpec, dims: MlgRefilDims) -> tuple[
     rc = lib.mlg_refil_rollout_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name), ctypes.byref(lds))
     if rc != 0:
         raise NativeError(f"mlg_refil_rollout_describe failed: {lib.mlg_last_error().decode()}")
+    return name.value.decode(), int(lds.value)
+
+
+def refil_rollout_selfplay_describe(spec: MlgEntityEnvSpec, dims: MlgRefilDims) -> tuple[str, int]:
+    """(arm name "sp-ro2/kc1" | "sp-ro2/kc2" | "sp-ro2/kc3", dynamic LDS bytes) of the launch mlg_refil_rollout_selfplay
+    would make for this two-policy entity spec and one side's agent dims (mlg_refil_rollout_selfplay_describe: host
+    only, needs no GPU)."""
+    lib = load()
+    name = ctypes.create_string_buffer(32)
+    lds = ctypes.c_int64(0)
+    rc = lib.mlg_refil_rollout_selfplay_describe(ctypes.byref(spec), ctypes.byref(dims), name, len(name),
+                                                 ctypes.byref(lds))
+    if rc != 0:
+        raise NativeError(f"mlg_refil_rollout_selfplay_describe failed: {lib.mlg_last_error().decode()}")
     return name.value.decode(), int(lds.value)
 
 

@@ -7,6 +7,11 @@ reference ships no env producing it (REFIL is vendored, unwired) a
 build defines one on top of spec v1: S unit slots per team (policy team = entities 0..S-1, scripted basic-AI
 team = S..2S-1), k ~ U{min_agents..max_agents} active slots per team per episode, absent slots padded and
 masked. Executed by the HIP kernel mlg_refil_rollout; checked bit-exact against oracle/env_ref.c.
+
+``self_play=True`` is the two-policy variant (DESIGN.md §3b'): both teams policy-controlled (``scripted = [0, 0]``,
+``n_policy_teams = 2``, ``n_agents = 2S`` with ``agent_unit[a] = a``; home = units 0..S-1, away = units S..2S-1),
+executed by mlg_refil_rollout_selfplay. Everything else (reset, the per-episode k, resolution, rewards per team) is
+the same env.
 """
 from __future__ import annotations
 
@@ -30,9 +35,10 @@ class EntityEnvSpec:
     episode_limit: int = DEFAULT_EPISODE_LIMIT
     stochastic: bool = True
     seed: int = 0
+    self_play: bool = False  # both teams policy-controlled (§3b')
 
     @classmethod
-    def from_env_args(cls, env_args: dict, config_dir: str | None = None) -> "EntityEnvSpec":
+    def from_env_args(cls, env_args: dict, config_dir: str | None = None, self_play: bool = False) -> "EntityEnvSpec":
         plan = env_args.get("match_build_plan", "refil_8")
         if isinstance(plan, str) and plan in ("refil_8",):
             units = builtin_composition(plan)
@@ -52,7 +58,8 @@ class EntityEnvSpec:
         return cls(roles=roles, melees=melees, min_agents=kmin, max_agents=kmax,
                    grid=int(env_args.get("grid_size", 20)),
                    episode_limit=int(env_args.get("episode_limit", DEFAULT_EPISODE_LIMIT)),
-                   stochastic=bool(env_args.get("stochastic_spawns", True)), seed=int(env_args.get("seed", 0) or 0))
+                   stochastic=bool(env_args.get("stochastic_spawns", True)), seed=int(env_args.get("seed", 0) or 0),
+                   self_play=bool(self_play))
 
     @property
     def S(self) -> int:
@@ -64,7 +71,11 @@ class EntityEnvSpec:
 
     @property
     def n_agents(self) -> int:
-        return self.S
+        return 2 * self.S if self.self_play else self.S
+
+    @property
+    def n_policy_teams(self) -> int:
+        return 2 if self.self_play else 1
 
     @property
     def n_entities(self) -> int:
@@ -85,16 +96,16 @@ class EntityEnvSpec:
         c = _native.MlgEntityEnvSpec()
         s = c.base
         S = self.S
-        s.U, s.n_agents, s.n_actions = self.U, S, self.n_actions
+        s.U, s.n_agents, s.n_actions = self.U, self.n_agents, self.n_actions
         s.grid, s.episode_limit, s.stochastic = self.grid, self.episode_limit, int(self.stochastic)
-        s.policy_team, s.n_policy_teams = 0, 1
+        s.policy_team, s.n_policy_teams = 0, self.n_policy_teams
         for u in range(self.U):
             s.team[u] = 0 if u < S else 1
             s.role[u] = self.roles[u % S]
             s.melee[u] = self.melees[u % S]
-        for a in range(S):
+        for a in range(self.n_agents):
             s.agent_unit[a] = a
-        s.scripted[0], s.scripted[1] = 0, 1
+        s.scripted[0], s.scripted[1] = 0, 0 if self.self_play else 1
         s.seed = self.seed & 0xFFFFFFFFFFFFFFFF
         c.min_agents, c.max_agents = self.min_agents, self.max_agents
         return c

@@ -29,6 +29,7 @@ import torch
 
 from .. import _native
 from ..envs.plans import mirror_plan
+from ..exceptions import refuse_entity_league
 from ..envs.teams_env import TeamsEnvSpec
 from .teams import match_plan
 
@@ -149,6 +150,7 @@ class CrossPlayEvaluator:
     def __init__(self, args, device, episodes_per_launch: Optional[int] = None):
         self.args = args
         self.device = torch.device(device)
+        refuse_entity_league(args, type(self).__name__)
         self._check_output_type(args)
         self._check_agent(args)
         self._check_mac(args)
@@ -395,6 +397,7 @@ def evaluator_for(args, device, episodes_per_launch: Optional[int] = None) -> Cr
     """The evaluator of ``args``: DistinctCrossPlayEvaluator for mac 'distinct' with agent_output_type 'q',
     FFCrossPlayEvaluator for agent 'dqn' with mac 'basic' and agent_output_type 'q', else by
     ``args.agent_output_type``: PolicyCrossPlayEvaluator for 'pi_logits', else CrossPlayEvaluator."""
+    refuse_entity_league(args, "evaluator_for")
     out = getattr(args, "agent_output_type", "q")
     if getattr(args, "mac", "basic") == "distinct" and out == "q":
         cls = DistinctCrossPlayEvaluator

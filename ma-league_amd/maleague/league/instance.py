@@ -24,6 +24,7 @@ import torch
 import torch.distributed as dist
 
 from ..envs.plans import mirror_plan
+from ..exceptions import refuse_entity_league
 from ..runs import LeagueExperiment, MultiAgentExperiment
 from ..runs.sp_ma_experiment import agent_vector, load_agent_vector
 from .distributed import DistributedLeague
@@ -61,6 +62,7 @@ class LeagueInstance:
         if int(opponents_per_match) < 1:
             raise ValueError(f"opponents_per_match={opponents_per_match} must be >= 1")
         self.opponents_per_match = int(opponents_per_match)
+        refuse_entity_league(args, type(self).__name__)
         if self.opponents_per_match > 1 and getattr(args, "agent_output_type", "q") == "pi_logits":
             raise NotImplementedError(f"LeagueInstance(opponents_per_match={self.opponents_per_match}): opponent "
                                       "mixtures with agent_output_type='pi_logits' are not supported (a pi_logits "
@@ -345,6 +347,7 @@ class DistinctLeagueInstance(LeagueInstance):
 
 def league_instance_for(args, logger, league, **kw) -> LeagueInstance:
     """The league instance of ``args.mac``: DistinctLeagueInstance for 'distinct', else LeagueInstance."""
+    refuse_entity_league(args, "league_instance_for")
     cls = DistinctLeagueInstance if getattr(args, "mac", "basic") == "distinct" else LeagueInstance
     return cls(args, logger, league, **kw)
 

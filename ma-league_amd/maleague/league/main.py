@@ -203,6 +203,8 @@ def main(argv=None) -> dict:
     cfg["matchmaking"] = matchmaking
     cfg["league_eval_seed"] = seed  # one env seed for every rank's share of the evaluation pairs (equal terms)
     args = to_args(cfg)
+    from maleague.exceptions import refuse_entity_league
+    refuse_entity_league(args, "league/main.py")
 
     from maleague.league import DistributedLeague, PayoffEntry, league_instance_for
     max_hist = a.max_historical if a.max_historical is not None else 4 * world

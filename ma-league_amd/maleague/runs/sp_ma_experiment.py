@@ -7,6 +7,9 @@ fused rollout launch (SelfPlayParallelStepper), only the home learner trains (sp
 With ``mac: distinct`` both MACs are DistinctMACs (one network per agent slot) and the launch is
 SelfPlayDistinctParallelStepper's; an agent vector is then the N networks back to back, agent 0 first, each in
 named_parameters() order (the learner's flat layout).
+
+With ``entity_scheme`` (REFIL, attn_qmix, attn_vdn) both MACs are EntityMACs over the two-policy entity env and the
+launch is SelfPlayEntityParallelStepper's (DESIGN.md §3b', §4c''): each side's MAC sees S agents among 2S entities.
 """
 from __future__ import annotations
 
@@ -19,6 +22,7 @@ from ..controllers.distinct_controller import DistinctMAC
 from ..learners.q_learner import FlatParams
 from ..utils.flat import module_flat_view
 from ..steppers import SELF_DISTINCT_REGISTRY as self_distinct_steppers_REGISTRY
+from ..steppers import SELF_ENTITY_REGISTRY as self_entity_steppers_REGISTRY
 from ..steppers import SELF_FF_REGISTRY as self_ff_steppers_REGISTRY
 from ..steppers import SELF_POLICY_REGISTRY as self_policy_steppers_REGISTRY
 from ..steppers import SELF_REGISTRY as self_steppers_REGISTRY
@@ -94,6 +98,9 @@ class SelfPlayMultiAgentExperiment(MultiAgentExperiment):
                              "scenario. Ensure the Self-Play scenario has two team set to is_scripted=False")
         env_scheme = {"n_agents": total_n_agents // 2, "n_actions": int(self.env_info["n_actions"]),
                       "state_shape": int(self.env_info["state_shape"]), "total_n_agents": total_n_agents}
+        if getattr(self.args, "entity_scheme", False):  # one side's EntityMAC: S agents among all 2S entities
+            env_scheme.update(n_entities=int(self.env_info["n_entities"]),
+                              entity_shape=int(self.env_info["entity_shape"]))
         self._update_args(env_scheme)
         self.stepper.args = self.args
         return env_scheme
@@ -102,7 +109,11 @@ class SelfPlayMultiAgentExperiment(MultiAgentExperiment):
         # two pi_logits MACs (COMA) roll out through the policy softmax and the multinomial draw
         # two DistinctMACs (mac: distinct) through mlg_rollout_selfplay_distinct
         # two feed-forward MACs (agent: dqn) through mlg_rollout_selfplay_ff
-        if getattr(self.args, "mac", "basic") == "distinct":
+        # two EntityMACs (entity_scheme: REFIL, attn_qmix, attn_vdn) through mlg_refil_rollout_selfplay over the
+        # two-policy entity env (the stepper builds its spec with self_play=True)
+        if getattr(self.args, "entity_scheme", False):
+            reg = self_entity_steppers_REGISTRY
+        elif getattr(self.args, "mac", "basic") == "distinct":
             reg = self_distinct_steppers_REGISTRY
         elif getattr(self.args, "agent_output_type", "q") == "pi_logits":
             reg = self_policy_steppers_REGISTRY

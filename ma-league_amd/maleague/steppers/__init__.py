@@ -3,7 +3,7 @@ same keys resolve to the entity-env steppers (see build_stepper)."""
 from .entity_stepper import EntityEpisodeStepper, EntityParallelStepper
 from .parallel_stepper import EnvStepper, EpisodeStepper, ParallelStepper
 from .self_play_stepper import (OpponentMix, SelfPlayDistinctParallelStepper, SelfPlayDistinctStepper,
-                                SelfPlayFFParallelStepper, SelfPlayFFStepper, SelfPlayParallelStepper,
+                                SelfPlayEntityParallelStepper, SelfPlayEntityStepper, SelfPlayFFParallelStepper, SelfPlayFFStepper, SelfPlayParallelStepper,
                                 SelfPlayPolicyParallelStepper, SelfPlayPolicyStepper, SelfPlayStepper)
 
 REGISTRY = {"episode": EpisodeStepper, "parallel": ParallelStepper}
@@ -15,6 +15,8 @@ SELF_DISTINCT_REGISTRY = {"episode": SelfPlayDistinctStepper, "parallel": SelfPl
 # two feed-forward MACs (agent: dqn in self-play and the league): no hidden state on either side
 SELF_FF_REGISTRY = {"episode": SelfPlayFFStepper, "parallel": SelfPlayFFParallelStepper}
 ENTITY_REGISTRY = {"episode": EntityEpisodeStepper, "parallel": EntityParallelStepper}
+# two EntityMACs (REFIL, attn_qmix, attn_vdn in self-play): the two-policy entity env, away side in the canonical view
+SELF_ENTITY_REGISTRY = {"episode": SelfPlayEntityStepper, "parallel": SelfPlayEntityParallelStepper}
 
 
 def build_stepper(args, logger, log_start_t=0):
@@ -25,5 +27,5 @@ def build_stepper(args, logger, log_start_t=0):
 __all__ = ["EnvStepper", "OpponentMix", "EpisodeStepper", "ParallelStepper", "SelfPlayParallelStepper", "SelfPlayStepper",
            "SelfPlayPolicyParallelStepper", "SelfPlayPolicyStepper", "SelfPlayDistinctParallelStepper",
            "SelfPlayDistinctStepper", "SelfPlayFFParallelStepper", "SelfPlayFFStepper", "EntityParallelStepper",
-           "EntityEpisodeStepper", "REGISTRY", "SELF_REGISTRY", "SELF_POLICY_REGISTRY", "SELF_DISTINCT_REGISTRY",
-           "SELF_FF_REGISTRY", "ENTITY_REGISTRY", "build_stepper"]
+           "EntityEpisodeStepper", "SelfPlayEntityParallelStepper", "SelfPlayEntityStepper", "REGISTRY", "SELF_REGISTRY", "SELF_POLICY_REGISTRY", "SELF_DISTINCT_REGISTRY",
+           "SELF_FF_REGISTRY", "ENTITY_REGISTRY", "SELF_ENTITY_REGISTRY", "build_stepper"]

@@ -24,6 +24,11 @@ Two ``DistinctMAC``s (mac: distinct, one DRQN per agent slot on both sides): ``S
 Two feed-forward MACs (agent: dqn on both sides): ``SelfPlayFFParallelStepper`` / ``SelfPlayFFStepper``
 (``SELF_FF_REGISTRY``) make the same run with one launch of ``mlg_rollout_selfplay_ff``: selection is epsilon-greedy over
 Q values as in SelfPlayParallelStepper, and no hidden state is carried.
+
+Two ``EntityMAC``s (REFIL, attn_qmix, attn_vdn: ``entity_scheme``): ``SelfPlayEntityParallelStepper`` /
+``SelfPlayEntityStepper`` (``SELF_ENTITY_REGISTRY``) run the two-policy entity env (DESIGN.md §3b') with one launch of
+``mlg_refil_rollout_selfplay``: both batches are entity batches, the away one in the canonical view, so a network
+trained as home plays away unchanged.
 """
 from __future__ import annotations
 
@@ -34,9 +39,12 @@ from typing import Optional, Sequence
 import torch
 
 from .. import _native
-from ..components.batch_view import mlg_batch
+from ..components.batch_view import mlg_entity_batch
 from ..components.replay_buffer import RingEpisodeBatch
 from ..controllers.distinct_controller import DistinctMAC
+from ..controllers.entity_controller import EntityMAC
+from ..envs.entity_env import EntityEnvSpec
+from ..envs.teams_env import _enum_name, load_match_build_plan
 from ..exceptions import MultiAgentControllerNotInitialized
 from ..modules.agents import DQNAgentNetwork, DRQNAgentNetwork
 from .parallel_stepper import LazyEnvInfos, ParallelStepper
@@ -185,14 +193,14 @@ class SelfPlayParallelStepper(ParallelStepper):
             ring = None
         if ring is not None:
             slot0 = ring.buffer_index
-            mb_h, k = mlg_batch(ring)
+            mb_h, k = self._to_mlg(ring)
             keep.append(k)
             mb_h.B, mb_h.ring_slot0, mb_h.ring_size, mb_h.full_write = self.batch_size, slot0, ring.buffer_size, 1
             mb_h.slot_extent = ring.extent_ptr()
             self.home_batch = RingEpisodeBatch(ring, slot0, self.batch_size)
         else:
             self.home_batch = self.new_batch_fn()
-            mb_h, k = mlg_batch(self.home_batch)
+            mb_h, k = self._to_mlg(self.home_batch)
             keep.append(k)
         if getattr(self.args, "reuse_away_batch", True):
             # one away batch, rewritten in full-write mode by every run (every byte of its B slots is stored,
@@ -206,12 +214,12 @@ class SelfPlayParallelStepper(ParallelStepper):
                 self._away_extent = torch.full((self.batch_size,), self.episode_limit + 1, dtype=torch.int32,
                                                device=self.device)
             self.away_batch = self._away_buf
-            mb_a, k = mlg_batch(self.away_batch)
+            mb_a, k = self._to_mlg(self.away_batch)
             mb_a.full_write = 1
             mb_a.slot_extent = self._away_extent.data_ptr()
         else:
             self.away_batch = self.new_batch_fn()
-            mb_a, k = mlg_batch(self.away_batch)
+            mb_a, k = self._to_mlg(self.away_batch)
         keep.append(k)
         h_agent, a_agent = self._packers()
         d, d_a = h_agent.dims(), a_agent.dims()
@@ -417,3 +425,76 @@ class SelfPlayFFParallelStepper(SelfPlayParallelStepper):
 
 class SelfPlayFFStepper(_SingleEnv, SelfPlayFFParallelStepper):
     """Single-env form of SelfPlayFFParallelStepper: B = 1, returns the final env_info dict."""
+
+
+class SelfPlayEntityParallelStepper(SelfPlayParallelStepper):
+    """Self-play of two ``EntityMAC``s over the two-policy entity env (DESIGN.md §3b'): one launch of
+    ``mlg_refil_rollout_selfplay`` per run. The home batch is what EntityParallelStepper records; the away batch is the
+    same run in the canonical view (own team first, x mirrored, team flipped, actions remapped) with team 1's reward.
+    Selection is SelfPlayParallelStepper's (epsilon-greedy over Q values, one epsilon per side, the same counter-RNG
+    streams), and so are the run summary and the ring / away-batch reuse. The entity spec has one roster for both teams
+    and no opponent pool: mixtures and plans whose two teams differ are refused."""
+
+    _batch_keys = ("entities", "obs_mask", "entity_mask", "actions", "avail_actions", "reward", "terminated",
+                   "actions_onehot", "filled")
+
+    def _build_spec(self, env_args, config_dir):
+        return EntityEnvSpec.from_env_args(env_args, config_dir, self_play=True)
+
+    def _to_mlg(self, batch):
+        return mlg_entity_batch(batch)
+
+    def initialize(self, scheme, groups, preprocess, home_mac, away_mac=None):
+        if away_mac is None:
+            raise ValueError("self-play needs an away MAC (initialize(..., home_mac, away_mac))")
+        for side, mac in (("home", home_mac), ("away", away_mac)):
+            if not isinstance(mac, EntityMAC):
+                raise NotImplementedError(f"{type(self).__name__} drives two EntityMACs (mac='entity_mac'): the {side} "
+                                          f"MAC is a {type(mac).__name__} (an entity side against an obs / state side "
+                                          "is out of scope; two BasicMACs are steppers.SELF_REGISTRY)")
+            if getattr(mac, "agent_output_type", "q") != "q":
+                raise NotImplementedError(f"{type(self).__name__} selects epsilon-greedy over Q values: the {side} "
+                                          f"MAC's agent_output_type={mac.agent_output_type!r} is not supported")
+        d, d_a = home_mac.agent.dims(), away_mac.agent.dims()
+        if any(getattr(d, f) != getattr(d_a, f) for f, _ in d._fields_):
+            raise ValueError("home and away EntityMACs must have the same architecture (equal agent dims)")
+        ParallelStepper.initialize(self, scheme, groups, preprocess, home_mac)
+        self.away_mac = away_mac
+        self._away_buf = None
+
+    def set_opponent_mix(self, mix):
+        if mix is None:
+            return
+        raise NotImplementedError(f"{type(self).__name__}.set_opponent_mix: opponent mixtures over entity agents are "
+                                  "not supported (mlg_rollout_selfplay_mix packs DRQN blocks and reads one roster per "
+                                  "opponent; the entity env spec has one roster: a match of EntityMACs plays one "
+                                  "opponent)")
+
+    def _spec_of_plan(self, plan):
+        if not (isinstance(plan, str) and plan in ("refil_8",)):
+            teams = load_match_build_plan(plan, getattr(self.args, "config_dir", None))
+            rosters = [[(_enum_name(u["role"]), _enum_name(u.get("attack_type", "RANGED"))) for u in t["units"]]
+                       for t in teams]
+            if any(r != rosters[0] for r in rosters[1:]):
+                raise NotImplementedError(f"{type(self).__name__}.set_match_build_plan: the plan's two teams differ "
+                                          f"({rosters[0]} vs {next(r for r in rosters[1:] if r != rosters[0])}); the "
+                                          "entity env spec has one roster for both teams (per-team rosters are out of "
+                                          "scope)")
+        return super()._spec_of_plan(plan)
+
+    def describe_rollout(self):
+        """(arm name, dynamic LDS bytes) of the launch run() would make (mlg_refil_rollout_selfplay_describe: host
+        only)."""
+        if self.home_mac is None:
+            raise MultiAgentControllerNotInitialized()
+        return _native.refil_rollout_selfplay_describe(self._cspec, self.home_mac.agent.dims())
+
+    def _launch_selfplay(self, st, d, p_h, p_a, mb_h, mb_a, run_info, eps_h, eps_a, test_mode):
+        _native.call("mlg_refil_rollout_selfplay", _native.byref(self._cspec), _native.byref(st), _native.byref(d),
+                     _native.ptr(p_h), _native.ptr(p_a), _native.byref(mb_h), _native.byref(mb_a),
+                     _native.byref(run_info), float(eps_h), float(eps_a), int(bool(test_mode)),
+                     _native.stream_ptr(self.device))
+
+
+class SelfPlayEntityStepper(_SingleEnv, SelfPlayEntityParallelStepper):
+    """Single-env form of SelfPlayEntityParallelStepper: B = 1, returns the final env_info dict."""
